@@ -26,12 +26,19 @@
     is computed from.
   * --curve: the whole weak-scaling curve (1, 2, 4, ... N ranks, one launch each) in ONE invocation, one JSON line with
     `curve: [{n, value, per_rank_ms_min_max, rccl_ranks, efficiency_vs_1}]`.
-  * K < 500 (the driver's --steps 20): `roofline.frac` / `achieved` are priced on 1000 further steps of the same loop, run
-    right behind the timed K (`priced_on`); the K-step sample is `frac_timed_region`.  `value` is always the K timed steps.
+  * --dump-outputs DIR: after the timed steps, the features the last timed step returned are written as DIR/<name>.npy
+    (float32; rank 0's shard).  The inputs are seeded, so the same arguments give the same inputs on every run and two
+    builds can be compared output for output.  Over the size budget, a fixed seeded sample of whole clips is written.
 
-Prints ONE JSON line on rank 0 with the driver's fields plus `roofline` (dominant kernel vs the HBM roofline, timed
-live with HIP events on the launch stream; `traffic` measured in-run with rocprofv3 PMC passes when rocprofv3 is on
-PATH) and `cpu_baseline` (the reference's CPU composition timed on this box's host cores).
+A plain run (set-up, warm-up, the K timed steps, the dump if asked for) prints ONE JSON line on rank 0 with the driver's
+fields.  --full adds everything else the line used to carry, each measured after and outside the timed K steps:
+  * `roofline` (dominant kernel vs the HBM roofline, timed live with HIP events on the launch stream; `traffic` measured
+    in-run with rocprofv3 PMC passes when rocprofv3 is on PATH).  K < 500 (the driver's --steps 20): `roofline.frac` /
+    `achieved` are priced on 1000 further steps of the same loop, run right behind the timed K (`priced_on`); the K-step
+    sample is `frac_timed_region`.  `value` is always the K timed steps.
+  * `box_calibration` (copy rate and ALU clock of the box), `configs` (the other BASELINE configs) and `cpu_baseline`
+    (the reference's CPU composition timed on this box's host cores); --no-configs / --no-traffic / --no-cpu-baseline
+    leave single legs out.
 """
 import argparse
 import csv
@@ -216,6 +223,33 @@ def cpu_model():
     return None
 
 
+DUMP_BUDGET_BYTES = 32_000_000    # per array; --dump-outputs writes one array (at most 64 MB in all)
+DUMP_SEED = 0
+
+
+def dump_rows(n_rows, row_bytes):
+    """Indices of the clips --dump-outputs writes: all of them when they fit the budget, else a fixed seeded sample (the same
+    rows on every run and every build), in ascending order."""
+    import numpy as np
+    k = max(1, min(n_rows, DUMP_BUDGET_BYTES // max(row_bytes, 1)))
+    if k == n_rows:
+        return np.arange(n_rows)
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(n_rows, size=k, replace=False))
+
+
+def dump_outputs(dirname, name, y):
+    """`y` (clips first) as dirname/<name>.npy in float32; see dump_rows."""
+    import numpy as np
+    import torch
+    rows = dump_rows(y.shape[0], y[0].numel() * 4)
+    a = y.detach().index_select(0, torch.as_tensor(rows, device=y.device)).float().cpu().numpy()
+    os.makedirs(dirname, exist_ok=True)
+    path = os.path.join(dirname, name + ".npy")
+    np.save(path, a)
+    print(f"[bench] wrote {path}: {a.shape} float32, clips {'all' if len(rows) == y.shape[0] else rows.tolist()} "
+          f"of {y.shape[0]} (seed {DUMP_SEED})", file=sys.stderr, flush=True)
+
+
 def pmc_child():
     """A few launches of the bench's own loop body for a rocprofv3 counter pass."""
     import torch
@@ -245,7 +279,7 @@ def selftest_cpu(args, world, rank, launched):
         ranks = int(one.item())
         assert ranks == world
     from audio_amd import distributed as D
-    x = torch.randn(4, 16000)
+    x = torch.randn(4, 16000, generator=torch.Generator().manual_seed(1234 + rank))
     w = torch.hann_window(N_FFT)
 
     def cpu_step():
@@ -262,11 +296,13 @@ def selftest_cpu(args, world, rank, launched):
         dist.barrier()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        cpu_step()
+        z = cpu_step()
     mine = time.perf_counter() - t0
     if dist is not None:
         dist.barrier()
     t = torch.tensor([time.perf_counter() - t0], dtype=torch.float64)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, "selftest", z)
     per_rank = None
     if dist is not None:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -311,7 +347,7 @@ def free_port():
 def curve(args):
     """`--curve`: one child launch per point (1, 2, 4, ..., N ranks; N itself if it is not a power of two), each the exact
     command the driver would run for that N, so a point of the curve and a stand-alone run are the same measurement.  Side
-    measurements (configs, PMC passes, CPU baseline) run once, at N = 1.  The efficiency printed here is value(n) / (n x
+    measurements (--full: configs, PMC passes, CPU baseline) run once, at N = 1.  The efficiency printed here is value(n) / (n x
     value(1)) -- a convenience; the driver computes its own from its own runs."""
     ns, n = [], 1
     while n < args.gpus:
@@ -383,11 +419,17 @@ def main():
                          "captured ONCE, before the timed region, in a HIP graph (K kernel nodes over the rotating batches) and "
                          "replayed inside it.  Measured in round 6 (profiles/r06_zv_launch_modes.txt): the graph's kernel nodes "
                          "run 83-90 us apart where eager launches run 70-71 us apart -- not the default")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed K steps, also measure the roofline (with rocprofv3 PMC passes), the box calibration, "
+                         "the other BASELINE configs and the CPU baseline, and report them in the line (off by default)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the features of the last timed step as DIR/<name>.npy (float32, at most 64 MB in all: a fixed "
+                         "seeded sample of clips when the batch is larger)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-configs", action="store_true",
-                    help="skip the other BASELINE configs (cfg3 / cfg4 / cfg5a / cfg5b shards, measured after the timed K steps "
-                         "at N = 1 and reported under `configs`)")
-    ap.add_argument("--no-traffic", action="store_true", help="skip the in-run rocprofv3 PMC passes")
+                    help="with --full: skip the other BASELINE configs (cfg3 / cfg4 / cfg5a / cfg5b shards, measured after the "
+                         "timed K steps at N = 1 and reported under `configs`)")
+    ap.add_argument("--no-traffic", action="store_true", help="with --full: skip the in-run rocprofv3 PMC passes")
     ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--selftest-cpu", action="store_true",
                     help="plumbing self-test WITHOUT GPUs (tests/test_bench_cli.py): same launch / rendezvous / barrier / "
@@ -399,6 +441,8 @@ def main():
                          "{n, value, ms_per_step, per_rank_ms_min_max, rccl_ranks, efficiency_vs_1} per point; the top-level "
                          "fields are those of the largest N.  Only from a plain `python bench.py` (not under torchrun).")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1: `ms_per_step` is the time of one timed step")
     if args.pmc_child:
         return pmc_child()
 
@@ -527,8 +571,13 @@ def main():
         torch.cuda.synchronize()
         wall = time.perf_counter() - t0
     kernel_ms = e0.elapsed_time(e1) / args.steps
+    y = ys[(args.steps - 1) % ring]                          # what the last timed step returned
+    n_frames = y.shape[-1]
+    assert tuple(y.shape) == (batch, n_out, n_frames) and n_frames == 1001
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, "melspectrogram" if args.op == "mel" else "mfcc", y)
     eager_ms = None
-    if graph is not None:
+    if graph is not None and args.full:
         # the same K steps with one Python call per step (rounds 1-5's timed region), host clock, outside the timed region
         with torch.no_grad():
             torch.cuda.synchronize()
@@ -537,9 +586,8 @@ def main():
                 step(i)
             torch.cuda.synchronize()
             eager_ms = (time.perf_counter() - te) / args.steps * 1e3
-    y = ys[(args.steps - 1) % ring] if args.steps else run(xs[0])
     steady = None
-    if args.steps < 500:
+    if args.full and args.steps < 500:
         # a short timed region (the driver's --steps 20 is 1.4 ms of GPU time) is a small sample: the same loop over 1000 more
         # steps, OUTSIDE the timed K and never used for `value`, is reported beside it
         with torch.no_grad():
@@ -553,26 +601,28 @@ def main():
         steady = {"steps": 1000, "ms_per_step": s0.elapsed_time(s1) / 1000.0,
                   "note": "outside the timed region; not used for `value` / `ms_per_step`"}
 
-    # box calibration, outside the timed region: a plain device-to-device copy of one input batch (read + write).  Boxes of
-    # this pool differ (the same kernel ran 66 us on most and 94 us on one, profiles/r03_zz_lfilter_issue.txt); the copy rate
-    # measured in the same process says which kind this run was on
-    with torch.no_grad():
-        dst = torch.empty_like(xs[0])
-        for i in range(10):
-            dst.copy_(xs[i % ring])
-        torch.cuda.synchronize()
-        c0, c1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        c0.record()
-        for i in range(50):
-            dst.copy_(xs[i % ring])
-        c1.record()
-        torch.cuda.synchronize()
-        copy_ms = c0.elapsed_time(c1) / 50
-        calibration = {"hbm_copy_GBps": 2 * xs[0].numel() * 4 / (copy_ms * 1e-3) / 1e9, "copy_ms": copy_ms,
-                       "note": "torch copy_ of one input batch (read + write), 50 launches, outside the timed region; "
-                               "5.3 TB/s on the boxes the profiles/ numbers come from"}
-        del dst
-        calibration.update(box_probe(dev))
+    calibration = None
+    if args.full:
+        # box calibration, outside the timed region: a plain device-to-device copy of one input batch (read + write).  Boxes of
+        # this pool differ (the same kernel ran 66 us on most and 94 us on one, profiles/r03_zz_lfilter_issue.txt); the copy rate
+        # measured in the same process says which kind this run was on
+        with torch.no_grad():
+            dst = torch.empty_like(xs[0])
+            for i in range(10):
+                dst.copy_(xs[i % ring])
+            torch.cuda.synchronize()
+            c0, c1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            c0.record()
+            for i in range(50):
+                dst.copy_(xs[i % ring])
+            c1.record()
+            torch.cuda.synchronize()
+            copy_ms = c0.elapsed_time(c1) / 50
+            calibration = {"hbm_copy_GBps": 2 * xs[0].numel() * 4 / (copy_ms * 1e-3) / 1e9, "copy_ms": copy_ms,
+                           "note": "torch copy_ of one input batch (read + write), 50 launches, outside the timed region; "
+                                   "5.3 TB/s on the boxes the profiles/ numbers come from"}
+            del dst
+            calibration.update(box_probe(dev))
 
     t = torch.tensor([wall], dtype=torch.float64, device=dev)
     per_rank = None
@@ -583,8 +633,6 @@ def main():
         dist.all_gather(gathered, mine)
         per_rank = [float(v.item()) / max(args.steps, 1) * 1e3 for v in gathered]
     wall = float(t.item())
-    n_frames = y.shape[-1]
-    assert tuple(y.shape) == (batch, n_out, n_frames) and n_frames == 1001
 
     sg = None
     if args.scatter_gather:
@@ -640,7 +688,7 @@ def main():
         traffic, tdetail = (None, {"traffic_source": "committed", "why": "--no-traffic, --op mfcc or N > 1"})
         pmc = {}
         mfcc_report = None
-        if args.op == "mfcc":
+        if args.full and args.op == "mfcc":
             # the label says what was measured -- the module reports which path its calls took
             mfcc_report = mod.fused_report()
             if mfcc_report["calls_two_kernel"] == 0:
@@ -649,7 +697,7 @@ def main():
         xs = ys = None
         torch.cuda.empty_cache()
         configs = None
-        if world == 1 and not args.no_configs:
+        if args.full and world == 1 and not args.no_configs:
             # the other BASELINE configs (per-GPU shards), after and outside the timed K steps of the headline metric
             sys.path.insert(0, os.path.join(ROOT, "tools"))
             try:
@@ -659,10 +707,10 @@ def main():
                 configs = bench_configs.measure_configs(dev, steps=200, warmup=100, which=which)
             except Exception as e:                            # never lose the headline line to a side measurement
                 configs = [{"error": f"{type(e).__name__}: {e}"[:400]}]
-        if world == 1 and not args.no_traffic and args.op == "mel":
+        if args.full and world == 1 and not args.no_traffic and args.op == "mel":
             traffic, tdetail = measure_traffic()
             pmc = measure_issue(priced_ms)
-        if traffic is None and args.op == "mel":
+        if args.full and traffic is None and args.op == "mel":
             traffic = committed_traffic()
         out = {
             "metric": metric,
@@ -688,18 +736,20 @@ def main():
                                    "top_db cut-off) between the two kernels",
                        "buffer_ring": f"{ring} input batches x {ring + 1} output buffers rotate "
                                       f"({ring * algo_bytes / 1e6:.0f} MB per cycle > 256 MiB Infinity Cache)"},
-            "roofline": dict({"bound": "hbm", "kernel": " + ".join(kernels), "achieved": achieved, "peak": HBM_PEAK_GBS,
-                              "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
-                              "priced_on": priced_on, "priced_ms": priced_ms,
-                              "achieved_timed_region": achieved_timed, "frac_timed_region": achieved_timed / HBM_PEAK_GBS,
-                              "frac_on_wall_clock": algo_bytes / (wall / args.steps) / 1e9 / HBM_PEAK_GBS,
-                              "timing": "`achieved` / `frac`: see `priced_on`; `*_timed_region` from HIP events around the K "
-                                        "steps on the launch stream (`kernel_ms`); `frac_on_wall_clock` from `ms_per_step` "
-                                        "(host clock, barrier to barrier)",
-                              "algorithmic_bytes_per_launch": algo_bytes, "kernel_ms": kernel_ms,
-                              "read_only_frac": (batch * L * 4) / (priced_ms * 1e-3) / 1e9 / HBM_PEAK_GBS}, **tdetail, **pmc),
         }
-        out["box_calibration"] = calibration
+        if args.full:
+            out["roofline"] = dict({"bound": "hbm", "kernel": " + ".join(kernels), "achieved": achieved, "peak": HBM_PEAK_GBS,
+                                    "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
+                                    "priced_on": priced_on, "priced_ms": priced_ms,
+                                    "achieved_timed_region": achieved_timed, "frac_timed_region": achieved_timed / HBM_PEAK_GBS,
+                                    "frac_on_wall_clock": algo_bytes / (wall / args.steps) / 1e9 / HBM_PEAK_GBS,
+                                    "timing": "`achieved` / `frac`: see `priced_on`; `*_timed_region` from HIP events around the K "
+                                              "steps on the launch stream (`kernel_ms`); `frac_on_wall_clock` from `ms_per_step` "
+                                              "(host clock, barrier to barrier)",
+                                    "algorithmic_bytes_per_launch": algo_bytes, "kernel_ms": kernel_ms,
+                                    "read_only_frac": (batch * L * 4) / (priced_ms * 1e-3) / 1e9 / HBM_PEAK_GBS},
+                                   **tdetail, **pmc)
+            out["box_calibration"] = calibration
         if mfcc_report is not None:
             out["mfcc_path"] = mfcc_report
         if configs is not None:
@@ -712,7 +762,7 @@ def main():
         if steady is not None:
             steady["frac_of_hbm_peak"] = algo_bytes / (steady["ms_per_step"] * 1e-3) / 1e9 / HBM_PEAK_GBS
             out["steady_state_1000_steps"] = steady
-        if world == 1 and not args.no_cpu_baseline and args.op == "mel":
+        if args.full and world == 1 and not args.no_cpu_baseline and args.op == "mel":
             from oracle import torch_cpu_ref
             sweep = torch_cpu_ref.sweep_mel_baseline(batch, SECONDS, SR, N_FFT, HOP, N_MELS)
             best = max(sweep, key=lambda r: r["audio_sec_per_sec"])

@@ -5,6 +5,8 @@ import os
 import subprocess
 import sys
 
+import pytest
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -95,3 +97,67 @@ def test_curve_with_three_ranks_adds_the_odd_endpoint_and_refuses_a_torchrun_lau
     assert [p["n"] for p in _json_lines(r.stdout)[0]["curve"]] == [1, 2, 3]
     r = _run(["--gpus", "2", "--selftest-cpu", "--curve"], env={"WORLD_SIZE": "2", "RANK": "0"})
     assert r.returncode != 0 and "--curve" in (r.stderr + r.stdout)
+
+
+def test_dump_outputs_writes_the_last_step_the_same_on_every_run(tmp_path):
+    """`--dump-outputs DIR`: the last timed step's result as DIR/<name>.npy in float32, written after the timed steps; the inputs
+    are seeded, so two runs with the same arguments write the same array, and `--steps` is the number of timed steps."""
+    import numpy as np
+    got = []
+    for run in ("a", "b"):
+        r = _run(["--steps", "3", "--warmup", "1", "--selftest-cpu", "--dump-outputs", str(tmp_path / run)])
+        assert r.returncode == 0, r.stderr[-2000:]
+        line = _json_lines(r.stdout)[0]
+        assert line["steps"] == 3 and line["ms_per_step"] > 0
+        got.append(np.load(tmp_path / run / "selftest.npy"))
+    assert got[0].dtype == np.float32 and got[0].shape == (4, 201, 101)
+    assert np.array_equal(got[0], got[1])
+
+
+def test_dump_sample_is_fixed_and_within_the_budget():
+    """A batch over the budget is written as the same seeded sample of whole clips on every call; at most 64 MB in all."""
+    sys.path.insert(0, ROOT)
+    import bench
+    row_bytes = bench.N_MELS * 1001 * 4                      # one clip of the headline output
+    rows = bench.dump_rows(256, row_bytes)
+    assert 0 < len(rows) < 256 and len(rows) * row_bytes <= 64_000_000
+    assert list(rows) == sorted(set(rows.tolist())) and list(rows) == list(bench.dump_rows(256, row_bytes))
+    assert list(bench.dump_rows(4, 1000)) == [0, 1, 2, 3]
+
+
+def test_steps_below_one_is_an_error():
+    r = _run(["--steps", "0", "--selftest-cpu"])
+    assert r.returncode != 0 and "--steps" in r.stderr
+
+
+@pytest.mark.gpu
+def test_plain_run_reports_the_headline_alone_and_dumps_its_last_step(tmp_path):
+    """A plain run is set-up, warm-up, the K timed steps and the line, none of the --full measurements; its dump is what the
+    module returns for the batch of the last timed step (step K - 1 reads slot (K - 1) % RING of the seeded ring)."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    import audio_amd.transforms as T
+    steps = 3
+    r = _run(["--gpus", "1", "--steps", str(steps), "--warmup", "1", "--clock-ramp", "0", "--dump-outputs", str(tmp_path)],
+             timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = _json_lines(r.stdout)
+    assert len(lines) == 1, r.stdout
+    line = lines[0]
+    assert line["steps"] == steps and line["ms_per_step"] > 0 and line["value"] > 0
+    assert line["unit"] == "audio-sec/sec" and line["higher_is_better"] is True and line["dtype"] == "f32"
+    assert not {"roofline", "box_calibration", "configs", "cpu_baseline", "steady_state_1000_steps"} & set(line)
+    got = np.load(tmp_path / "melspectrogram.npy")
+    dev = torch.device("cuda", 0)
+    g = torch.Generator(device=dev).manual_seed(1234)
+    for _ in range((steps - 1) % bench.RING + 1):
+        x = (0.5 * torch.randn(bench.BATCH, int(bench.SECONDS * bench.SR), device=dev, generator=g)).clamp_(-1, 1)
+    mel = T.MelSpectrogram(sample_rate=bench.SR, n_fft=bench.N_FFT, hop_length=bench.HOP, n_mels=bench.N_MELS).to(dev)
+    with torch.no_grad():
+        y = mel(x)
+    rows = bench.dump_rows(bench.BATCH, y[0].numel() * 4)
+    exp = y[torch.as_tensor(rows, device=dev)].cpu().numpy()
+    assert got.dtype == np.float32 and got.shape == exp.shape
+    assert np.abs(got - exp).max() <= 1e-6 * np.abs(exp).max()

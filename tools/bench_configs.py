@@ -58,7 +58,7 @@ def measure_configs(dev, steps=200, warmup=100, which=None, gen_seed=1234):
     """Every BASELINE.json config besides the headline one, per-GPU shard, as a list of records:
       {id, workload, ms, clip_seconds_per_launch, value (audio-s/s per GPU), algorithmic_bytes,
        roofline {bound, achieved, peak, unit, frac} [, roofline_matrix_f16, fp32_equivalent, note, ...]}
-    bench.py calls this on rank 0 at N = 1, OUTSIDE its timed K steps, and puts the list into the driver-run JSON line under
+    bench.py --full calls this on rank 0 at N = 1, OUTSIDE its timed K steps, and puts the list into the driver-run JSON line under
     "configs" (VERDICT r3 next 2); `python tools/bench_configs.py` prints the same records one per line."""
     g = torch.Generator(device=dev).manual_seed(gen_seed)
     recs = []

@@ -6,9 +6,9 @@
 #   tests_reverse / tests_serialize   the suite in reverse order / under AMD_SERIALIZE_KERNEL=3 -> pytest_reverse.log / pytest_serialize.log
 #   tests:<expr>     `pytest -m gpu -k <expr>`                            -> pytest_k.log
 #   smoke            __graft_entry__.smoke()                              -> smoke.log
-#   bench            bench.py with its defaults (all configs, PMC passes, CPU baseline)   -> bench.json
+#   bench            bench.py --full (all configs, PMC passes, CPU baseline)              -> bench.json
 #   bench_driver     bench.py --gpus 1 --steps 20 --warmup 5 (the driver's flags)        -> bench_driver_flags.json
-#   bench_mfcc       bench.py --op mfcc --no-configs                      -> bench_mfcc.json
+#   bench_mfcc       bench.py --full --op mfcc --no-configs               -> bench_mfcc.json
 #   prof             rocprofv3 --kernel-trace --stats of a headline run   -> prof_summary.txt
 #   prof_configs     rocprofv3 --kernel-trace --stats of tools/bench_configs.py (every BASELINE config) -> prof_configs_summary.txt
 #   configs          tools/bench_configs.py                               -> configs.jsonl
@@ -28,9 +28,9 @@ for step in "$@"; do
     tests_serialize) AMD_SERIALIZE_KERNEL=3 timeout 1800 python -m pytest tests -m gpu -x -q > $O/pytest_serialize.log 2>&1; echo "pytest rc=$?" >> $O/pytest_serialize.log; tail -3 $O/pytest_serialize.log ;;
     tests:*) timeout 900 python -m pytest tests -m gpu -x -q -k "${step#tests:}" > $O/pytest_k.log 2>&1; echo "pytest rc=$?" >> $O/pytest_k.log; tail -15 $O/pytest_k.log ;;
     smoke) timeout 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1; echo "smoke rc=$?" >> $O/smoke.log; tail -2 $O/smoke.log ;;
-    bench) timeout 900 python bench.py > $O/bench.json 2> $O/bench.err; echo "rc=$?" >> $O/bench.err; cat $O/bench.json; tail -3 $O/bench.err ;;
+    bench) timeout 900 python bench.py --full > $O/bench.json 2> $O/bench.err; echo "rc=$?" >> $O/bench.err; cat $O/bench.json; tail -3 $O/bench.err ;;
     bench_driver) timeout 600 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_driver_flags.json 2> $O/bench_driver_flags.err; cat $O/bench_driver_flags.json | cut -c1-1500 ;;
-    bench_mfcc) timeout 400 python bench.py --op mfcc --no-configs > $O/bench_mfcc.json 2> $O/bench_mfcc.err; cat $O/bench_mfcc.json ;;
+    bench_mfcc) timeout 400 python bench.py --full --op mfcc --no-configs > $O/bench_mfcc.json 2> $O/bench_mfcc.err; cat $O/bench_mfcc.json ;;
     prof)
       (cd /tmp && timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $R/$O/prof -o mel -- python $R/bench.py --steps 1000 --warmup 500 --no-cpu-baseline --no-traffic --no-configs > $R/$O/prof.log 2>&1)
       python tools/prof_summary.py $O/prof > $O/prof_summary.txt; head -8 $O/prof_summary.txt
