@@ -271,3 +271,44 @@ def phase_vocoder(spec: Tensor, rate: float, phase_advance: Tensor) -> Tensor:
     phase = torch.cumsum(torch.cat([z[..., :1].angle(), step[..., :-1]], dim=-1), -1)
     out = torch.polar(frac * z1.abs() + (1 - frac) * z0.abs(), phase)
     return out.reshape(tuple(shape[:-2]) + out.shape[1:])
+
+
+def cmn_window_bounds(n_frames: int, cmn_window: int, min_cmn_window: int, center: bool, device) -> Tuple[Tensor, Tensor]:
+    """The windows [s(t), e(t)) of F.sliding_window_cmn for every frame, vectorised (the reference's per-frame loop;
+    csrc/feat_post.h cmn_window() is the same map)."""
+    t = torch.arange(n_frames, device=device)
+    if center:
+        s = t - cmn_window // 2
+        e = s + cmn_window
+    else:
+        s = t - cmn_window
+        e = t + 1
+    neg = s < 0
+    e = torch.where(neg, e - s, e)
+    s = torch.where(neg, torch.zeros_like(s), s)
+    if not center:
+        e = torch.where(e > t, torch.clamp(t + 1, min=min_cmn_window), e)
+    over = e > n_frames
+    s = torch.where(over, torch.clamp(s - (e - n_frames), min=0), s)
+    e = torch.where(over, torch.full_like(e, n_frames), e)
+    return s, e
+
+
+def sliding_window_cmvn(x3: Tensor, cmn_window: int, min_cmn_window: int, center: bool) -> Tensor:
+    """F.sliding_window_cmn(norm_vars=True) as a differentiable torch composition (the training path: an input that asks
+    for a gradient).  Window sums are differences of float64 prefix sums gathered at s(t) and e(t) -- no per-frame loop;
+    x3 is (channels, time, freq)."""
+    T = x3.shape[1]
+    s, e = cmn_window_bounds(T, cmn_window, min_cmn_window, center, x3.device)
+    xd = x3.to(torch.float64)
+    zero = xd.new_zeros((xd.shape[0], 1, xd.shape[2]))
+    p1 = torch.cat([zero, torch.cumsum(xd, 1)], 1)
+    p2 = torch.cat([zero, torch.cumsum(xd * xd, 1)], 1)
+    n = (e - s).to(torch.float64).view(1, T, 1)
+    s1 = p1.index_select(1, e) - p1.index_select(1, s)
+    s2 = p2.index_select(1, e) - p2.index_select(1, s)
+    centred = xd - s1 / n
+    single = n == 1
+    var = torch.where(single, torch.ones_like(s2), s2 / n - (s1 * s1) / (n * n))
+    out = torch.where(single, torch.zeros_like(centred), centred * torch.pow(var, -0.5))
+    return out.to(x3.dtype)

@@ -135,6 +135,12 @@ _SIGS = {
                                        C.c_int64, C.c_int64, _P, _P]),
     "aamd_fftconvolve_staged_f32": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _P, _P,
                                               C.c_int64, C.c_int64, _P, C.c_int32, _P]),
+    # feature post-processing (additions to ABI 7)
+    "aamd_compute_deltas_f32": (C.c_int, [_P, _P] + [C.c_int64] * 6 + [C.c_int32] * 3 + [_P]),
+    "aamd_compute_deltas_f64": (C.c_int, [_P, _P] + [C.c_int64] * 6 + [C.c_int32] * 3 + [_P]),
+    "aamd_sliding_window_cmn_workspace": (C.c_int64, [C.c_int64] * 3 + [C.c_int32]),
+    "aamd_sliding_window_cmn_f32": (C.c_int, [_P, _P, _P] + [C.c_int64] * 8 + [C.c_int32] * 3 + [_P]),
+    "aamd_sliding_window_cmn_f64": (C.c_int, [_P, _P, _P] + [C.c_int64] * 8 + [C.c_int32] * 3 + [_P]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS)

@@ -52,6 +52,8 @@ _DEF.define("designed_biquad(Tensor waveform, str kind, int sample_rate, float[]
 _DEF.define("mfcc_module(Tensor waveform, Tensor window, Tensor fb, Tensor dct_mat, int pad, int n_fft, int hop_length, "
             "int win_length, float power, int norm_mode, bool center, str pad_mode, bool log_mels, float top_db, "
             "float multiplier, float amin, float db_multiplier, int fused, int state) -> Tensor")
+_DEF.define("compute_deltas(Tensor specgram, int win_length, str mode) -> Tensor")
+_DEF.define("sliding_window_cmn(Tensor specgram, int cmn_window, int min_cmn_window, bool center, bool norm_vars) -> Tensor")
 _DEF.define("rnnt_features(Tensor waveform, Tensor window, Tensor fb, int n_fft, int hop_length, float gain, Tensor mean, "
             "Tensor invstddev, int right_padding) -> Tensor")
 
@@ -153,6 +155,8 @@ def _rnnt_features(waveform, window, fb, n_fft, hop_length, gain, mean, invstdde
 
 
 _register("rnnt_features", _rnnt_features)
+_register("compute_deltas", F.compute_deltas)
+_register("sliding_window_cmn", F.sliding_window_cmn)
 
 
 # ---- Meta implementations: shapes / strides only ---------------------------------------------
@@ -268,3 +272,16 @@ _META.impl("inverse_spectrogram", _inverse_spectrogram_meta)
 _META.impl("phase_vocoder", _phase_vocoder_meta)
 _META.impl("griffinlim", _griffinlim_meta)
 _META.impl("rnnt_features", _rnnt_features_meta)
+
+
+def _compute_deltas_meta(specgram, win_length, mode):
+    return torch.empty_like(specgram, memory_format=torch.contiguous_format)
+
+
+def _sliding_window_cmn_meta(specgram, cmn_window, min_cmn_window, center, norm_vars):
+    out = torch.empty_like(specgram, memory_format=torch.contiguous_format)
+    return out.squeeze(0) if specgram.dim() == 2 else out
+
+
+_META.impl("compute_deltas", _compute_deltas_meta)
+_META.impl("sliding_window_cmn", _sliding_window_cmn_meta)

@@ -28,7 +28,9 @@ OPS = ("spectrogram", "mel_spectrogram", "mel_spectrogram_db", "mfcc_dct", "resa
        "mel_spectrogram_grad", "resample_sparse", "kaldi_features", "lfilter_f64", "resample_f64", "fftconvolve_f64",
        # round 5: the staged form of fftconvolve (prepared tap spectra for a repeated impulse response), the prepared tap
        # fragments of the matrix-core resampler
-       "fftconvolve_staged", "resample_frag_build")
+       "fftconvolve_staged", "resample_frag_build",
+       # the feature post-processing entries (F.compute_deltas, F.sliding_window_cmn; additions to ABI 7)
+       "compute_deltas", "sliding_window_cmn")
 
 _lock = threading.Lock()
 _handle = None
@@ -183,6 +185,14 @@ def _register_fakes() -> None:
     @reg("aamd::fftconvolve_f64")
     def _(x, y, x_row_of, y_row_of, rows, start, out_len):
         return x.new_empty((rows, out_len))
+
+    @reg("aamd::compute_deltas")
+    def _(x, win_length, pad_mode, adjoint):
+        return x.new_empty(x.shape)
+
+    @reg("aamd::sliding_window_cmn")
+    def _(x, cmn_window, min_cmn_window, center, norm_vars, adjoint):
+        return x.new_empty(x.shape)
 
 
 def available() -> bool:

@@ -16,6 +16,7 @@
 #include "../../include/audio_amd.h"
 #include "db_mfcc.h"
 #include "f64_paths.h"
+#include "feat_post.h"
 #include "fftconv.h"
 #include "fftconv_os.h"
 #include "fftconv_fdr.h"
@@ -1747,6 +1748,89 @@ int aamd_fftconvolve_staged_f32(const float* x, const float* y, float* out, int6
   hipLaunchKernelGGL(fftconv_direct_kernel, dim3((unsigned)blocks), dim3(kFcThreads), 0, s,
                      g, xa, ya, xmap, ymap, out);
   return launch_check();
+}
+
+// ---- feature post-processing: deltas and sliding-window CMN (csrc/feat_post.h) -----------------------------------------
+extern "C++" template <typename T>
+static int compute_deltas(const T* x, T* out, int64_t channels, int64_t n_feat, int64_t n_frames, int64_t sc, int64_t sf,
+                          int64_t st, int32_t win_length, int32_t pad_mode, int32_t adjoint, void* stream) {
+  DeviceScope dev_scope_(x);
+  AAMD_CHECK_ARG(channels >= 0 && n_feat >= 0 && n_frames >= 0, "bad sizes");
+  AAMD_CHECK_ARG(win_length >= 3, "win_length must be >= 3");
+  AAMD_CHECK_ARG(pad_mode >= AAMD_PAD_REFLECT && pad_mode <= AAMD_PAD_CIRCULAR, "unknown pad mode");
+  const int n = (win_length - 1) / 2;
+  AAMD_CHECK_ARG(pad_mode != AAMD_PAD_REFLECT || n < n_frames, "reflect padding needs (win_length - 1) / 2 < frames");
+  AAMD_CHECK_ARG(pad_mode != AAMD_PAD_CIRCULAR || n <= n_frames, "circular padding needs (win_length - 1) / 2 <= frames");
+  if (channels * n_feat * n_frames == 0) return AAMD_OK;
+  AAMD_CHECK_ARG(x && out, "null buffer");
+  fp::DeltaGeom g;
+  if (!fp::delta_plan(g, channels, n_feat, n_frames, sc, sf, st, n, pad_mode, adjoint, (int64_t)sizeof(T)))
+    return fail(AAMD_EUNSUPPORTED, "audio_amd: compute_deltas: win_length too large for one LDS tile");
+  const int64_t blocks = channels * g.n_ftiles * g.n_ttiles;
+  AAMD_CHECK_ARG(blocks < (1ll << 31), "too many tiles for one launch");
+  const size_t lds = (size_t)g.tf * g.w * sizeof(T);
+  hipLaunchKernelGGL(fp::deltas_kernel<T>, dim3((unsigned)blocks), dim3(fp::kDtThreads), lds, (hipStream_t)stream, x, out, g);
+  return launch_check();
+}
+
+int aamd_compute_deltas_f32(const float* x, float* out, int64_t channels, int64_t n_feat, int64_t n_frames,
+                            int64_t stride_channel, int64_t stride_feat, int64_t stride_frame, int32_t win_length,
+                            int32_t pad_mode, int32_t adjoint, void* stream) {
+  return compute_deltas<float>(x, out, channels, n_feat, n_frames, stride_channel, stride_feat, stride_frame, win_length,
+                               pad_mode, adjoint, stream);
+}
+
+int aamd_compute_deltas_f64(const double* x, double* out, int64_t channels, int64_t n_feat, int64_t n_frames,
+                            int64_t stride_channel, int64_t stride_feat, int64_t stride_frame, int32_t win_length,
+                            int32_t pad_mode, int32_t adjoint, void* stream) {
+  return compute_deltas<double>(x, out, channels, n_feat, n_frames, stride_channel, stride_feat, stride_frame, win_length,
+                                pad_mode, adjoint, stream);
+}
+
+int64_t aamd_sliding_window_cmn_workspace(int64_t channels, int64_t n_frames, int64_t n_feat, int32_t norm_vars) {
+  if (channels < 0 || n_frames < 0 || n_feat < 0) return 0;
+  const int64_t n_chunks = (n_frames + fp::kCmnL - 1) / fp::kCmnL;
+  return channels * n_chunks * n_feat * (norm_vars ? 2 : 1) * (int64_t)sizeof(double);
+}
+
+extern "C++" template <typename T>
+static int sliding_window_cmn(const T* x, T* out, void* workspace, int64_t channels, int64_t n_frames, int64_t n_feat,
+                              int64_t sc, int64_t sf, int64_t st, int64_t cmn_window, int64_t min_cmn_window,
+                              int32_t center, int32_t norm_vars, int32_t adjoint, void* stream) {
+  DeviceScope dev_scope_(x);
+  AAMD_CHECK_ARG(channels >= 0 && n_frames >= 0 && n_feat >= 0, "bad sizes");
+  AAMD_CHECK_ARG(cmn_window >= 0, "cmn_window must be >= 0");
+  AAMD_CHECK_ARG(!(adjoint && norm_vars), "the adjoint is served for norm_vars = false only");
+  if (channels * n_frames * n_feat == 0) return AAMD_OK;
+  AAMD_CHECK_ARG(x && out && workspace, "null buffer");
+  AAMD_CHECK_ARG(((uintptr_t)workspace & 7) == 0, "workspace must be 8-byte aligned");
+  fp::CmnGeom g;
+  fp::cmn_plan(g, channels, n_frames, n_feat, sc, st, sf, cmn_window, min_cmn_window, center, norm_vars, adjoint);
+  const int64_t blocks = channels * g.n_chunks * g.n_ftiles;
+  AAMD_CHECK_ARG(blocks < (1ll << 31), "too many chunks for one launch");
+  hipStream_t s = (hipStream_t)stream;
+  double* ws = static_cast<double*>(workspace);
+  hipLaunchKernelGGL(fp::cmn_chunk_kernel<T>, dim3((unsigned)blocks), dim3(g.threads), 0, s, x, ws, g);
+  int rc = launch_check();
+  if (rc != AAMD_OK) return rc;
+  hipLaunchKernelGGL(fp::cmn_walk_kernel<T>, dim3((unsigned)blocks), dim3(g.threads), 0, s, x, ws, out, g);
+  return launch_check();
+}
+
+int aamd_sliding_window_cmn_f32(const float* x, float* out, void* workspace, int64_t channels, int64_t n_frames,
+                                int64_t n_feat, int64_t stride_channel, int64_t stride_feat, int64_t stride_frame,
+                                int64_t cmn_window, int64_t min_cmn_window, int32_t center, int32_t norm_vars,
+                                int32_t adjoint, void* stream) {
+  return sliding_window_cmn<float>(x, out, workspace, channels, n_frames, n_feat, stride_channel, stride_feat, stride_frame,
+                                   cmn_window, min_cmn_window, center, norm_vars, adjoint, stream);
+}
+
+int aamd_sliding_window_cmn_f64(const double* x, double* out, void* workspace, int64_t channels, int64_t n_frames,
+                                int64_t n_feat, int64_t stride_channel, int64_t stride_feat, int64_t stride_frame,
+                                int64_t cmn_window, int64_t min_cmn_window, int32_t center, int32_t norm_vars,
+                                int32_t adjoint, void* stream) {
+  return sliding_window_cmn<double>(x, out, workspace, channels, n_frames, n_feat, stride_channel, stride_feat, stride_frame,
+                                    cmn_window, min_cmn_window, center, norm_vars, adjoint, stream);
 }
 
 }  // extern "C"

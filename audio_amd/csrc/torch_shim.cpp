@@ -724,6 +724,44 @@ Tensor fftconvolve_f64(Tensor x, Tensor y, std::optional<Tensor> x_row_of, std::
   return out;
 }
 
+// ---- aamd::compute_deltas / sliding_window_cmn (F.compute_deltas, F.sliding_window_cmn; csrc/feat_post.h) -----------------
+// The input is read in place through its strides (no contiguity requirement); the result is allocated dense.
+void want_feat(const Tensor& x, const char* what) {
+  STD_TORCH_CHECK(x.is_cuda(), "audio_amd: ", what, " must be on an MI355X (ROCm) device; there is no CPU kernel");
+  STD_TORCH_CHECK(x.scalar_type() == ScalarType::Float || x.scalar_type() == ScalarType::Double,
+                  "audio_amd: ", what, " must be float32 or float64");
+  STD_TORCH_CHECK(x.dim() == 3, "audio_amd: ", what, " must have 3 dimensions");
+}
+Tensor compute_deltas(Tensor x, int64_t win_length, int64_t pad_mode, bool adjoint) {
+  want_feat(x, "specgram");                                       // (channels, freq, time)
+  const torch::stable::accelerator::DeviceGuard guard(x.get_device_index());
+  Tensor out = torch::stable::new_empty(x, {x.size(0), x.size(1), x.size(2)});
+  if (x.scalar_type() == ScalarType::Double)
+    check(aamd_compute_deltas_f64(x.numel() ? static_cast<const double*>(x.data_ptr()) : nullptr, dpm(out), x.size(0), x.size(1),
+                                  x.size(2), x.stride(0), x.stride(1), x.stride(2), (int32_t)win_length, (int32_t)pad_mode,
+                                  adjoint ? 1 : 0, current_stream(x)));
+  else
+    check(aamd_compute_deltas_f32(fp(x), fpm(out), x.size(0), x.size(1), x.size(2), x.stride(0), x.stride(1), x.stride(2),
+                                  (int32_t)win_length, (int32_t)pad_mode, adjoint ? 1 : 0, current_stream(x)));
+  return out;
+}
+Tensor sliding_window_cmn(Tensor x, int64_t cmn_window, int64_t min_cmn_window, bool center, bool norm_vars, bool adjoint) {
+  want_feat(x, "specgram");                                       // (channels, time, freq)
+  const torch::stable::accelerator::DeviceGuard guard(x.get_device_index());
+  Tensor out = torch::stable::new_empty(x, {x.size(0), x.size(1), x.size(2)});
+  const int64_t ws_bytes = aamd_sliding_window_cmn_workspace(x.size(0), x.size(1), x.size(2), norm_vars ? 1 : 0);
+  Tensor ws = torch::stable::new_empty(x, {ws_bytes / 8 > 0 ? ws_bytes / 8 : 1}, ScalarType::Double);
+  if (x.scalar_type() == ScalarType::Double)
+    check(aamd_sliding_window_cmn_f64(x.numel() ? static_cast<const double*>(x.data_ptr()) : nullptr, dpm(out), ws.data_ptr(),
+                                      x.size(0), x.size(1), x.size(2), x.stride(0), x.stride(2), x.stride(1), cmn_window,
+                                      min_cmn_window, center ? 1 : 0, norm_vars ? 1 : 0, adjoint ? 1 : 0, current_stream(x)));
+  else
+    check(aamd_sliding_window_cmn_f32(fp(x), fpm(out), ws.data_ptr(), x.size(0), x.size(1), x.size(2), x.stride(0), x.stride(2),
+                                      x.stride(1), cmn_window, min_cmn_window, center ? 1 : 0, norm_vars ? 1 : 0,
+                                      adjoint ? 1 : 0, current_stream(x)));
+  return out;
+}
+
 // ---- torchaudio::_lfilter_core_loop on the CUDA key (lfilter.cpp:118-134, iir_cuda.cu:37-79) ------------------------
 //   padded_out[n][c][i + n_order - 1] = in[n][c][i] - sum_{j < n_order-1} a_flipped[c][j] * padded_out[n][c][i + j]
 // = the pure recursion y = IIR(in; a) with a = flip(a_flipped), b = (1, 0, ...), no clamp: aamd_lfilter_f32 runs it as a
@@ -820,6 +858,8 @@ STABLE_TORCH_LIBRARY(aamd, m) {
   m.def("lfilter_f64(Tensor waveform, Tensor a_coeffs, Tensor b_coeffs, int n_stages, int clamp) -> Tensor");
   m.def("resample_f64(Tensor wav, Tensor kernel, int orig, int new, int width, int out_len) -> Tensor");
   m.def("fftconvolve_f64(Tensor x, Tensor y, Tensor? x_row_of, Tensor? y_row_of, int rows, int start, int out_len) -> Tensor");
+  m.def("compute_deltas(Tensor specgram, int win_length, int pad_mode, bool adjoint) -> Tensor");
+  m.def("sliding_window_cmn(Tensor specgram, int cmn_window, int min_cmn_window, bool center, bool norm_vars, bool adjoint) -> Tensor");
 }
 
 STABLE_TORCH_LIBRARY_IMPL(aamd, CUDA, m) {
@@ -851,6 +891,8 @@ STABLE_TORCH_LIBRARY_IMPL(aamd, CUDA, m) {
   m.impl("lfilter_f64", TORCH_BOX(&lfilter_f64));
   m.impl("resample_f64", TORCH_BOX(&resample_f64));
   m.impl("fftconvolve_f64", TORCH_BOX(&fftconvolve_f64));
+  m.impl("compute_deltas", TORCH_BOX(&compute_deltas));
+  m.impl("sliding_window_cmn", TORCH_BOX(&sliding_window_cmn));
 }
 
 // The reference's op.  libtorchaudio (when present) has already run

@@ -31,6 +31,7 @@ __all__ = [
     "lfilter", "biquad", "fftconvolve", "mel_scale", "filtfilt",
     "lowpass_biquad", "highpass_biquad", "allpass_biquad", "bandpass_biquad",
     "bandreject_biquad", "equalizer_biquad", "band_biquad", "treble_biquad", "bass_biquad", "deemph_biquad", "riaa_biquad",
+    "compute_deltas", "sliding_window_cmn",
 ]
 
 # --------------------------------------------------------------------------- #
@@ -2204,6 +2205,132 @@ def _fftconvolve_eager(x: Tensor, y: Tensor, mode: str = "full") -> Tensor:
 
 
 # --------------------------------------------------------------------------- #
+# deltas / sliding-window CMN (csrc/feat_post.h)                              #
+# --------------------------------------------------------------------------- #
+
+_DELTA_PAD = {"reflect": 0, "constant": 1, "replicate": 2, "circular": 3}
+
+
+def _deltas_launch(x3: Tensor, win_length: int, mode_id: int, adjoint: bool) -> Tensor:
+    """(C, F, T) of any strides -> dense (C, F, T): the delta stencil (adjoint: its transpose), one launch."""
+    ops = _ops()
+    if ops is not None:
+        return ops.compute_deltas(x3, win_length, mode_id, adjoint)
+    out = torch.empty(x3.shape, dtype=x3.dtype, device=x3.device)
+    fn = _lib.lib().aamd_compute_deltas_f64 if x3.dtype == torch.float64 else _lib.lib().aamd_compute_deltas_f32
+    with torch.cuda.device(x3.device):
+        _lib.check(fn(_lib.ptr(x3) or None, _lib.ptr(out) or None, x3.shape[0], x3.shape[1], x3.shape[2], x3.stride(0),
+                      x3.stride(1), x3.stride(2), win_length, mode_id, int(adjoint), _lib.current_stream(x3.device)))
+    return out
+
+
+class _DeltasFunction(torch.autograd.Function):
+    """The delta stencil D (adjoint=False) or its transpose D^T (adjoint=True).  Linear: the backward is the other one,
+    applied through this Function again, so gradients of every order run on the kernel."""
+
+    @staticmethod
+    def forward(ctx, x3, win_length, mode_id, adjoint):
+        ctx.args = (win_length, mode_id, adjoint)
+        return _deltas_launch(x3, win_length, mode_id, adjoint)
+
+    @staticmethod
+    def backward(ctx, g):
+        win_length, mode_id, adjoint = ctx.args
+        if torch.is_grad_enabled():
+            return _DeltasFunction.apply(g, win_length, mode_id, not adjoint), None, None, None
+        return _deltas_launch(g, win_length, mode_id, not adjoint), None, None, None
+
+
+@_reduced_precision_io
+def _compute_deltas_eager(specgram: Tensor, win_length: int = 5, mode: str = "replicate") -> Tensor:
+    r"""Delta coefficients along time of a ``(..., freq, time)`` tensor (reference: F.compute_deltas, pad + grouped conv1d).
+    The input is read in place through its strides -- time-contiguous rows and the frame-major storage of every
+    MelSpectrogram / Spectrogram output alike -- and the result is a new contiguous tensor of the input's shape."""
+    if win_length < 3:
+        raise ValueError(f"Window length should be greater than or equal to 3. Found win_length {win_length}")
+    if mode not in _DELTA_PAD:
+        raise ValueError(f"audio_amd: compute_deltas: unknown padding mode {mode!r} "
+                         "(reflect, constant, replicate, circular)")
+    _require_device(specgram, "specgram", allow_grad=True, allow_f64=True)
+    shape = specgram.shape
+    T = shape[-1] if specgram.dim() >= 1 else 1
+    n = (win_length - 1) // 2
+    if (mode == "reflect" and n >= T) or (mode == "circular" and n > T):
+        raise RuntimeError(f"audio_amd: compute_deltas: {mode} padding of {n} frames needs "
+                           f"{'more than' if mode == 'reflect' else 'at least'} {n} frames, got {T}")
+    x3 = specgram.reshape(-1, shape[-2] if specgram.dim() >= 2 else 1, T)       # a view wherever the strides allow
+    if torch.is_grad_enabled() and specgram.requires_grad:
+        out = _DeltasFunction.apply(x3, win_length, _DELTA_PAD[mode], False)
+    else:
+        out = _deltas_launch(x3, win_length, _DELTA_PAD[mode], False)
+    return out.view(shape)
+
+
+def _cmn_launch(x3: Tensor, cmn_window: int, min_cmn_window: int, center: bool, norm_vars: bool, adjoint: bool) -> Tensor:
+    """(C, T, F) of any strides -> dense (C, T, F): chunk sums, then the window walk (two launches)."""
+    ops = _ops()
+    if ops is not None:
+        return ops.sliding_window_cmn(x3, cmn_window, min_cmn_window, center, norm_vars, adjoint)
+    L = _lib.lib()
+    out = torch.empty(x3.shape, dtype=x3.dtype, device=x3.device)
+    ws = torch.empty((max(int(L.aamd_sliding_window_cmn_workspace(*x3.shape, int(norm_vars))) // 8, 1),),
+                     dtype=torch.float64, device=x3.device)
+    fn = L.aamd_sliding_window_cmn_f64 if x3.dtype == torch.float64 else L.aamd_sliding_window_cmn_f32
+    with torch.cuda.device(x3.device):
+        _lib.check(fn(_lib.ptr(x3) or None, _lib.ptr(out) or None, ws.data_ptr(), x3.shape[0], x3.shape[1], x3.shape[2],
+                      x3.stride(0), x3.stride(2), x3.stride(1), cmn_window, min_cmn_window, int(center), int(norm_vars),
+                      int(adjoint), _lib.current_stream(x3.device)))
+    return out
+
+
+class _CmnFunction(torch.autograd.Function):
+    """Sliding-window mean normalisation (norm_vars=False) is linear: x - W x.  The backward is its transpose
+    g - W^T (g), run by the same kernels (adjoint=1), and the transpose of that is the forward again."""
+
+    @staticmethod
+    def forward(ctx, x3, cmn_window, min_cmn_window, center, adjoint):
+        ctx.args = (cmn_window, min_cmn_window, center, adjoint)
+        return _cmn_launch(x3, cmn_window, min_cmn_window, center, False, adjoint)
+
+    @staticmethod
+    def backward(ctx, g):
+        cmn_window, min_cmn_window, center, adjoint = ctx.args
+        if torch.is_grad_enabled():
+            gx = _CmnFunction.apply(g, cmn_window, min_cmn_window, center, not adjoint)
+        else:
+            gx = _cmn_launch(g, cmn_window, min_cmn_window, center, False, not adjoint)
+        return gx, None, None, None, None
+
+
+@_reduced_precision_io
+def _sliding_window_cmn_eager(specgram: Tensor, cmn_window: int = 600, min_cmn_window: int = 100, center: bool = False,
+                              norm_vars: bool = False) -> Tensor:
+    r"""Kaldi's sliding-window cepstral mean (and variance) normalisation of a ``(..., time, freq)`` tensor (reference:
+    F.sliding_window_cmn, a per-frame loop with a float32 running sum).  Every window sum here is exact to float64
+    accumulation.  Any strides are accepted (the reference's ``view`` refuses some); the result is a new contiguous
+    tensor, squeezed like the reference's for a 2-D input of one frame.  With ``norm_vars`` and an input that requires
+    grad the call takes the differentiable composition ``_diff.sliding_window_cmvn``."""
+    if specgram.dim() < 2:
+        raise ValueError(f"audio_amd: sliding_window_cmn expects (..., time, freq), got shape {tuple(specgram.shape)}")
+    if cmn_window < 0:
+        raise ValueError(f"audio_amd: sliding_window_cmn: cmn_window must be >= 0, got {cmn_window}")
+    _require_device(specgram, "specgram", allow_grad=True, allow_f64=True)
+    shape = specgram.shape
+    x3 = specgram.reshape(-1, shape[-2], shape[-1])
+    grad = torch.is_grad_enabled() and specgram.requires_grad
+    if norm_vars and grad:
+        out = _diff.sliding_window_cmvn(x3, cmn_window, min_cmn_window, center)
+    elif grad:
+        out = _CmnFunction.apply(x3, cmn_window, min_cmn_window, center, False)
+    else:
+        out = _cmn_launch(x3, cmn_window, min_cmn_window, center, norm_vars, False)
+    out = out.view(shape)
+    if len(shape) == 2:
+        out = out.squeeze(0)
+    return out
+
+
+# --------------------------------------------------------------------------- #
 # the public entry points                                                     #
 # --------------------------------------------------------------------------- #
 # Every public function is a small TorchScript-able front (the reference guarantees `torch.jit.script` on this surface:
@@ -2493,3 +2620,19 @@ def fftconvolve(x: Tensor, y: Tensor, mode: str = "full") -> Tensor:
     if not torch.jit.is_scripting():
         return _fftconvolve_eager(x, y, mode)
     return torch.ops.audio_amd.fftconvolve(x, y, mode)
+
+
+def compute_deltas(specgram: Tensor, win_length: int = 5, mode: str = "replicate") -> Tensor:
+    r"""Delta coefficients of a ``(..., freq, time)`` tensor (reference: F.compute_deltas); see ``_compute_deltas_eager``."""
+    if not torch.jit.is_scripting():
+        return _compute_deltas_eager(specgram, win_length, mode)
+    return torch.ops.audio_amd.compute_deltas(specgram, win_length, mode)
+
+
+def sliding_window_cmn(specgram: Tensor, cmn_window: int = 600, min_cmn_window: int = 100, center: bool = False,
+                       norm_vars: bool = False) -> Tensor:
+    r"""Sliding-window CMN of a ``(..., time, freq)`` tensor (reference: F.sliding_window_cmn); see
+    ``_sliding_window_cmn_eager``."""
+    if not torch.jit.is_scripting():
+        return _sliding_window_cmn_eager(specgram, cmn_window, min_cmn_window, center, norm_vars)
+    return torch.ops.audio_amd.sliding_window_cmn(specgram, cmn_window, min_cmn_window, center, norm_vars)

@@ -1,5 +1,5 @@
 """Drop-in replacements for the hot-path modules of ``torchaudio.transforms``:
-Spectrogram, MelScale, MelSpectrogram, AmplitudeToDB, MFCC, Resample, FFTConvolve.
+Spectrogram, MelScale, MelSpectrogram, AmplitudeToDB, MFCC, Resample, FFTConvolve, ComputeDeltas, SlidingWindowCmn.
 
 Constructor / forward signatures, registered buffer names (``window``, ``fb``, ``dct_mat``,
 ``kernel``), shapes, strides, warnings and error messages follow
@@ -31,7 +31,8 @@ _norm_mode = F._norm_mode      # `normalized` as the op schemas' integer: 0 none
 # scripted module keeps ``state_dict`` keys, buffers and attributes.
 
 __all__ = ["Spectrogram", "InverseSpectrogram", "GriffinLim", "TimeStretch", "PitchShift", "Speed", "SpeedPerturbation",
-           "MelScale", "MelSpectrogram", "AmplitudeToDB", "MFCC", "Resample", "FFTConvolve"]
+           "MelScale", "MelSpectrogram", "AmplitudeToDB", "MFCC", "Resample", "FFTConvolve", "ComputeDeltas",
+           "SlidingWindowCmn"]
 
 
 class Spectrogram(torch.nn.Module):
@@ -295,6 +296,42 @@ class AmplitudeToDB(torch.nn.Module):
             if torch.compiler.is_compiling():
                 return torch.ops.audio_amd.amplitude_to_DB(x, self.multiplier, self.amin, self.db_multiplier, self.top_db)
         return F.amplitude_to_DB(x, self.multiplier, self.amin, self.db_multiplier, self.top_db)
+
+
+class ComputeDeltas(torch.nn.Module):
+    r"""Delta coefficients of a ``(..., freq, time)`` tensor (reference: T.ComputeDeltas); no buffers."""
+    __constants__ = ["win_length"]
+
+    def __init__(self, win_length: int = 5, mode: str = "replicate") -> None:
+        super().__init__()
+        self.win_length = win_length
+        self.mode = mode
+
+    def forward(self, specgram: Tensor) -> Tensor:
+        if not torch.jit.is_scripting():
+            if torch.compiler.is_compiling():
+                return torch.ops.audio_amd.compute_deltas(specgram, self.win_length, self.mode)
+        return F.compute_deltas(specgram, win_length=self.win_length, mode=self.mode)
+
+
+class SlidingWindowCmn(torch.nn.Module):
+    r"""Sliding-window cepstral mean (and variance) normalisation of a ``(..., time, freq)`` tensor (reference:
+    T.SlidingWindowCmn); no buffers."""
+
+    def __init__(self, cmn_window: int = 600, min_cmn_window: int = 100, center: bool = False,
+                 norm_vars: bool = False) -> None:
+        super().__init__()
+        self.cmn_window = cmn_window
+        self.min_cmn_window = min_cmn_window
+        self.center = center
+        self.norm_vars = norm_vars
+
+    def forward(self, specgram: Tensor) -> Tensor:
+        if not torch.jit.is_scripting():
+            if torch.compiler.is_compiling():
+                return torch.ops.audio_amd.sliding_window_cmn(specgram, self.cmn_window, self.min_cmn_window, self.center,
+                                                              self.norm_vars)
+        return F.sliding_window_cmn(specgram, self.cmn_window, self.min_cmn_window, self.center, self.norm_vars)
 
 
 class MelScale(torch.nn.Module):

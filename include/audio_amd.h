@@ -42,6 +42,9 @@
  *                             libtorchaudio/lfilter.cpp:17-48 / iir_cuda.cu:10-35
  *                             (op torchaudio::_lfilter_core_loop, lfilter.cpp:118-124)
  *   aamd_fftconvolve_f32      functional/functional.py:2222-2258 (F.fftconvolve)
+ *   aamd_compute_deltas_f32   F.compute_deltas / T.ComputeDeltas (pad + grouped conv1d in the reference)
+ *   aamd_sliding_window_cmn_f32  F.sliding_window_cmn / T.SlidingWindowCmn (a per-frame loop in the reference)
+ *                             -- these two (and their _f64 forms) are additions to ABI 7, which stays 7
  *
  * The reference-side binding a maintainer would add is shown in INTEGRATION.md.
  */
@@ -479,6 +482,37 @@ int aamd_resample_f64(const double* wav, const double* kernel, double* out, int6
 int aamd_fftconvolve_f64(const double* x, const double* y, double* out, int64_t rows, int64_t n_x_rows, int64_t n_y_rows,
                          int64_t nx, int64_t ny, const int64_t* x_row_of, const int64_t* y_row_of, int64_t start,
                          int64_t out_len, void* stream);
+
+/* ---- feature post-processing (additions to ABI 7; csrc/feat_post.h) --------------------------------------------- */
+
+/* Delta coefficients, F.compute_deltas (functional/functional.py, compute_deltas): every (channel, feature) row of
+ * n_frames frames is padded by n = (win_length - 1) / 2 frames with pad_mode (AAMD_PAD_*) and correlated with
+ * [-n .. n]; the result is divided by n (n + 1) (2n + 1) / 3.  x is read in place through its element strides
+ * (stride_channel, stride_feat, stride_frame): time-contiguous rows and frame-major storage (stride_feat == 1, what
+ * MelSpectrogram returns) are both read without a copy.  out is dense (channels, n_feat, n_frames).
+ * adjoint = 1 applies the transpose of the same linear map (its gradient; the adjoint of the adjoint is the forward).
+ * win_length >= 3; AAMD_PAD_REFLECT needs n < n_frames and AAMD_PAD_CIRCULAR n <= n_frames (AAMD_EINVAL otherwise);
+ * a window whose LDS tile does not fit (n in the thousands) is AAMD_EUNSUPPORTED. */
+int aamd_compute_deltas_f32(const float* x, float* out, int64_t channels, int64_t n_feat, int64_t n_frames,
+                            int64_t stride_channel, int64_t stride_feat, int64_t stride_frame, int32_t win_length,
+                            int32_t pad_mode, int32_t adjoint, void* stream);
+int aamd_compute_deltas_f64(const double* x, double* out, int64_t channels, int64_t n_feat, int64_t n_frames,
+                            int64_t stride_channel, int64_t stride_feat, int64_t stride_frame, int32_t win_length,
+                            int32_t pad_mode, int32_t adjoint, void* stream);
+/* Sliding-window cepstral mean (and variance) normalisation, F.sliding_window_cmn (functional/functional.py,
+ * sliding_window_cmn; Kaldi's apply-cmvn-sliding): x is (channels, n_frames, n_feat) through its element strides (given,
+ * like the deltas', in (channel, feature, frame) order); out is dense (channels, n_frames, n_feat).  Every window sum is
+ * accumulated in float64 (chunk sums in `workspace`, which must hold aamd_sliding_window_cmn_workspace() bytes, 8-byte
+ * aligned).  adjoint = 1 (norm_vars = 0 only) applies the transpose of the linear map x -> out.  cmn_window >= 0. */
+int64_t aamd_sliding_window_cmn_workspace(int64_t channels, int64_t n_frames, int64_t n_feat, int32_t norm_vars);
+int aamd_sliding_window_cmn_f32(const float* x, float* out, void* workspace, int64_t channels, int64_t n_frames,
+                                int64_t n_feat, int64_t stride_channel, int64_t stride_feat, int64_t stride_frame,
+                                int64_t cmn_window, int64_t min_cmn_window, int32_t center, int32_t norm_vars,
+                                int32_t adjoint, void* stream);
+int aamd_sliding_window_cmn_f64(const double* x, double* out, void* workspace, int64_t channels, int64_t n_frames,
+                                int64_t n_feat, int64_t stride_channel, int64_t stride_feat, int64_t stride_frame,
+                                int64_t cmn_window, int64_t min_cmn_window, int32_t center, int32_t norm_vars,
+                                int32_t adjoint, void* stream);
 
 #ifdef __cplusplus
 }
