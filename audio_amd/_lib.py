@@ -141,6 +141,9 @@ _SIGS = {
     "aamd_sliding_window_cmn_workspace": (C.c_int64, [C.c_int64] * 3 + [C.c_int32]),
     "aamd_sliding_window_cmn_f32": (C.c_int, [_P, _P, _P] + [C.c_int64] * 8 + [C.c_int32] * 3 + [_P]),
     "aamd_sliding_window_cmn_f64": (C.c_int, [_P, _P, _P] + [C.c_int64] * 8 + [C.c_int32] * 3 + [_P]),
+    "aamd_detect_pitch_workspace": (C.c_int64, [C.c_int64, C.c_int64, C.c_int32]),
+    "aamd_detect_pitch_f32": (C.c_int, [_P, _P, _P] + [C.c_int64] * 3 + [C.c_int32] * 6 + [_P]),
+    "aamd_detect_pitch_f64": (C.c_int, [_P, _P, _P] + [C.c_int64] * 3 + [C.c_int32] * 6 + [_P]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS)

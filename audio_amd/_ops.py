@@ -54,6 +54,8 @@ _DEF.define("mfcc_module(Tensor waveform, Tensor window, Tensor fb, Tensor dct_m
             "float multiplier, float amin, float db_multiplier, int fused, int state) -> Tensor")
 _DEF.define("compute_deltas(Tensor specgram, int win_length, str mode) -> Tensor")
 _DEF.define("sliding_window_cmn(Tensor specgram, int cmn_window, int min_cmn_window, bool center, bool norm_vars) -> Tensor")
+_DEF.define("detect_pitch_frequency(Tensor waveform, int sample_rate, float frame_time, int win_length, int freq_low, "
+            "int freq_high) -> Tensor")
 _DEF.define("rnnt_features(Tensor waveform, Tensor window, Tensor fb, int n_fft, int hop_length, float gain, Tensor mean, "
             "Tensor invstddev, int right_padding) -> Tensor")
 
@@ -157,6 +159,7 @@ def _rnnt_features(waveform, window, fb, n_fft, hop_length, gain, mean, invstdde
 _register("rnnt_features", _rnnt_features)
 _register("compute_deltas", F.compute_deltas)
 _register("sliding_window_cmn", F.sliding_window_cmn)
+_register("detect_pitch_frequency", F.detect_pitch_frequency)
 
 
 # ---- Meta implementations: shapes / strides only ---------------------------------------------
@@ -285,3 +288,13 @@ def _sliding_window_cmn_meta(specgram, cmn_window, min_cmn_window, center, norm_
 
 _META.impl("compute_deltas", _compute_deltas_meta)
 _META.impl("sliding_window_cmn", _sliding_window_cmn_meta)
+
+
+def _detect_pitch_frequency_meta(waveform, sample_rate, frame_time, win_length, freq_low, freq_high):
+    if waveform.dim() == 0:
+        raise ValueError("audio_amd: detect_pitch_frequency expects a (..., time) waveform, got a 0-d tensor")
+    n_out = F._pitch_plan(waveform.shape[-1], sample_rate, frame_time, win_length, freq_low, freq_high)[4]
+    return waveform.new_empty(tuple(waveform.shape[:-1]) + (n_out,), dtype=torch.float32)
+
+
+_META.impl("detect_pitch_frequency", _detect_pitch_frequency_meta)

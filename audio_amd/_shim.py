@@ -30,7 +30,9 @@ OPS = ("spectrogram", "mel_spectrogram", "mel_spectrogram_db", "mfcc_dct", "resa
        # fragments of the matrix-core resampler
        "fftconvolve_staged", "resample_frag_build",
        # the feature post-processing entries (F.compute_deltas, F.sliding_window_cmn; additions to ABI 7)
-       "compute_deltas", "sliding_window_cmn")
+       "compute_deltas", "sliding_window_cmn",
+       # the NCCF pitch tracker (F.detect_pitch_frequency, F._compute_nccf; an addition to ABI 7)
+       "detect_pitch")
 
 _lock = threading.Lock()
 _handle = None
@@ -193,6 +195,13 @@ def _register_fakes() -> None:
     @reg("aamd::sliding_window_cmn")
     def _(x, cmn_window, min_cmn_window, center, norm_vars, adjoint):
         return x.new_empty(x.shape)
+
+    @reg("aamd::detect_pitch")
+    def _(x, sample_rate, frame_size, lags, lag_min, win_length, mode):
+        frames = -(-x.shape[1] // frame_size)
+        if mode == 1:
+            return x.new_empty((x.shape[0], frames, lags))
+        return x.new_empty((x.shape[0], frames + (win_length - 1) // 2 - win_length + 1), dtype=torch.float32)
 
 
 def available() -> bool:

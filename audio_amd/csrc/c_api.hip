@@ -28,6 +28,7 @@
 #include "lfilter.h"
 #include "lfilter_wave.h"
 #include "melspec400.h"
+#include "pitch.h"
 #include "resample.h"
 #include "resample_mfma.h"
 #include "stft_generic.h"
@@ -1831,6 +1832,68 @@ int aamd_sliding_window_cmn_f64(const double* x, double* out, void* workspace, i
                                 int32_t adjoint, void* stream) {
   return sliding_window_cmn<double>(x, out, workspace, channels, n_frames, n_feat, stride_channel, stride_feat, stride_frame,
                                     cmn_window, min_cmn_window, center, norm_vars, adjoint, stream);
+}
+
+// ---- NCCF pitch tracker (csrc/pitch.h) ------------------------------------------------------------------------------------
+int64_t aamd_detect_pitch_workspace(int64_t rows, int64_t length, int32_t frame_size) {
+  if (rows < 0 || length < 0 || frame_size < 1) return 0;
+  return rows * ((length + frame_size - 1) / frame_size) * (int64_t)sizeof(int32_t);
+}
+
+extern "C++" template <typename T>
+static int detect_pitch(const T* x, void* out, void* workspace, int64_t rows, int64_t length, int64_t row_stride,
+                        int32_t sample_rate, int32_t frame_size, int32_t lags, int32_t lag_min, int32_t win_length,
+                        int32_t mode, void* stream) {
+  DeviceScope dev_scope_(x);
+  AAMD_CHECK_ARG(rows >= 0 && length >= 0, "bad sizes");
+  AAMD_CHECK_ARG(mode == 0 || mode == 1, "mode must be 0 (pitch) or 1 (nccf)");
+  AAMD_CHECK_ARG(frame_size >= 1 && lags >= 1, "frame_size and lags must be >= 1");
+  AAMD_CHECK_ARG(mode == 1 || (lag_min >= 0 && lag_min < lags / 2), "need 0 <= lag_min < lags / 2");
+  AAMD_CHECK_ARG(mode == 1 || win_length >= 3, "win_length must be >= 3");
+  if (frame_size > pt::kMaxFrameSize || lags > pt::kMaxLags)
+    return fail(AAMD_EUNSUPPORTED, "audio_amd: detect_pitch_frequency: frame size > 8192 or lags > 16384 is not supported");
+  pt::PitchGeom g;
+  if (!pt::pitch_plan(g, rows, length, row_stride, frame_size, lags, lag_min, mode == 1 ? 3 : win_length,
+                      (float)sample_rate, mode, (int64_t)sizeof(T)))
+    return fail(AAMD_EUNSUPPORTED, "audio_amd: detect_pitch_frequency: no LDS tile fits these sizes");
+  AAMD_CHECK_ARG(mode == 1 || g.n_out >= 1, "fewer than one output frame");
+  if (rows == 0 || g.F == 0) return AAMD_OK;
+  AAMD_CHECK_ARG(x && out && (mode == 1 || workspace), "null buffer");
+  AAMD_CHECK_ARG(rows == 1 || row_stride >= length, "rows must not overlap");
+  const int64_t blocks = rows * g.n_ftiles;
+  AAMD_CHECK_ARG(blocks < (1ll << 31), "too many frame tiles for one launch");
+  hipStream_t s = (hipStream_t)stream;
+  const size_t lds = (size_t)pt::pitch_lds_bytes(g, (int64_t)sizeof(T));
+  auto kern = pt::pitch_nccf_pick_kernel<T>;
+  if (lds > 48 * 1024) {
+    if (lds > dev_props().lds_per_block_optin)
+      return fail(AAMD_EUNSUPPORTED, "audio_amd: detect_pitch_frequency: the LDS tile exceeds this device's");
+    AAMD_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  }
+  int32_t* lag = static_cast<int32_t*>(workspace);
+  hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(pt::kThreads), lds, s, x, g, lag, static_cast<T*>(out));
+  int rc = launch_check();
+  if (rc != AAMD_OK || mode == 1) return rc;
+  const int64_t mblocks = rows * ((g.n_out + pt::kMedT - 1) / pt::kMedT);
+  AAMD_CHECK_ARG(mblocks < (1ll << 31), "too many output tiles for one launch");
+  const size_t mlds = pt::pitch_median_tiled(g) ? (size_t)(pt::kMedT + g.win - 1) * sizeof(int) : 0;
+  hipLaunchKernelGGL(pt::pitch_median_kernel, dim3((unsigned)mblocks), dim3(pt::kThreads), mlds, s, lag,
+                     static_cast<float*>(out), g);
+  return launch_check();
+}
+
+int aamd_detect_pitch_f32(const float* x, void* out, void* workspace, int64_t rows, int64_t length, int64_t row_stride,
+                          int32_t sample_rate, int32_t frame_size, int32_t lags, int32_t lag_min, int32_t win_length,
+                          int32_t mode, void* stream) {
+  return detect_pitch<float>(x, out, workspace, rows, length, row_stride, sample_rate, frame_size, lags, lag_min, win_length,
+                             mode, stream);
+}
+
+int aamd_detect_pitch_f64(const double* x, void* out, void* workspace, int64_t rows, int64_t length, int64_t row_stride,
+                          int32_t sample_rate, int32_t frame_size, int32_t lags, int32_t lag_min, int32_t win_length,
+                          int32_t mode, void* stream) {
+  return detect_pitch<double>(x, out, workspace, rows, length, row_stride, sample_rate, frame_size, lags, lag_min,
+                              win_length, mode, stream);
 }
 
 }  // extern "C"

@@ -762,6 +762,36 @@ Tensor sliding_window_cmn(Tensor x, int64_t cmn_window, int64_t min_cmn_window, 
   return out;
 }
 
+// ---- aamd::detect_pitch (F.detect_pitch_frequency, F._compute_nccf; csrc/pitch.h) -------------------------------------------
+// x is (rows, L) with time stride 1, rows read in place through stride(0).  mode 0: float32 (rows, n_out) pitch;
+// mode 1: (rows, F, lags) NCCF of x's dtype.
+Tensor detect_pitch(Tensor x, int64_t sample_rate, int64_t frame_size, int64_t lags, int64_t lag_min, int64_t win_length,
+                    int64_t mode) {
+  STD_TORCH_CHECK(x.is_cuda(), "audio_amd: waveform must be on an MI355X (ROCm) device; there is no CPU kernel");
+  STD_TORCH_CHECK(x.scalar_type() == ScalarType::Float || x.scalar_type() == ScalarType::Double,
+                  "audio_amd: waveform must be float32 or float64");
+  STD_TORCH_CHECK(x.dim() == 2 && (x.size(1) <= 1 || x.stride(1) == 1), "audio_amd: waveform must be (rows, L) with time stride 1");
+  STD_TORCH_CHECK(frame_size >= 1, "audio_amd: frame_size must be >= 1");
+  const torch::stable::accelerator::DeviceGuard guard(x.get_device_index());
+  const int64_t rows = x.size(0), L = x.size(1), frames = (L + frame_size - 1) / frame_size;
+  Tensor out = mode == 1 ? torch::stable::new_empty(x, {rows, frames, lags})
+                         : torch::stable::new_empty(x, {rows, frames + (win_length - 1) / 2 - win_length + 1}, ScalarType::Float);
+  const int64_t ws_bytes = aamd_detect_pitch_workspace(rows, L, (int32_t)frame_size);
+  Tensor ws = torch::stable::new_empty(x, {ws_bytes / 4 > 0 ? ws_bytes / 4 : 1}, ScalarType::Int);
+  const void* xp = x.numel() ? x.data_ptr() : nullptr;
+  void* op = out.numel() ? out.data_ptr() : nullptr;
+  const int64_t rs = rows > 1 ? x.stride(0) : L;
+  if (x.scalar_type() == ScalarType::Double)
+    check(aamd_detect_pitch_f64(static_cast<const double*>(xp), op, ws.data_ptr(), rows, L, rs, (int32_t)sample_rate,
+                                (int32_t)frame_size, (int32_t)lags, (int32_t)lag_min, (int32_t)win_length, (int32_t)mode,
+                                current_stream(x)));
+  else
+    check(aamd_detect_pitch_f32(static_cast<const float*>(xp), op, ws.data_ptr(), rows, L, rs, (int32_t)sample_rate,
+                                (int32_t)frame_size, (int32_t)lags, (int32_t)lag_min, (int32_t)win_length, (int32_t)mode,
+                                current_stream(x)));
+  return out;
+}
+
 // ---- torchaudio::_lfilter_core_loop on the CUDA key (lfilter.cpp:118-134, iir_cuda.cu:37-79) ------------------------
 //   padded_out[n][c][i + n_order - 1] = in[n][c][i] - sum_{j < n_order-1} a_flipped[c][j] * padded_out[n][c][i + j]
 // = the pure recursion y = IIR(in; a) with a = flip(a_flipped), b = (1, 0, ...), no clamp: aamd_lfilter_f32 runs it as a
@@ -860,6 +890,7 @@ STABLE_TORCH_LIBRARY(aamd, m) {
   m.def("fftconvolve_f64(Tensor x, Tensor y, Tensor? x_row_of, Tensor? y_row_of, int rows, int start, int out_len) -> Tensor");
   m.def("compute_deltas(Tensor specgram, int win_length, int pad_mode, bool adjoint) -> Tensor");
   m.def("sliding_window_cmn(Tensor specgram, int cmn_window, int min_cmn_window, bool center, bool norm_vars, bool adjoint) -> Tensor");
+  m.def("detect_pitch(Tensor x, int sample_rate, int frame_size, int lags, int lag_min, int win_length, int mode) -> Tensor");
 }
 
 STABLE_TORCH_LIBRARY_IMPL(aamd, CUDA, m) {
@@ -893,6 +924,7 @@ STABLE_TORCH_LIBRARY_IMPL(aamd, CUDA, m) {
   m.impl("fftconvolve_f64", TORCH_BOX(&fftconvolve_f64));
   m.impl("compute_deltas", TORCH_BOX(&compute_deltas));
   m.impl("sliding_window_cmn", TORCH_BOX(&sliding_window_cmn));
+  m.impl("detect_pitch", TORCH_BOX(&detect_pitch));
 }
 
 // The reference's op.  libtorchaudio (when present) has already run

@@ -31,7 +31,7 @@ __all__ = [
     "lfilter", "biquad", "fftconvolve", "mel_scale", "filtfilt",
     "lowpass_biquad", "highpass_biquad", "allpass_biquad", "bandpass_biquad",
     "bandreject_biquad", "equalizer_biquad", "band_biquad", "treble_biquad", "bass_biquad", "deemph_biquad", "riaa_biquad",
-    "compute_deltas", "sliding_window_cmn",
+    "compute_deltas", "sliding_window_cmn", "detect_pitch_frequency",
 ]
 
 # --------------------------------------------------------------------------- #
@@ -2331,6 +2331,107 @@ def _sliding_window_cmn_eager(specgram: Tensor, cmn_window: int = 600, min_cmn_w
 
 
 # --------------------------------------------------------------------------- #
+# NCCF pitch tracker (csrc/pitch.h)                                           #
+# --------------------------------------------------------------------------- #
+
+_PITCH_MAX_FRAME = 8192
+_PITCH_MAX_LAGS = 16384
+
+
+def _pitch_sizes(length: int, sample_rate: int, frame_time: float, freq_low: int) -> Tuple[int, int, int]:
+    """(lags, frame_size, frames) with exactly the reference's expressions (_compute_nccf); its errors where it has them."""
+    lags = int(math.ceil(sample_rate / freq_low))
+    fs = int(math.ceil(sample_rate * frame_time))
+    F_ = int(math.ceil(length / fs))
+    if lags < 1:      # the reference's lag loop is empty: torch.cat([])
+        raise ValueError(f"torch.cat(): expected a non-empty list of Tensors (lags = ceil({sample_rate} / {freq_low}) = {lags})")
+    if fs < 0:
+        raise RuntimeError(f"audio_amd: detect_pitch_frequency: frame size ceil({sample_rate} * {frame_time}) = {fs} < 0")
+    return lags, fs, F_
+
+
+def _pitch_plan(length: int, sample_rate: int, frame_time: float, win_length: int, freq_low: int,
+                freq_high: int) -> Tuple[int, int, int, int, int]:
+    """(lags, frame_size, frames, lag_min, n_out) of detect_pitch_frequency, raising what the reference raises, in its
+    order; sizes this build does not serve raise NotImplementedError."""
+    lags, fs, F_ = _pitch_sizes(length, sample_rate, frame_time, freq_low)
+    lag_min = int(math.ceil(sample_rate / freq_high))
+    if lag_min < 0:
+        raise ValueError(f"audio_amd: detect_pitch_frequency: freq_high = {freq_high} gives a negative minimal lag")
+    if lag_min >= lags or lags // 2 <= lag_min:    # torch.max over nccf[..., lag_min:] or nccf[..., lag_min:lags // 2]
+        raise IndexError(f"max(): Expected reduction dim 2 to have non-zero size. (lag_min = {lag_min}, lags = {lags}: "
+                         "freq_high must be well above freq_low)")
+    p = (win_length - 1) // 2
+    if F_ == 0:
+        raise IndexError(f"index {p} is out of bounds for dimension 1 with size {p} (the waveform has no frame)")
+    if p <= 0:        # _median_smoothing's torch.cat(pad_length * [...])
+        raise ValueError(f"torch.cat(): expected a non-empty list of Tensors (win_length = {win_length} < 3)")
+    n_out = F_ + p - win_length + 1
+    if n_out < 1:     # _median_smoothing's unfold
+        raise RuntimeError(f"maximum size for tensor at dimension 1 is {F_ + p} but size is {win_length} "
+                           f"({F_} frames are fewer than one median window)")
+    if fs > _PITCH_MAX_FRAME or lags > _PITCH_MAX_LAGS:
+        raise NotImplementedError(f"audio_amd: detect_pitch_frequency serves frame sizes up to {_PITCH_MAX_FRAME} and up to "
+                                  f"{_PITCH_MAX_LAGS} lags (got {fs} and {lags})")
+    return lags, fs, F_, lag_min, n_out
+
+
+def _pitch_rows(waveform: Tensor) -> Tensor:
+    """(..., L) -> (rows, L) float32 / float64 with time stride 1, rows read in place where the strides allow."""
+    if waveform.dtype in LOW_PRECISION and waveform.is_cuda:
+        x = waveform.detach().float()
+    else:
+        _require_device(waveform, "waveform", allow_grad=True, allow_f64=True)
+        x = waveform.detach()
+    if x.dim() == 0:
+        raise ValueError("audio_amd: detect_pitch_frequency expects a (..., time) waveform, got a 0-d tensor")
+    return _rows2d(x)
+
+
+def _pitch_launch(x2: Tensor, sample_rate: int, fs: int, lags: int, lag_min: int, win_length: int, mode: int) -> Tensor:
+    """mode 0: float32 (rows, n_out) pitch; mode 1: (rows, F, lags) NCCF of x2's dtype."""
+    ops = _ops()
+    if ops is not None:
+        return ops.detect_pitch(x2, sample_rate, fs, lags, lag_min, win_length, mode)
+    rows, L = x2.shape
+    F_ = -(-L // fs)
+    if mode == 1:
+        out = torch.empty((rows, F_, lags), dtype=x2.dtype, device=x2.device)
+    else:
+        out = torch.empty((rows, F_ + (win_length - 1) // 2 - win_length + 1), dtype=torch.float32, device=x2.device)
+    Lb = _lib.lib()
+    ws = torch.empty((max(int(Lb.aamd_detect_pitch_workspace(rows, L, fs)) // 4, 1),), dtype=torch.int32, device=x2.device)
+    fn = Lb.aamd_detect_pitch_f64 if x2.dtype == torch.float64 else Lb.aamd_detect_pitch_f32
+    with torch.cuda.device(x2.device):
+        _lib.check(fn(_lib.ptr(x2) or None, _lib.ptr(out) or None, ws.data_ptr(), rows, L, x2.stride(0), sample_rate, fs,
+                      lags, lag_min, win_length, mode, _lib.current_stream(x2.device)))
+    return out
+
+
+def _compute_nccf(waveform: Tensor, sample_rate: int, frame_time: float, freq_low: int) -> Tensor:
+    r"""The NCCF of the reference's private helper: ``(..., L)`` -> ``(..., frames, lags)``, float64 for a float64 input and
+    float32 otherwise.  It is what detect_pitch_frequency's fused pick reads, bit for bit (the same kernel, mode 1)."""
+    x2 = _pitch_rows(waveform)
+    lags, fs, F_ = _pitch_sizes(x2.shape[-1], sample_rate, frame_time, freq_low)
+    if fs > _PITCH_MAX_FRAME or lags > _PITCH_MAX_LAGS:
+        raise NotImplementedError(f"audio_amd: _compute_nccf serves frame sizes up to {_PITCH_MAX_FRAME} and up to "
+                                  f"{_PITCH_MAX_LAGS} lags (got {fs} and {lags})")
+    out = _pitch_launch(x2, sample_rate, fs, lags, 0, 3, 1)
+    return out.view(tuple(waveform.shape[:-1]) + (F_, lags))
+
+
+def _detect_pitch_frequency_eager(waveform: Tensor, sample_rate: int, frame_time: float = 10 ** (-2), win_length: int = 30,
+                                  freq_low: int = 85, freq_high: int = 3400) -> Tensor:
+    r"""Pitch of a ``(..., time)`` waveform in Hz (reference: F.detect_pitch_frequency): the NCCF, both max reductions and
+    the 0.99 combine in one kernel, the median smoothing and the reciprocal in a second.  float32 out for every input dtype
+    (float64 inputs compute in float64, float16 / bfloat16 in float32); no gradient, as in the reference."""
+    x2 = _pitch_rows(waveform)
+    lags, fs, F_, lag_min, n_out = _pitch_plan(x2.shape[-1], sample_rate, frame_time, win_length, freq_low, freq_high)
+    out = _pitch_launch(x2, sample_rate, fs, lags, lag_min, win_length, 0)
+    return out.view(tuple(waveform.shape[:-1]) + (n_out,))
+
+
+# --------------------------------------------------------------------------- #
 # the public entry points                                                     #
 # --------------------------------------------------------------------------- #
 # Every public function is a small TorchScript-able front (the reference guarantees `torch.jit.script` on this surface:
@@ -2636,3 +2737,15 @@ def sliding_window_cmn(specgram: Tensor, cmn_window: int = 600, min_cmn_window: 
     if not torch.jit.is_scripting():
         return _sliding_window_cmn_eager(specgram, cmn_window, min_cmn_window, center, norm_vars)
     return torch.ops.audio_amd.sliding_window_cmn(specgram, cmn_window, min_cmn_window, center, norm_vars)
+
+
+def detect_pitch_frequency(waveform: Tensor, sample_rate: int, frame_time: float = 10 ** (-2), win_length: int = 30,
+                           freq_low: int = 85, freq_high: int = 3400) -> Tensor:
+    r"""Pitch in Hz of a ``(..., time)`` waveform (reference: F.detect_pitch_frequency); see
+    ``_detect_pitch_frequency_eager``."""
+    if not torch.jit.is_scripting():
+        if torch.compiler.is_compiling():
+            return torch.ops.audio_amd.detect_pitch_frequency(waveform, sample_rate, frame_time, win_length, freq_low,
+                                                              freq_high)
+        return _detect_pitch_frequency_eager(waveform, sample_rate, frame_time, win_length, freq_low, freq_high)
+    return torch.ops.audio_amd.detect_pitch_frequency(waveform, sample_rate, frame_time, win_length, freq_low, freq_high)

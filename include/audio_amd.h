@@ -45,6 +45,8 @@
  *   aamd_compute_deltas_f32   F.compute_deltas / T.ComputeDeltas (pad + grouped conv1d in the reference)
  *   aamd_sliding_window_cmn_f32  F.sliding_window_cmn / T.SlidingWindowCmn (a per-frame loop in the reference)
  *                             -- these two (and their _f64 forms) are additions to ABI 7, which stays 7
+ *   aamd_detect_pitch_f32     F.detect_pitch_frequency (_compute_nccf + _find_max_per_frame + _median_smoothing in the
+ *                             reference; an addition to ABI 7 as well)
  *
  * The reference-side binding a maintainer would add is shown in INTEGRATION.md.
  */
@@ -513,6 +515,25 @@ int aamd_sliding_window_cmn_f64(const double* x, double* out, void* workspace, i
                                 int64_t n_feat, int64_t stride_channel, int64_t stride_feat, int64_t stride_frame,
                                 int64_t cmn_window, int64_t min_cmn_window, int32_t center, int32_t norm_vars,
                                 int32_t adjoint, void* stream);
+
+/* ---- NCCF pitch tracker (additions to ABI 7; csrc/pitch.h) ----------------------------------------------------------- */
+
+/* F.detect_pitch_frequency (functional/functional.py, detect_pitch_frequency): x is `rows` rows of `length` samples,
+ * row r at x + r * row_stride (time stride 1).  The caller computes the sizes with the reference's expressions:
+ * frame_size = ceil(sample_rate * frame_time), lags = ceil(sample_rate / freq_low), lag_min = ceil(sample_rate / freq_high).
+ * mode 0: out is float32 (rows, n_out), n_out = F + p - win_length + 1 with F = ceil(length / frame_size) and
+ *         p = (win_length - 1) / 2: the median-smoothed pitch in Hz, float32 whatever the input type.  `workspace` holds
+ *         aamd_detect_pitch_workspace() bytes (one int32 lag per frame), 4-byte aligned.  Needs win_length >= 3,
+ *         0 <= lag_min < lags / 2 and n_out >= 1 (AAMD_EINVAL otherwise).
+ * mode 1: out is (rows, F, lags) of the input's type: the NCCF the pick of mode 0 reads, bit for bit; no workspace.
+ * frame_size > 8192 or lags > 16384 is AAMD_EUNSUPPORTED.  No gradient. */
+int64_t aamd_detect_pitch_workspace(int64_t rows, int64_t length, int32_t frame_size);
+int aamd_detect_pitch_f32(const float* x, void* out, void* workspace, int64_t rows, int64_t length, int64_t row_stride,
+                          int32_t sample_rate, int32_t frame_size, int32_t lags, int32_t lag_min, int32_t win_length,
+                          int32_t mode, void* stream);
+int aamd_detect_pitch_f64(const double* x, void* out, void* workspace, int64_t rows, int64_t length, int64_t row_stride,
+                          int32_t sample_rate, int32_t frame_size, int32_t lags, int32_t lag_min, int32_t win_length,
+                          int32_t mode, void* stream);
 
 #ifdef __cplusplus
 }
