@@ -144,6 +144,9 @@ _SIGS = {
     "aamd_detect_pitch_workspace": (C.c_int64, [C.c_int64, C.c_int64, C.c_int32]),
     "aamd_detect_pitch_f32": (C.c_int, [_P, _P, _P] + [C.c_int64] * 3 + [C.c_int32] * 6 + [_P]),
     "aamd_detect_pitch_f64": (C.c_int, [_P, _P, _P] + [C.c_int64] * 3 + [C.c_int32] * 6 + [_P]),
+    # SpecAugment masking (additions to ABI 7)
+    "aamd_spec_augment_iid": (C.c_int, [_P, _P] + [C.c_int64] * 6 + [C.c_int32] * 3 + [_P, _P, _P, C.c_uint64, _P, _P]),
+    "aamd_spec_augment_shared": (C.c_int, [_P, _P] + [C.c_int64] * 6 + [C.c_int32] * 3 + [_P, _P, _P, C.c_uint64, _P, _P]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS)

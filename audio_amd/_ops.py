@@ -56,6 +56,10 @@ _DEF.define("compute_deltas(Tensor specgram, int win_length, str mode) -> Tensor
 _DEF.define("sliding_window_cmn(Tensor specgram, int cmn_window, int min_cmn_window, bool center, bool norm_vars) -> Tensor")
 _DEF.define("detect_pitch_frequency(Tensor waveform, int sample_rate, float frame_time, int win_length, int freq_low, "
             "int freq_high) -> Tensor")
+_DEF.define("mask_along_axis(Tensor specgram, int mask_param, float mask_value, int axis, float p) -> Tensor")
+_DEF.define("mask_along_axis_iid(Tensor specgrams, int mask_param, float mask_value, int axis, float p) -> Tensor")
+_DEF.define("spec_augment(Tensor specgram, int n_time_masks, int time_mask_param, int n_freq_masks, int freq_mask_param, "
+            "bool iid_masks, float p, bool zero_masking) -> Tensor")
 _DEF.define("rnnt_features(Tensor waveform, Tensor window, Tensor fb, int n_fft, int hop_length, float gain, Tensor mean, "
             "Tensor invstddev, int right_padding) -> Tensor")
 
@@ -160,6 +164,9 @@ _register("rnnt_features", _rnnt_features)
 _register("compute_deltas", F.compute_deltas)
 _register("sliding_window_cmn", F.sliding_window_cmn)
 _register("detect_pitch_frequency", F.detect_pitch_frequency)
+_register("mask_along_axis", F._mask_along_axis_eager)
+_register("mask_along_axis_iid", F._mask_along_axis_iid_eager)
+_register("spec_augment", F._spec_augment_eager)
 
 
 # ---- Meta implementations: shapes / strides only ---------------------------------------------
@@ -298,3 +305,15 @@ def _detect_pitch_frequency_meta(waveform, sample_rate, frame_time, win_length, 
 
 
 _META.impl("detect_pitch_frequency", _detect_pitch_frequency_meta)
+
+
+def _masking_meta(specgram, *rest):
+    # a dense input keeps its strides in either order of the last two axes (masked_fill does); others come back contiguous
+    if specgram.dim() >= 2 and not specgram.is_contiguous() and specgram.transpose(-1, -2).is_contiguous():
+        return torch.empty_like(specgram.transpose(-1, -2), memory_format=torch.contiguous_format).transpose(-1, -2)
+    return torch.empty_like(specgram, memory_format=torch.contiguous_format)
+
+
+_META.impl("mask_along_axis", _masking_meta)
+_META.impl("mask_along_axis_iid", _masking_meta)
+_META.impl("spec_augment", _masking_meta)

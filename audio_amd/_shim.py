@@ -32,7 +32,9 @@ OPS = ("spectrogram", "mel_spectrogram", "mel_spectrogram_db", "mfcc_dct", "resa
        # the feature post-processing entries (F.compute_deltas, F.sliding_window_cmn; additions to ABI 7)
        "compute_deltas", "sliding_window_cmn",
        # the NCCF pitch tracker (F.detect_pitch_frequency, F._compute_nccf; an addition to ABI 7)
-       "detect_pitch")
+       "detect_pitch",
+       # SpecAugment masking: a whole policy in one launch (F.mask_along_axis[_iid], T.SpecAugment; an addition to ABI 7)
+       "spec_augment")
 
 _lock = threading.Lock()
 _handle = None
@@ -202,6 +204,10 @@ def _register_fakes() -> None:
         if mode == 1:
             return x.new_empty((x.shape[0], frames, lags))
         return x.new_empty((x.shape[0], frames + (win_length - 1) // 2 - win_length + 1), dtype=torch.float32)
+
+    @reg("aamd::spec_augment")
+    def _(x, draws, axes, params, starts, ends, time_inner, value_bits, value):
+        return x.new_empty(x.shape)
 
 
 def available() -> bool:

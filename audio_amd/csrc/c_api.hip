@@ -31,6 +31,7 @@
 #include "pitch.h"
 #include "resample.h"
 #include "resample_mfma.h"
+#include "spec_augment.h"
 #include "stft_generic.h"
 
 using namespace aamd;
@@ -1894,6 +1895,65 @@ int aamd_detect_pitch_f64(const double* x, void* out, void* workspace, int64_t r
                           int32_t mode, void* stream) {
   return detect_pitch<double>(x, out, workspace, rows, length, row_stride, sample_rate, frame_size, lags, lag_min,
                               win_length, mode, stream);
+}
+
+// ---- SpecAugment masking: a whole policy in one launch (csrc/spec_augment.h) --------------------------------------------
+// draws != nullptr: bounds from the raw draws (params); else the shared bounds (starts / ends).
+static int spec_augment(const void* x, void* out, int64_t examples, int64_t n_outer, int64_t n_inner, int64_t se, int64_t so,
+                        int64_t si, int32_t dtype, int32_t time_inner, int32_t n_masks, const int32_t* axes,
+                        const int64_t* params, const void* draws, const int64_t* starts, const int64_t* ends,
+                        uint64_t value_bits, const void* value_ptr, void* stream) {
+  DeviceScope dev_scope_(x);
+  AAMD_CHECK_ARG(examples >= 0 && n_outer >= 0 && n_inner >= 0, "bad sizes");
+  AAMD_CHECK_ARG(n_outer < (1ll << 31) && n_inner < (1ll << 31), "spec_augment: an axis of 2^31 or more elements");
+  AAMD_CHECK_ARG(dtype >= AAMD_SA_F32 && dtype <= AAMD_SA_BF16, "spec_augment: unknown element type");
+  AAMD_CHECK_ARG(n_masks >= 0 && n_masks <= sa::kMaxMasks, "spec_augment: at most 32 masks per launch");
+  AAMD_CHECK_ARG(n_masks == 0 || axes, "null mask table");
+  AAMD_CHECK_ARG(n_masks == 0 || (draws ? params != nullptr : (starts && ends)), "null mask table");
+  for (int m = 0; m < n_masks; ++m)
+    AAMD_CHECK_ARG(axes[m] == AAMD_SA_FREQ || axes[m] == AAMD_SA_TIME, "spec_augment: a mask axis is AAMD_SA_FREQ or AAMD_SA_TIME");
+  if (examples * n_outer * n_inner == 0) return AAMD_OK;
+  AAMD_CHECK_ARG(x && out, "null buffer");
+  sa::Plan p{};
+  p.E = examples; p.O = n_outer; p.I = n_inner;
+  p.xe = se; p.xo = so; p.xi = si;
+  p.draws = draws; p.value_ptr = value_ptr; p.value_bits = value_bits;
+  p.dtype = dtype;
+  sa::plan_masks(p, time_inner, n_masks, axes, draws ? params : nullptr, starts, ends);
+  const int es = sa::elem_size(dtype);
+  const bool dense = sa::plan_is_dense(p, x, out);
+  sa::plan_chunks(p, dense, es);
+  const int64_t blocks = examples * p.chunks;
+  AAMD_CHECK_ARG(blocks < (1ll << 31), "too many examples for one launch");
+  hipStream_t s = (hipStream_t)stream;
+  const dim3 grid((unsigned)blocks), block(sa::kThreads);
+  if (dense) {
+    if (es == 2) hipLaunchKernelGGL((sa::spec_augment_kernel<2, 1>), grid, block, 0, s, x, out, p);
+    else if (es == 4) hipLaunchKernelGGL((sa::spec_augment_kernel<4, 1>), grid, block, 0, s, x, out, p);
+    else hipLaunchKernelGGL((sa::spec_augment_kernel<8, 1>), grid, block, 0, s, x, out, p);
+  } else {
+    if (es == 2) hipLaunchKernelGGL((sa::spec_augment_kernel<2, 0>), grid, block, 0, s, x, out, p);
+    else if (es == 4) hipLaunchKernelGGL((sa::spec_augment_kernel<4, 0>), grid, block, 0, s, x, out, p);
+    else hipLaunchKernelGGL((sa::spec_augment_kernel<8, 0>), grid, block, 0, s, x, out, p);
+  }
+  return launch_check();
+}
+
+int aamd_spec_augment_iid(const void* x, void* out, int64_t examples, int64_t n_outer, int64_t n_inner,
+                          int64_t stride_example, int64_t stride_outer, int64_t stride_inner, int32_t dtype,
+                          int32_t time_inner, int32_t n_masks, const int32_t* axes, const int64_t* mask_params,
+                          const void* draws, uint64_t value_bits, const void* value_ptr, void* stream) {
+  AAMD_CHECK_ARG(n_masks <= 0 || draws, "spec_augment: null draws");
+  return spec_augment(x, out, examples, n_outer, n_inner, stride_example, stride_outer, stride_inner, dtype, time_inner,
+                      n_masks, axes, mask_params, draws, nullptr, nullptr, value_bits, value_ptr, stream);
+}
+
+int aamd_spec_augment_shared(const void* x, void* out, int64_t examples, int64_t n_outer, int64_t n_inner,
+                             int64_t stride_example, int64_t stride_outer, int64_t stride_inner, int32_t dtype,
+                             int32_t time_inner, int32_t n_masks, const int32_t* axes, const int64_t* starts,
+                             const int64_t* ends, uint64_t value_bits, const void* value_ptr, void* stream) {
+  return spec_augment(x, out, examples, n_outer, n_inner, stride_example, stride_outer, stride_inner, dtype, time_inner,
+                      n_masks, axes, nullptr, nullptr, starts, ends, value_bits, value_ptr, stream);
 }
 
 }  // extern "C"

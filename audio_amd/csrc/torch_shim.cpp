@@ -792,6 +792,54 @@ Tensor detect_pitch(Tensor x, int64_t sample_rate, int64_t frame_size, int64_t l
   return out;
 }
 
+// ---- aamd::spec_augment (F.mask_along_axis[_iid], T.SpecAugment; csrc/spec_augment.h) ---------------------------------------
+// x is (examples, outer, inner) of any strides, `inner` the axis the caller's storage is contiguous along; the result is dense
+// in that order.  draws given: bounds from the raw draws ([masks][2][examples] of x's dtype) and params; else the shared
+// bounds starts / ends.  mask_value: the 0-d device tensor `value` (x's dtype), or the element's bits in value_bits.
+Tensor spec_augment(Tensor x, std::optional<Tensor> draws, std::vector<int64_t> axes, std::vector<int64_t> params,
+                    std::vector<int64_t> starts, std::vector<int64_t> ends, bool time_inner, int64_t value_bits,
+                    std::optional<Tensor> value) {
+  STD_TORCH_CHECK(x.is_cuda(), "audio_amd: specgram must be on an MI355X (ROCm) device; there is no CPU kernel");
+  STD_TORCH_CHECK(x.dim() == 3, "audio_amd: specgram must have 3 dimensions");
+  int32_t dtype = -1;
+  switch (x.scalar_type()) {
+    case ScalarType::Float: dtype = AAMD_SA_F32; break;
+    case ScalarType::Double: dtype = AAMD_SA_F64; break;
+    case ScalarType::Half: dtype = AAMD_SA_F16; break;
+    case ScalarType::BFloat16: dtype = AAMD_SA_BF16; break;
+    default: break;
+  }
+  STD_TORCH_CHECK(dtype >= 0, "audio_amd: specgram must be float16, bfloat16, float32 or float64");
+  const int64_t n = (int64_t)axes.size();
+  const void* vp = nullptr;
+  if (value.has_value()) {
+    STD_TORCH_CHECK(value->is_cuda() && value->numel() == 1 && value->scalar_type() == x.scalar_type(),
+                    "audio_amd: mask_value must be one device element of specgram's dtype");
+    same_device(x, *value);
+    vp = value->data_ptr();
+  }
+  const torch::stable::accelerator::DeviceGuard guard(x.get_device_index());
+  Tensor out = torch::stable::new_empty(x, {x.size(0), x.size(1), x.size(2)});
+  const void* xp = x.numel() ? x.data_ptr() : nullptr;
+  void* op = out.numel() ? out.data_ptr() : nullptr;
+  std::vector<int32_t> ax(axes.begin(), axes.end());
+  if (draws.has_value()) {
+    STD_TORCH_CHECK((int64_t)params.size() == n, "audio_amd: one mask_param per mask");
+    STD_TORCH_CHECK(draws->is_cuda() && draws->is_contiguous() && draws->scalar_type() == x.scalar_type() &&
+                    draws->numel() == n * 2 * x.size(0), "audio_amd: draws must be (masks, 2, examples) of specgram's dtype");
+    same_device(x, *draws);
+    check(aamd_spec_augment_iid(xp, op, x.size(0), x.size(1), x.size(2), x.stride(0), x.stride(1), x.stride(2), dtype,
+                                time_inner ? 1 : 0, (int32_t)n, ax.data(), params.data(), draws->numel() ? draws->data_ptr() : nullptr,
+                                (uint64_t)value_bits, vp, current_stream(x)));
+  } else {
+    STD_TORCH_CHECK((int64_t)starts.size() == n && (int64_t)ends.size() == n, "audio_amd: one start and one end per mask");
+    check(aamd_spec_augment_shared(xp, op, x.size(0), x.size(1), x.size(2), x.stride(0), x.stride(1), x.stride(2), dtype,
+                                   time_inner ? 1 : 0, (int32_t)n, ax.data(), starts.data(), ends.data(), (uint64_t)value_bits, vp,
+                                   current_stream(x)));
+  }
+  return out;
+}
+
 // ---- torchaudio::_lfilter_core_loop on the CUDA key (lfilter.cpp:118-134, iir_cuda.cu:37-79) ------------------------
 //   padded_out[n][c][i + n_order - 1] = in[n][c][i] - sum_{j < n_order-1} a_flipped[c][j] * padded_out[n][c][i + j]
 // = the pure recursion y = IIR(in; a) with a = flip(a_flipped), b = (1, 0, ...), no clamp: aamd_lfilter_f32 runs it as a
@@ -891,6 +939,8 @@ STABLE_TORCH_LIBRARY(aamd, m) {
   m.def("compute_deltas(Tensor specgram, int win_length, int pad_mode, bool adjoint) -> Tensor");
   m.def("sliding_window_cmn(Tensor specgram, int cmn_window, int min_cmn_window, bool center, bool norm_vars, bool adjoint) -> Tensor");
   m.def("detect_pitch(Tensor x, int sample_rate, int frame_size, int lags, int lag_min, int win_length, int mode) -> Tensor");
+  m.def("spec_augment(Tensor x, Tensor? draws, int[] axes, int[] params, int[] starts, int[] ends, bool time_inner, "
+        "int value_bits, Tensor? value) -> Tensor");
 }
 
 STABLE_TORCH_LIBRARY_IMPL(aamd, CUDA, m) {
@@ -925,6 +975,7 @@ STABLE_TORCH_LIBRARY_IMPL(aamd, CUDA, m) {
   m.impl("compute_deltas", TORCH_BOX(&compute_deltas));
   m.impl("sliding_window_cmn", TORCH_BOX(&sliding_window_cmn));
   m.impl("detect_pitch", TORCH_BOX(&detect_pitch));
+  m.impl("spec_augment", TORCH_BOX(&spec_augment));
 }
 
 // The reference's op.  libtorchaudio (when present) has already run

@@ -31,7 +31,7 @@ __all__ = [
     "lfilter", "biquad", "fftconvolve", "mel_scale", "filtfilt",
     "lowpass_biquad", "highpass_biquad", "allpass_biquad", "bandpass_biquad",
     "bandreject_biquad", "equalizer_biquad", "band_biquad", "treble_biquad", "bass_biquad", "deemph_biquad", "riaa_biquad",
-    "compute_deltas", "sliding_window_cmn", "detect_pitch_frequency",
+    "compute_deltas", "sliding_window_cmn", "detect_pitch_frequency", "mask_along_axis", "mask_along_axis_iid",
 ]
 
 # --------------------------------------------------------------------------- #
@@ -2432,6 +2432,232 @@ def _detect_pitch_frequency_eager(waveform: Tensor, sample_rate: int, frame_time
 
 
 # --------------------------------------------------------------------------- #
+# SpecAugment masking (csrc/spec_augment.h)                                   #
+# --------------------------------------------------------------------------- #
+
+_SA_FREQ, _SA_TIME = 0, 1                                      # axis tags of the C ABI (AAMD_SA_FREQ / AAMD_SA_TIME)
+_SA_DTYPES = {torch.float32: 0, torch.float64: 1, torch.float16: 2, torch.bfloat16: 3}
+_SA_BITS = {2: torch.int16, 4: torch.int32, 8: torch.int64}
+_SA_MAX_MASKS = 32                                             # per launch; longer policies chain launches
+
+
+def _get_mask_param(mask_param: int, p: float, axis_length: int) -> int:
+    if p == 1.0:
+        return mask_param
+    return min(mask_param, int(axis_length * p))
+
+
+def _sa_require(x: Tensor, what: str) -> None:
+    if not x.is_floating_point():
+        raise TypeError(f"audio_amd: {what} must be a floating-point tensor (got {x.dtype})")
+    if not x.is_cuda:
+        raise RuntimeError(f"audio_amd: {what} must be on an MI355X (ROCm) device, got {x.device}. "
+                           "The HIP kernels have no CPU fallback.")
+
+
+def _sa_check(dim: int, min_dim: int, axis: int, p: float) -> None:
+    if dim < min_dim:
+        if min_dim == 3:
+            raise ValueError(f"Spectrogram must have at least three dimensions ({dim} given).")
+        raise ValueError(f"Spectrogram must have at least two dimensions (time and frequency) ({dim} given).")
+    if axis not in [dim - 2, dim - 1]:
+        raise ValueError("Only Frequency and Time masking are supported"
+                         f" (axis {dim - 2} and axis {dim - 1} supported; {axis} given).")
+    if not 0.0 <= p <= 1.0:
+        raise ValueError(f"The value of p must be between 0.0 and 1.0 ({p} given).")
+
+
+def _sa_value_bits(value: float, dtype: torch.dtype) -> int:
+    """mask_value as the element's bits (unsigned), converted the way masked_fill converts a Python scalar."""
+    def make():
+        t = torch.full((), value, dtype=dtype)
+        return int(t.view(_SA_BITS[t.element_size()]).item()) & ((1 << (8 * t.element_size())) - 1)
+    return _cached(("sa_value_bits", float(value), dtype), make)
+
+
+def _sa_launch(x3: Tensor, time_inner: bool, draws: Optional[Tensor], axes: List[int], params: List[int],
+               starts: List[int], ends: List[int], bits: int, value: Optional[Tensor]) -> Tensor:
+    """(examples, outer, inner) of any strides -> dense, at most _SA_MAX_MASKS masks, one launch."""
+    ops = _ops()
+    if ops is not None:
+        return ops.spec_augment(x3, draws, axes, params, starts, ends, time_inner, bits - (1 << 64) if bits >= 1 << 63 else bits,
+                                value)
+    out = torch.empty(x3.shape, dtype=x3.dtype, device=x3.device)
+    n = len(axes)
+    ax = (C.c_int32 * max(n, 1))(*axes)
+    common = (_lib.ptr(x3) or None, _lib.ptr(out) or None, x3.shape[0], x3.shape[1], x3.shape[2], x3.stride(0), x3.stride(1),
+              x3.stride(2), _SA_DTYPES[x3.dtype], int(time_inner), n, ax)
+    vp = value.data_ptr() if value is not None else None
+    with torch.cuda.device(x3.device):
+        if draws is not None:
+            _lib.check(_lib.lib().aamd_spec_augment_iid(*common, (C.c_int64 * max(n, 1))(*params), _lib.ptr(draws) or None,
+                                                        bits, vp, _lib.current_stream(x3.device)))
+        else:
+            _lib.check(_lib.lib().aamd_spec_augment_shared(*common, (C.c_int64 * max(n, 1))(*starts),
+                                                           (C.c_int64 * max(n, 1))(*ends), bits, vp,
+                                                           _lib.current_stream(x3.device)))
+    return out
+
+
+def _sa_run(x: Tensor, draws: Optional[Tensor], plan, bounds, value) -> Tensor:
+    """The policy over x (..., freq, time): `plan` lists (axis tag, mask_param) per mask; iid bounds come from `draws`
+    (masks, 2, examples), shared ones from `bounds` [(start, end)].  A dense x in either order of its last two axes is
+    streamed along its own contiguous axis and the result has x's strides; anything else is gathered into a contiguous
+    result."""
+    shape = tuple(x.shape)
+    n_freq, n_time = shape[-2], shape[-1]
+    examples = 1
+    for d in shape[:-2]:
+        examples *= d
+    if x.is_contiguous():
+        x3, time_inner = x.view(examples, n_freq, n_time), True
+    elif x.transpose(-1, -2).is_contiguous():                      # frame-major: what every MelSpectrogram here returns
+        x3, time_inner = x.transpose(-1, -2).view(examples, n_time, n_freq), False
+    else:
+        x3, time_inner = x.reshape(examples, n_freq, n_time), True
+    bits, vt = 0, None
+    if isinstance(value, Tensor):
+        vt = value.detach().to(device=x.device, dtype=x.dtype).reshape(())
+    else:
+        bits = _sa_value_bits(value, x.dtype)
+    out = x3
+    for at in range(0, max(len(plan), 1), _SA_MAX_MASKS):
+        part = plan[at:at + _SA_MAX_MASKS]
+        axes = [a for a, _ in part]
+        if draws is not None:
+            out = _sa_launch(out, time_inner, draws[at:at + len(part)], axes, [m for _, m in part], [], [], bits, vt)
+        else:
+            b = bounds[at:at + len(part)]
+            out = _sa_launch(out, time_inner, None, axes, [], [s_ for s_, _ in b], [e_ for _, e_ in b], bits, vt)
+    if time_inner:
+        return out.view(shape)
+    return out.view(shape[:-2] + (n_time, n_freq)).transpose(-1, -2)
+
+
+class _SpecAugmentFunction(torch.autograd.Function):
+    """out = x (1 - m) + v m.  The gradient to x is the same masks over the cotangent with value 0 (its own adjoint, so
+    every order runs on the kernel); a tensor mask_value receives what the masks removed, (g - g_x).sum()."""
+
+    @staticmethod
+    def forward(ctx, x, value, draws, plan, bounds):
+        ctx.masks = (draws, plan, bounds)
+        ctx.value_grad = isinstance(value, Tensor) and value.requires_grad
+        ctx.value_meta = (value.shape, value.dtype, value.device) if isinstance(value, Tensor) else None
+        return _sa_run(x, draws, plan, bounds, value)
+
+    @staticmethod
+    def backward(ctx, g):
+        draws, plan, bounds = ctx.masks
+        gx = gv = None
+        if ctx.needs_input_grad[0] or ctx.value_grad:
+            if torch.is_grad_enabled():
+                gx = _SpecAugmentFunction.apply(g, 0.0, draws, plan, bounds)
+            else:
+                gx = _sa_run(g, draws, plan, bounds, 0.0)
+        if ctx.value_grad:
+            shape, dtype, device = ctx.value_meta
+            gv = (g - gx).sum().to(device=device, dtype=dtype).reshape(shape)
+        return (gx if ctx.needs_input_grad[0] else None), gv, None, None, None
+
+
+def _spec_augment_apply(x: Tensor, draws_or_bounds, plan, mask_value=0.0) -> Tensor:
+    r"""A masking policy with explicit masks over ``x`` (..., freq, time), any number of masks: ``plan`` lists one
+    ``(axis, mask_param)`` per mask, axis 0 for frequency and 1 for time (or ``-2`` / ``-1``).  ``draws_or_bounds`` is either
+    the raw uniform draws, a ``(masks, 2) + x.shape[:-2]`` tensor of ``x``'s dtype on its device (per-example masks with the
+    arithmetic of F.mask_along_axis_iid), or a list of shared ``(start, end)`` pairs (mask_param is then unused).
+    ``mask_value`` is a number or a one-element tensor (read on the device: no synchronisation)."""
+    _sa_require(x, "specgram")
+    if x.dim() < 2:
+        raise ValueError(f"Spectrogram must have at least two dimensions (time and frequency) ({x.dim()} given).")
+    plan = [(a, 0) if isinstance(a, int) else (a[0], int(a[1])) for a in plan]
+    plan = [(_SA_TIME if a in (_SA_TIME, -1) else _SA_FREQ, m) for a, m in plan]
+    draws = bounds = None
+    if isinstance(draws_or_bounds, Tensor):
+        draws = draws_or_bounds
+        if draws.dtype != x.dtype or draws.device != x.device or tuple(draws.shape) != (len(plan), 2) + tuple(x.shape[:-2]):
+            raise ValueError("audio_amd: draws must be a (masks, 2) + specgram.shape[:-2] tensor of specgram's dtype on its device")
+        draws = draws.contiguous().view(len(plan), 2, -1) if draws.numel() else draws.reshape(len(plan), 2, 0)
+    else:
+        bounds = [(int(s_), int(e_)) for s_, e_ in draws_or_bounds]
+        if len(bounds) != len(plan):
+            raise ValueError("audio_amd: one (start, end) pair per mask")
+    wants = x.requires_grad or (isinstance(mask_value, Tensor) and mask_value.requires_grad)
+    if torch.is_grad_enabled() and wants:
+        return _SpecAugmentFunction.apply(x, mask_value, draws, plan, bounds)
+    return _sa_run(x, draws, plan, bounds, mask_value)
+
+
+def _sa_draw_iid(specgrams: Tensor, n_masks: int) -> Tensor:
+    """The reference's draws, in its order: per mask torch.rand(lead) for `value`, then for `min_value`, of the tensor's
+    dtype on its device -- each written into its slice of one buffer (a seeded call reproduces the reference's masks)."""
+    lead = specgrams.shape[:-2]
+    draws = torch.empty((n_masks, 2) + tuple(lead), dtype=specgrams.dtype, device=specgrams.device)
+    for m in range(n_masks):
+        torch.rand(lead, device=specgrams.device, dtype=specgrams.dtype, out=draws[m, 0])
+        torch.rand(lead, device=specgrams.device, dtype=specgrams.dtype, out=draws[m, 1])
+    return draws
+
+
+def _sa_draw_shared(mask_param: int, size: int) -> Tuple[int, int]:
+    """The reference's shared mask: float32 draws on the CPU whatever the tensor's dtype."""
+    value = torch.rand(1) * mask_param
+    min_value = torch.rand(1) * (size - value)
+    start = int(min_value.long())
+    end = start + int(value.long())
+    if end - start >= mask_param:
+        raise ValueError("Number of columns to be masked should be less than mask_param")
+    return start, end
+
+
+def _mask_along_axis_iid_eager(specgrams: Tensor, mask_param: int, mask_value, axis: int, p: float = 1.0) -> Tensor:
+    r"""Per-example masks along frequency or time (reference: F.mask_along_axis_iid), one launch: the two raw draws go to
+    the kernel, which derives every example's [start, end) itself in the tensor's dtype."""
+    dim = specgrams.dim()
+    _sa_check(dim, 3, axis, p)
+    mask_param = _get_mask_param(mask_param, p, specgrams.shape[axis])
+    if mask_param < 1:
+        return specgrams
+    _sa_require(specgrams, "specgrams")
+    draws = _sa_draw_iid(specgrams, 1)
+    return _spec_augment_apply(specgrams, draws, [(_SA_TIME if axis == dim - 1 else _SA_FREQ, mask_param)], mask_value)
+
+
+def _mask_along_axis_eager(specgram: Tensor, mask_param: int, mask_value, axis: int, p: float = 1.0) -> Tensor:
+    r"""One mask shared by every example (reference: F.mask_along_axis); its bounds travel in the kernel arguments."""
+    dim = specgram.dim()
+    _sa_check(dim, 2, axis, p)
+    mask_param = _get_mask_param(mask_param, p, specgram.shape[axis])
+    if mask_param < 1:
+        return specgram
+    _sa_require(specgram, "specgram")
+    bounds = [_sa_draw_shared(mask_param, specgram.shape[axis])]
+    return _spec_augment_apply(specgram, bounds, [(_SA_TIME if axis == dim - 1 else _SA_FREQ, mask_param)], mask_value)
+
+
+def _spec_augment_eager(specgram: Tensor, n_time_masks: int, time_mask_param: int, n_freq_masks: int, freq_mask_param: int,
+                        iid_masks: bool = True, p: float = 1.0, zero_masking: bool = False) -> Tensor:
+    r"""T.SpecAugment's forward: all time masks, then all frequency masks, in ONE launch (the union of the masks does not
+    depend on their order once mask_value is fixed).  mask_value = specgram.mean() stays on the device."""
+    dim = specgram.dim()
+    iid = dim > 2 and iid_masks
+    _sa_check(dim, 3 if iid else 2, dim - 1, p)
+    plan = []
+    for n, param, axis in ((n_time_masks, time_mask_param, dim - 1), (n_freq_masks, freq_mask_param, dim - 2)):
+        param = _get_mask_param(param, p, specgram.shape[axis])
+        if param >= 1:
+            plan += [(_SA_TIME if axis == dim - 1 else _SA_FREQ, param)] * max(n, 0)
+    if not plan:
+        return specgram
+    _sa_require(specgram, "specgram")
+    mask_value = 0.0 if zero_masking else specgram.mean()
+    if iid:
+        masks = _sa_draw_iid(specgram, len(plan))
+    else:
+        masks = [_sa_draw_shared(m, specgram.shape[-1] if a == _SA_TIME else specgram.shape[-2]) for a, m in plan]
+    return _spec_augment_apply(specgram, masks, plan, mask_value)
+
+
+# --------------------------------------------------------------------------- #
 # the public entry points                                                     #
 # --------------------------------------------------------------------------- #
 # Every public function is a small TorchScript-able front (the reference guarantees `torch.jit.script` on this surface:
@@ -2749,3 +2975,28 @@ def detect_pitch_frequency(waveform: Tensor, sample_rate: int, frame_time: float
                                                               freq_high)
         return _detect_pitch_frequency_eager(waveform, sample_rate, frame_time, win_length, freq_low, freq_high)
     return torch.ops.audio_amd.detect_pitch_frequency(waveform, sample_rate, frame_time, win_length, freq_low, freq_high)
+
+
+def mask_along_axis_iid(specgrams: Tensor, mask_param: int, mask_value: float, axis: int, p: float = 1.0) -> Tensor:
+    r"""Per-example masks along ``axis`` of a ``(..., freq, time)`` tensor with at least three dimensions (reference:
+    F.mask_along_axis_iid); see ``_mask_along_axis_iid_eager``.  The input itself is returned when the effective
+    ``mask_param`` is below 1."""
+    if not torch.jit.is_scripting():
+        if not torch.compiler.is_compiling():
+            return _mask_along_axis_iid_eager(specgrams, mask_param, mask_value, axis, p)
+    if p >= 0.0 and p <= 1.0 and (axis == specgrams.dim() - 1 or axis == specgrams.dim() - 2) and specgrams.dim() >= 3:
+        if _get_mask_param(mask_param, p, specgrams.size(axis)) < 1:
+            return specgrams
+    return torch.ops.audio_amd.mask_along_axis_iid(specgrams, mask_param, mask_value, axis, p)
+
+
+def mask_along_axis(specgram: Tensor, mask_param: int, mask_value: float, axis: int, p: float = 1.0) -> Tensor:
+    r"""One mask along ``axis`` of a ``(..., freq, time)`` tensor, shared by every example (reference: F.mask_along_axis);
+    see ``_mask_along_axis_eager``.  The input itself is returned when the effective ``mask_param`` is below 1."""
+    if not torch.jit.is_scripting():
+        if not torch.compiler.is_compiling():
+            return _mask_along_axis_eager(specgram, mask_param, mask_value, axis, p)
+    if p >= 0.0 and p <= 1.0 and (axis == specgram.dim() - 1 or axis == specgram.dim() - 2) and specgram.dim() >= 2:
+        if _get_mask_param(mask_param, p, specgram.size(axis)) < 1:
+            return specgram
+    return torch.ops.audio_amd.mask_along_axis(specgram, mask_param, mask_value, axis, p)

@@ -1,5 +1,6 @@
 """Drop-in replacements for the hot-path modules of ``torchaudio.transforms``:
-Spectrogram, MelScale, MelSpectrogram, AmplitudeToDB, MFCC, Resample, FFTConvolve, ComputeDeltas, SlidingWindowCmn.
+Spectrogram, MelScale, MelSpectrogram, AmplitudeToDB, MFCC, Resample, FFTConvolve, ComputeDeltas, SlidingWindowCmn,
+FrequencyMasking, TimeMasking, SpecAugment.
 
 Constructor / forward signatures, registered buffer names (``window``, ``fb``, ``dct_mat``,
 ``kernel``), shapes, strides, warnings and error messages follow
@@ -32,7 +33,7 @@ _norm_mode = F._norm_mode      # `normalized` as the op schemas' integer: 0 none
 
 __all__ = ["Spectrogram", "InverseSpectrogram", "GriffinLim", "TimeStretch", "PitchShift", "Speed", "SpeedPerturbation",
            "MelScale", "MelSpectrogram", "AmplitudeToDB", "MFCC", "Resample", "FFTConvolve", "ComputeDeltas",
-           "SlidingWindowCmn"]
+           "SlidingWindowCmn", "FrequencyMasking", "TimeMasking", "SpecAugment"]
 
 
 class Spectrogram(torch.nn.Module):
@@ -332,6 +333,72 @@ class SlidingWindowCmn(torch.nn.Module):
                 return torch.ops.audio_amd.sliding_window_cmn(specgram, self.cmn_window, self.min_cmn_window, self.center,
                                                               self.norm_vars)
         return F.sliding_window_cmn(specgram, self.cmn_window, self.min_cmn_window, self.center, self.norm_vars)
+
+
+class _AxisMasking(torch.nn.Module):
+    r"""One mask along frequency or time (reference: _transforms.py, _AxisMasking); no buffers."""
+    __constants__ = ["mask_param", "axis", "iid_masks", "p"]
+
+    def __init__(self, mask_param: int, axis: int, iid_masks: bool, p: float = 1.0) -> None:
+        super().__init__()
+        self.mask_param = mask_param
+        self.axis = axis
+        self.iid_masks = iid_masks
+        self.p = p
+
+    def forward(self, specgram: Tensor, mask_value: float = 0.0) -> Tensor:
+        if self.iid_masks:
+            return F.mask_along_axis_iid(specgram, self.mask_param, mask_value, self.axis + specgram.dim() - 3, p=self.p)
+        else:
+            return F.mask_along_axis(specgram, self.mask_param, mask_value, self.axis + specgram.dim() - 3, p=self.p)
+
+
+class FrequencyMasking(_AxisMasking):
+    r"""A mask of up to ``freq_mask_param`` bins along frequency of a ``(..., freq, time)`` tensor (reference:
+    T.FrequencyMasking): shared by every example, or one per example with ``iid_masks`` (three dimensions or more)."""
+
+    def __init__(self, freq_mask_param: int, iid_masks: bool = False) -> None:
+        super(FrequencyMasking, self).__init__(freq_mask_param, 1, iid_masks)
+
+
+class TimeMasking(_AxisMasking):
+    r"""A mask of up to ``time_mask_param`` frames (and at most ``p`` of the axis) along time (reference: T.TimeMasking)."""
+
+    def __init__(self, time_mask_param: int, iid_masks: bool = False, p: float = 1.0) -> None:
+        if not 0.0 <= p <= 1.0:
+            raise ValueError(f"The value of p must be between 0.0 and 1.0 ({p} given).")
+        super(TimeMasking, self).__init__(time_mask_param, 2, iid_masks, p=p)
+
+
+class SpecAugment(torch.nn.Module):
+    r"""Time masks, then frequency masks, filled with zero or the tensor's mean (reference: T.SpecAugment).  The whole
+    policy is one kernel launch whatever the number of masks (csrc/spec_augment.h); no buffers."""
+    __constants__ = ["n_time_masks", "time_mask_param", "n_freq_masks", "freq_mask_param", "iid_masks", "p", "zero_masking"]
+
+    def __init__(self, n_time_masks: int, time_mask_param: int, n_freq_masks: int, freq_mask_param: int,
+                 iid_masks: bool = True, p: float = 1.0, zero_masking: bool = False) -> None:
+        super(SpecAugment, self).__init__()
+        self.n_time_masks = n_time_masks
+        self.time_mask_param = time_mask_param
+        self.n_freq_masks = n_freq_masks
+        self.freq_mask_param = freq_mask_param
+        self.iid_masks = iid_masks
+        self.p = p
+        self.zero_masking = zero_masking
+
+    def forward(self, specgram: Tensor) -> Tensor:
+        if not torch.jit.is_scripting():
+            if not torch.compiler.is_compiling():
+                return F._spec_augment_eager(specgram, self.n_time_masks, self.time_mask_param, self.n_freq_masks,
+                                             self.freq_mask_param, self.iid_masks, self.p, self.zero_masking)
+        if specgram.dim() >= 2 and self.p >= 0.0 and self.p <= 1.0:
+            # no mask at all: the input itself, decided before the op
+            no_time = self.n_time_masks < 1 or F._get_mask_param(self.time_mask_param, self.p, specgram.size(-1)) < 1
+            no_freq = self.n_freq_masks < 1 or F._get_mask_param(self.freq_mask_param, self.p, specgram.size(-2)) < 1
+            if no_time and no_freq:
+                return specgram
+        return torch.ops.audio_amd.spec_augment(specgram, self.n_time_masks, self.time_mask_param, self.n_freq_masks,
+                                                self.freq_mask_param, self.iid_masks, self.p, self.zero_masking)
 
 
 class MelScale(torch.nn.Module):

@@ -45,6 +45,9 @@
  *   aamd_compute_deltas_f32   F.compute_deltas / T.ComputeDeltas (pad + grouped conv1d in the reference)
  *   aamd_sliding_window_cmn_f32  F.sliding_window_cmn / T.SlidingWindowCmn (a per-frame loop in the reference)
  *                             -- these two (and their _f64 forms) are additions to ABI 7, which stays 7
+ *   aamd_spec_augment_iid     F.mask_along_axis_iid / T.SpecAugment (a dozen element-wise launches and one masked_fill
+ *   aamd_spec_augment_shared  per mask in the reference); F.mask_along_axis / T.FrequencyMasking / T.TimeMasking
+ *                             -- additions to ABI 7 as well
  *   aamd_detect_pitch_f32     F.detect_pitch_frequency (_compute_nccf + _find_max_per_frame + _median_smoothing in the
  *                             reference; an addition to ABI 7 as well)
  *
@@ -534,6 +537,36 @@ int aamd_detect_pitch_f32(const float* x, void* out, void* workspace, int64_t ro
 int aamd_detect_pitch_f64(const double* x, void* out, void* workspace, int64_t rows, int64_t length, int64_t row_stride,
                           int32_t sample_rate, int32_t frame_size, int32_t lags, int32_t lag_min, int32_t win_length,
                           int32_t mode, void* stream);
+
+/* ---- SpecAugment masking (additions to ABI 7; csrc/spec_augment.h) --------------------------------------------------- */
+
+/* element types of aamd_spec_augment_*: they decide the arithmetic of the mask bounds; elements move as 2 / 4 / 8 bytes */
+enum { AAMD_SA_F32 = 0, AAMD_SA_F64 = 1, AAMD_SA_F16 = 2, AAMD_SA_BF16 = 3 };
+/* axis tag of one mask */
+enum { AAMD_SA_FREQ = 0, AAMD_SA_TIME = 1 };
+
+/* A whole masking policy in one launch (functional/functional.py, mask_along_axis_iid / mask_along_axis; transforms,
+ * SpecAugment): out[e, o, i] = mask_value where one of the n_masks masks covers (e, o, i), else a bit copy of x[e, o, i].
+ * x is (examples, n_outer, n_inner) through its element strides; out is dense in that order.  The caller names as `inner`
+ * the axis its storage is contiguous along and says with time_inner whether that axis is time (a time-contiguous
+ * (..., freq, time) tensor) or frequency (time_inner = 0: the frame-major storage MelSpectrogram returns); mask m covers
+ * axis axes[m] (AAMD_SA_FREQ / AAMD_SA_TIME).  When x is one dense block and x and out are 16-byte aligned the tensor is
+ * streamed with 16-byte accesses and vectors that are wholly masked are not read; any other strides are gathered.
+ * mask_value: one device element of the tensor's type at value_ptr (no host synchronisation; e.g. specgram.mean()), or,
+ * with value_ptr = NULL, the element's bits in value_bits.
+ * _iid:    draws holds the raw uniform draws, [n_masks][2][examples] of the tensor's type; example e's mask m is
+ *          value = draws[m][0][e] * mask_params[m], min_value = draws[m][1][e] * (size - value), start = (long) min_value,
+ *          end = start + (long) value, evaluated in the tensor's type as aten does (size = the length of the mask's axis).
+ * _shared: every example takes [starts[m], ends[m]) (cut to the axis).
+ * More than 32 masks, an unknown axis tag or element type: AAMD_EINVAL (chain launches beyond 32 masks). */
+int aamd_spec_augment_iid(const void* x, void* out, int64_t examples, int64_t n_outer, int64_t n_inner,
+                          int64_t stride_example, int64_t stride_outer, int64_t stride_inner, int32_t dtype,
+                          int32_t time_inner, int32_t n_masks, const int32_t* axes, const int64_t* mask_params,
+                          const void* draws, uint64_t value_bits, const void* value_ptr, void* stream);
+int aamd_spec_augment_shared(const void* x, void* out, int64_t examples, int64_t n_outer, int64_t n_inner,
+                             int64_t stride_example, int64_t stride_outer, int64_t stride_inner, int32_t dtype,
+                             int32_t time_inner, int32_t n_masks, const int32_t* axes, const int64_t* starts,
+                             const int64_t* ends, uint64_t value_bits, const void* value_ptr, void* stream);
 
 #ifdef __cplusplus
 }
