@@ -18,7 +18,8 @@ forward pass too: float64 is the precision path (generic kernels, csrc/f64_paths
 from __future__ import annotations
 
 import ctypes as C
-from typing import Tuple
+import math
+from typing import Optional, Tuple
 
 import numpy as np
 import torch
@@ -312,3 +313,23 @@ def sliding_window_cmvn(x3: Tensor, cmn_window: int, min_cmn_window: int, center
     var = torch.where(single, torch.ones_like(s2), s2 / n - (s1 * s1) / (n * n))
     out = torch.where(single, torch.zeros_like(centred), centred * torch.pow(var, -0.5))
     return out.to(x3.dtype)
+
+
+def add_noise_grads(g: Tensor, waveform: Tensor, noise: Tensor, snr: Tensor, lengths: Optional[Tensor]):
+    """The three gradients of F.add_noise for cotangent g, as a differentiable torch composition (the backward while it is
+    itself being recorded: create_graph).  Same formulas as the gradient mode of csrc/wave_augment.h; results have the
+    broadcast leading shape, the caller sums them to the inputs' shapes."""
+    L = waveform.shape[-1]
+    if lengths is not None:
+        mask = torch.arange(L, device=waveform.device) < lengths.unsqueeze(-1)
+        wm, nm = waveform * mask, noise * mask
+    else:
+        wm, nm = waveform, noise
+    es = (wm * wm).sum(-1)
+    en = (nm * nm).sum(-1)
+    s = 10 ** ((10 * (torch.log10(es) - torch.log10(en)) - snr) / 20.0)
+    d = (g * noise).sum(-1)
+    gw = g + (d * s / es).unsqueeze(-1) * wm
+    gn = s.unsqueeze(-1) * g - (d * s / en).unsqueeze(-1) * nm
+    gs = -(math.log(10.0) / 20.0) * s * d
+    return gw, gn, gs

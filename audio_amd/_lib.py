@@ -147,6 +147,14 @@ _SIGS = {
     # SpecAugment masking (additions to ABI 7)
     "aamd_spec_augment_iid": (C.c_int, [_P, _P] + [C.c_int64] * 6 + [C.c_int32] * 3 + [_P, _P, _P, C.c_uint64, _P, _P]),
     "aamd_spec_augment_shared": (C.c_int, [_P, _P] + [C.c_int64] * 6 + [C.c_int32] * 3 + [_P, _P, _P, C.c_uint64, _P, _P]),
+    # waveform augmentation (additions to ABI 7)
+    "aamd_add_noise_workspace": (C.c_int64, [C.c_int64] * 2),
+    "aamd_add_noise_f32": (C.c_int, [_P] * 6 + [C.c_int64] * 5 + [_P, C.c_int64, _P, C.c_int64, C.c_int32, _P]),
+    "aamd_add_noise_f64": (C.c_int, [_P] * 6 + [C.c_int64] * 5 + [_P, C.c_int64, _P, C.c_int64, C.c_int32, _P]),
+    "aamd_add_noise_lp": (C.c_int, [_P] * 6 + [C.c_int64] * 5 + [_P, C.c_int64, _P, C.c_int64, C.c_int32, C.c_int32, _P]),
+    "aamd_preemphasis_f32": (C.c_int, [_P, _P] + [C.c_int64] * 3 + [C.c_double, C.c_int32, _P]),
+    "aamd_preemphasis_f64": (C.c_int, [_P, _P] + [C.c_int64] * 3 + [C.c_double, C.c_int32, _P]),
+    "aamd_preemphasis_lp": (C.c_int, [_P, _P] + [C.c_int64] * 3 + [C.c_double, C.c_int32, C.c_int32, _P]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS)

@@ -60,6 +60,10 @@ _DEF.define("mask_along_axis(Tensor specgram, int mask_param, float mask_value, 
 _DEF.define("mask_along_axis_iid(Tensor specgrams, int mask_param, float mask_value, int axis, float p) -> Tensor")
 _DEF.define("spec_augment(Tensor specgram, int n_time_masks, int time_mask_param, int n_freq_masks, int freq_mask_param, "
             "bool iid_masks, float p, bool zero_masking) -> Tensor")
+_DEF.define("add_noise(Tensor waveform, Tensor noise, Tensor snr, Tensor? lengths) -> Tensor")
+_DEF.define("preemphasis(Tensor waveform, float coeff) -> Tensor")
+_DEF.define("deemphasis(Tensor waveform, float coeff) -> Tensor")
+_DEF.define("convolve(Tensor x, Tensor y, str mode) -> Tensor")
 _DEF.define("rnnt_features(Tensor waveform, Tensor window, Tensor fb, int n_fft, int hop_length, float gain, Tensor mean, "
             "Tensor invstddev, int right_padding) -> Tensor")
 
@@ -167,6 +171,10 @@ _register("detect_pitch_frequency", F.detect_pitch_frequency)
 _register("mask_along_axis", F._mask_along_axis_eager)
 _register("mask_along_axis_iid", F._mask_along_axis_iid_eager)
 _register("spec_augment", F._spec_augment_eager)
+_register("add_noise", F._add_noise_eager)
+_register("preemphasis", F._preemphasis_eager)
+_register("deemphasis", F._deemphasis_eager)
+_register("convolve", F._convolve_eager)
 
 
 # ---- Meta implementations: shapes / strides only ---------------------------------------------
@@ -317,3 +325,15 @@ def _masking_meta(specgram, *rest):
 _META.impl("mask_along_axis", _masking_meta)
 _META.impl("mask_along_axis_iid", _masking_meta)
 _META.impl("spec_augment", _masking_meta)
+
+
+def _add_noise_meta(waveform, noise, snr, lengths):
+    lead = torch.broadcast_shapes(tuple(waveform.shape[:-1]), tuple(noise.shape[:-1]), tuple(snr.shape),
+                                  tuple(lengths.shape) if lengths is not None else ())
+    return waveform.new_empty(tuple(lead) + (waveform.shape[-1],))
+
+
+_META.impl("add_noise", _add_noise_meta)
+_META.impl("preemphasis", lambda waveform, coeff: torch.empty_like(waveform, memory_format=torch.contiguous_format))
+_META.impl("deemphasis", lambda waveform, coeff: torch.empty_like(waveform, memory_format=torch.contiguous_format))
+_META.impl("convolve", _fftconvolve_meta)

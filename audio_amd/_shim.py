@@ -34,7 +34,9 @@ OPS = ("spectrogram", "mel_spectrogram", "mel_spectrogram_db", "mfcc_dct", "resa
        # the NCCF pitch tracker (F.detect_pitch_frequency, F._compute_nccf; an addition to ABI 7)
        "detect_pitch",
        # SpecAugment masking: a whole policy in one launch (F.mask_along_axis[_iid], T.SpecAugment; an addition to ABI 7)
-       "spec_augment")
+       "spec_augment",
+       # waveform augmentation: the two launches of F.add_noise, forward and gradient, and F.preemphasis (additions to ABI 7)
+       "add_noise", "add_noise_grad", "preemphasis")
 
 _lock = threading.Lock()
 _handle = None
@@ -208,6 +210,18 @@ def _register_fakes() -> None:
     @reg("aamd::spec_augment")
     def _(x, draws, axes, params, starts, ends, time_inner, value_bits, value):
         return x.new_empty(x.shape)
+
+    @reg("aamd::add_noise")
+    def _(waveform, noise, snr, lengths, workspace):
+        return waveform.new_empty(waveform.shape)
+
+    @reg("aamd::add_noise_grad")
+    def _(cotangent, waveform, noise, snr, lengths, workspace):
+        return waveform.new_empty((2,) + tuple(waveform.shape))
+
+    @reg("aamd::preemphasis")
+    def _(waveform, coeff, transposed):
+        return waveform.new_empty(waveform.shape)
 
 
 def available() -> bool:

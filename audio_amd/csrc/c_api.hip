@@ -33,6 +33,7 @@
 #include "resample_mfma.h"
 #include "spec_augment.h"
 #include "stft_generic.h"
+#include "wave_augment.h"
 
 using namespace aamd;
 
@@ -1954,6 +1955,115 @@ int aamd_spec_augment_shared(const void* x, void* out, int64_t examples, int64_t
                              const int64_t* ends, uint64_t value_bits, const void* value_ptr, void* stream) {
   return spec_augment(x, out, examples, n_outer, n_inner, stride_example, stride_outer, stride_inner, dtype, time_inner,
                       n_masks, axes, nullptr, nullptr, starts, ends, value_bits, value_ptr, stream);
+}
+
+// ---- waveform augmentation: add_noise and preemphasis (csrc/wave_augment.h) ----------------------------------------------
+int64_t aamd_add_noise_workspace(int64_t rows, int64_t length) {
+  if (rows < 0 || length < 0) return 0;
+  return (rows + rows * wa::n_chunks(length) * 3) * (int64_t)sizeof(double);
+}
+
+extern "C++" template <int DT>
+static int add_noise_launch(const wa::NoiseArgs& a, int64_t blocks, hipStream_t s) {
+  hipLaunchKernelGGL(wa::add_noise_reduce_kernel<DT>, dim3((unsigned)blocks), dim3(wa::kThreads), 0, s, a);
+  int rc = launch_check();
+  if (rc != AAMD_OK) return rc;
+  hipLaunchKernelGGL(wa::add_noise_apply_kernel<DT>, dim3((unsigned)blocks), dim3(wa::kThreads), 0, s, a);
+  return launch_check();
+}
+
+static int add_noise(int32_t dtype, const void* w, const void* n, const void* g, void* out, void* out2, void* workspace,
+                     int64_t rows, int64_t length, int64_t sw, int64_t sn, int64_t sg, const double* snr, int64_t ssnr,
+                     const int64_t* lengths, int64_t slen, int32_t mode, void* stream) {
+  DeviceScope dev_scope_(w);
+  AAMD_CHECK_ARG(rows >= 0 && length >= 0, "bad sizes");
+  AAMD_CHECK_ARG(mode == AAMD_ADD_NOISE_FORWARD || mode == AAMD_ADD_NOISE_GRADIENT, "add_noise: unknown mode");
+  AAMD_CHECK_ARG(sw >= 0 && sn >= 0 && sg >= 0 && ssnr >= 0 && slen >= 0, "add_noise: negative stride");
+  if (rows * length == 0) return AAMD_OK;
+  AAMD_CHECK_ARG(w && n && out && snr && workspace, "null buffer");
+  AAMD_CHECK_ARG(mode == AAMD_ADD_NOISE_FORWARD || (g && out2), "add_noise: the gradient needs a cotangent and two outputs");
+  AAMD_CHECK_ARG(((uintptr_t)workspace & 7) == 0, "workspace must be 8-byte aligned");
+  wa::NoiseArgs a{};
+  a.w = w; a.n = n; a.g = g; a.out = out; a.out2 = out2;
+  a.ws = static_cast<double*>(workspace);
+  a.snr = snr; a.lengths = lengths;
+  a.rows = rows; a.L = length; a.sw = sw; a.sn = sn; a.sg = sg; a.ssnr = ssnr; a.slen = slen;
+  a.chunks = wa::n_chunks(length);
+  a.grad = mode == AAMD_ADD_NOISE_GRADIENT;
+  const int64_t blocks = rows * a.chunks;
+  AAMD_CHECK_ARG(blocks < (1ll << 31), "too many chunks for one launch");
+  hipStream_t s = (hipStream_t)stream;
+  switch (dtype) {
+    case AAMD_SA_F32: return add_noise_launch<wa::kF32>(a, blocks, s);
+    case AAMD_SA_F64: return add_noise_launch<wa::kF64>(a, blocks, s);
+    case AAMD_SA_F16: return add_noise_launch<wa::kF16>(a, blocks, s);
+    case AAMD_SA_BF16: return add_noise_launch<wa::kBF16>(a, blocks, s);
+    default: return fail(AAMD_EINVAL, "audio_amd: add_noise: unknown element type");
+  }
+}
+
+int aamd_add_noise_f32(const float* waveform, const float* noise, const float* cotangent, float* out, float* out2,
+                       void* workspace, int64_t rows, int64_t length, int64_t stride_waveform, int64_t stride_noise,
+                       int64_t stride_cotangent, const double* snr, int64_t stride_snr, const int64_t* lengths,
+                       int64_t stride_lengths, int32_t mode, void* stream) {
+  return add_noise(AAMD_SA_F32, waveform, noise, cotangent, out, out2, workspace, rows, length, stride_waveform, stride_noise,
+                   stride_cotangent, snr, stride_snr, lengths, stride_lengths, mode, stream);
+}
+
+int aamd_add_noise_f64(const double* waveform, const double* noise, const double* cotangent, double* out, double* out2,
+                       void* workspace, int64_t rows, int64_t length, int64_t stride_waveform, int64_t stride_noise,
+                       int64_t stride_cotangent, const double* snr, int64_t stride_snr, const int64_t* lengths,
+                       int64_t stride_lengths, int32_t mode, void* stream) {
+  return add_noise(AAMD_SA_F64, waveform, noise, cotangent, out, out2, workspace, rows, length, stride_waveform, stride_noise,
+                   stride_cotangent, snr, stride_snr, lengths, stride_lengths, mode, stream);
+}
+
+int aamd_add_noise_lp(const void* waveform, const void* noise, const void* cotangent, void* out, void* out2, void* workspace,
+                      int64_t rows, int64_t length, int64_t stride_waveform, int64_t stride_noise, int64_t stride_cotangent,
+                      const double* snr, int64_t stride_snr, const int64_t* lengths, int64_t stride_lengths, int32_t dtype,
+                      int32_t mode, void* stream) {
+  AAMD_CHECK_ARG(dtype == AAMD_SA_F16 || dtype == AAMD_SA_BF16, "add_noise: the low-precision entry takes AAMD_SA_F16 or AAMD_SA_BF16");
+  return add_noise(dtype, waveform, noise, cotangent, out, out2, workspace, rows, length, stride_waveform, stride_noise,
+                   stride_cotangent, snr, stride_snr, lengths, stride_lengths, mode, stream);
+}
+
+static int preemphasis(int32_t dtype, const void* x, void* out, int64_t rows, int64_t length, int64_t stride_row, double coeff,
+                       int32_t transposed, void* stream) {
+  DeviceScope dev_scope_(x);
+  AAMD_CHECK_ARG(rows >= 0 && length >= 0 && stride_row >= 0, "bad sizes");
+  if (rows * length == 0) return AAMD_OK;
+  AAMD_CHECK_ARG(x && out, "null buffer");
+  wa::PreArgs a{};
+  a.x = x; a.out = out; a.rows = rows; a.L = length; a.sx = stride_row; a.chunks = wa::n_chunks(length);
+  a.coeff = coeff; a.transposed = transposed ? 1 : 0;
+  const int64_t blocks = rows * a.chunks;
+  AAMD_CHECK_ARG(blocks < (1ll << 31), "too many chunks for one launch");
+  hipStream_t s = (hipStream_t)stream;
+  const dim3 grid((unsigned)blocks), block(wa::kThreads);
+  switch (dtype) {
+    case AAMD_SA_F32: hipLaunchKernelGGL(wa::preemphasis_kernel<wa::kF32>, grid, block, 0, s, a); break;
+    case AAMD_SA_F64: hipLaunchKernelGGL(wa::preemphasis_kernel<wa::kF64>, grid, block, 0, s, a); break;
+    case AAMD_SA_F16: hipLaunchKernelGGL(wa::preemphasis_kernel<wa::kF16>, grid, block, 0, s, a); break;
+    case AAMD_SA_BF16: hipLaunchKernelGGL(wa::preemphasis_kernel<wa::kBF16>, grid, block, 0, s, a); break;
+    default: return fail(AAMD_EINVAL, "audio_amd: preemphasis: unknown element type");
+  }
+  return launch_check();
+}
+
+int aamd_preemphasis_f32(const float* x, float* out, int64_t rows, int64_t length, int64_t stride_row, double coeff,
+                         int32_t transposed, void* stream) {
+  return preemphasis(AAMD_SA_F32, x, out, rows, length, stride_row, coeff, transposed, stream);
+}
+
+int aamd_preemphasis_f64(const double* x, double* out, int64_t rows, int64_t length, int64_t stride_row, double coeff,
+                         int32_t transposed, void* stream) {
+  return preemphasis(AAMD_SA_F64, x, out, rows, length, stride_row, coeff, transposed, stream);
+}
+
+int aamd_preemphasis_lp(const void* x, void* out, int64_t rows, int64_t length, int64_t stride_row, double coeff, int32_t dtype,
+                        int32_t transposed, void* stream) {
+  AAMD_CHECK_ARG(dtype == AAMD_SA_F16 || dtype == AAMD_SA_BF16, "preemphasis: the low-precision entry takes AAMD_SA_F16 or AAMD_SA_BF16");
+  return preemphasis(dtype, x, out, rows, length, stride_row, coeff, transposed, stream);
 }
 
 }  // extern "C"

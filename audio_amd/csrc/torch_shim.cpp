@@ -840,6 +840,103 @@ Tensor spec_augment(Tensor x, std::optional<Tensor> draws, std::vector<int64_t> 
   return out;
 }
 
+// ---- aamd::add_noise / add_noise_grad / preemphasis (F.add_noise, F.preemphasis; csrc/wave_augment.h) ---------------------
+// Operands are (rows, L) with unit stride along time and any row stride (0: one row for every output row); snr is float64
+// (rows) and lengths int64 (rows), any stride, both read on the device.  workspace: float64, aamd_add_noise_workspace() bytes.
+int32_t wave_dtype(const Tensor& x, const char* what) {
+  STD_TORCH_CHECK(x.is_cuda(), "audio_amd: ", what, " must be on an MI355X (ROCm) device; there is no CPU kernel");
+  switch (x.scalar_type()) {
+    case ScalarType::Float: return AAMD_SA_F32;
+    case ScalarType::Double: return AAMD_SA_F64;
+    case ScalarType::Half: return AAMD_SA_F16;
+    case ScalarType::BFloat16: return AAMD_SA_BF16;
+    default: break;
+  }
+  STD_TORCH_CHECK(false, "audio_amd: ", what, " must be float16, bfloat16, float32 or float64");
+  return -1;
+}
+void want_rows(const Tensor& t, const char* what, const Tensor& ref) {
+  STD_TORCH_CHECK(t.is_cuda() && t.dim() == 2 && t.scalar_type() == ref.scalar_type() && t.size(0) == ref.size(0) &&
+                  t.size(1) == ref.size(1), "audio_amd: ", what, " must be a (rows, time) device tensor of the waveform's shape and dtype");
+  STD_TORCH_CHECK(t.size(1) <= 1 || t.stride(1) == 1, "audio_amd: ", what, " rows must have unit stride");
+  STD_TORCH_CHECK(t.stride(0) >= 0, "audio_amd: ", what, " has a negative row stride");
+  same_device(ref, t);
+}
+int64_t row_stride(const Tensor& t) { return t.size(0) > 1 ? t.stride(0) : 0; }
+
+Tensor add_noise_any(const Tensor* g, const Tensor& w, const Tensor& n, const Tensor& snr, const std::optional<Tensor>& lengths,
+                     Tensor& workspace) {
+  const int32_t dtype = wave_dtype(w, "waveform");
+  STD_TORCH_CHECK(w.dim() == 2, "audio_amd: waveform must be (rows, time)");
+  want_rows(w, "waveform", w);
+  want_rows(n, "noise", w);
+  if (g) want_rows(*g, "the cotangent", w);
+  const int64_t rows = w.size(0), L = w.size(1);
+  STD_TORCH_CHECK(snr.is_cuda() && snr.scalar_type() == ScalarType::Double && snr.dim() == 1 && snr.size(0) == rows,
+                  "audio_amd: snr must be a float64 device tensor with one element per row");
+  same_device(w, snr);
+  const int64_t* lp = nullptr;
+  int64_t slen = 0;
+  if (lengths.has_value()) {
+    STD_TORCH_CHECK(lengths->is_cuda() && lengths->scalar_type() == ScalarType::Long && lengths->dim() == 1 &&
+                    lengths->size(0) == rows, "audio_amd: lengths must be an int64 device tensor with one element per row");
+    same_device(w, *lengths);
+    lp = rows ? static_cast<const int64_t*>(lengths->data_ptr()) : nullptr;
+    slen = row_stride(*lengths);
+  }
+  STD_TORCH_CHECK(workspace.is_cuda() && workspace.scalar_type() == ScalarType::Double && workspace.is_contiguous() &&
+                  workspace.numel() * 8 >= aamd_add_noise_workspace(rows, L), "audio_amd: workspace too small");
+  same_device(w, workspace);
+  const torch::stable::accelerator::DeviceGuard guard(w.get_device_index());
+  Tensor out = g ? torch::stable::new_empty(w, {2, rows, L}) : torch::stable::new_empty(w, {rows, L});
+  if (rows * L == 0) return out;
+  const int32_t mode = g ? AAMD_ADD_NOISE_GRADIENT : AAMD_ADD_NOISE_FORWARD;
+  const void* gp = g ? g->data_ptr() : nullptr;
+  const int64_t sg = g ? row_stride(*g) : 0;
+  char* op = static_cast<char*>(out.data_ptr());
+  const int64_t es = dtype == AAMD_SA_F64 ? 8 : (dtype == AAMD_SA_F32 ? 4 : 2);
+  void* o2 = g ? op + rows * L * es : nullptr;
+  const double* sp = static_cast<const double*>(snr.data_ptr());
+  if (dtype == AAMD_SA_F32)
+    check(aamd_add_noise_f32(static_cast<const float*>(w.data_ptr()), static_cast<const float*>(n.data_ptr()),
+                             static_cast<const float*>(gp), reinterpret_cast<float*>(op), static_cast<float*>(o2),
+                             workspace.data_ptr(), rows, L, row_stride(w), row_stride(n), sg, sp, row_stride(snr), lp, slen, mode,
+                             current_stream(w)));
+  else if (dtype == AAMD_SA_F64)
+    check(aamd_add_noise_f64(static_cast<const double*>(w.data_ptr()), static_cast<const double*>(n.data_ptr()),
+                             static_cast<const double*>(gp), reinterpret_cast<double*>(op), static_cast<double*>(o2),
+                             workspace.data_ptr(), rows, L, row_stride(w), row_stride(n), sg, sp, row_stride(snr), lp, slen, mode,
+                             current_stream(w)));
+  else
+    check(aamd_add_noise_lp(w.data_ptr(), n.data_ptr(), gp, op, o2, workspace.data_ptr(), rows, L, row_stride(w), row_stride(n), sg,
+                            sp, row_stride(snr), lp, slen, dtype, mode, current_stream(w)));
+  return out;
+}
+Tensor add_noise(Tensor w, Tensor n, Tensor snr, std::optional<Tensor> lengths, Tensor workspace) {
+  return add_noise_any(nullptr, w, n, snr, lengths, workspace);
+}
+// (2, rows, L): grad_w, grad_n; the gradient to snr is left in the first `rows` elements of workspace
+Tensor add_noise_grad(Tensor g, Tensor w, Tensor n, Tensor snr, std::optional<Tensor> lengths, Tensor workspace) {
+  return add_noise_any(&g, w, n, snr, lengths, workspace);
+}
+Tensor preemphasis(Tensor x, double coeff, bool transposed) {
+  const int32_t dtype = wave_dtype(x, "waveform");
+  STD_TORCH_CHECK(x.dim() == 2, "audio_amd: waveform must be (rows, time)");
+  want_rows(x, "waveform", x);
+  const torch::stable::accelerator::DeviceGuard guard(x.get_device_index());
+  Tensor out = torch::stable::new_empty(x, {x.size(0), x.size(1)});
+  if (x.numel() == 0) return out;
+  if (dtype == AAMD_SA_F32)
+    check(aamd_preemphasis_f32(fp(x), fpm(out), x.size(0), x.size(1), row_stride(x), coeff, transposed ? 1 : 0, current_stream(x)));
+  else if (dtype == AAMD_SA_F64)
+    check(aamd_preemphasis_f64(static_cast<const double*>(x.data_ptr()), dpm(out), x.size(0), x.size(1), row_stride(x), coeff,
+                               transposed ? 1 : 0, current_stream(x)));
+  else
+    check(aamd_preemphasis_lp(x.data_ptr(), out.data_ptr(), x.size(0), x.size(1), row_stride(x), coeff, dtype, transposed ? 1 : 0,
+                              current_stream(x)));
+  return out;
+}
+
 // ---- torchaudio::_lfilter_core_loop on the CUDA key (lfilter.cpp:118-134, iir_cuda.cu:37-79) ------------------------
 //   padded_out[n][c][i + n_order - 1] = in[n][c][i] - sum_{j < n_order-1} a_flipped[c][j] * padded_out[n][c][i + j]
 // = the pure recursion y = IIR(in; a) with a = flip(a_flipped), b = (1, 0, ...), no clamp: aamd_lfilter_f32 runs it as a
@@ -941,6 +1038,9 @@ STABLE_TORCH_LIBRARY(aamd, m) {
   m.def("detect_pitch(Tensor x, int sample_rate, int frame_size, int lags, int lag_min, int win_length, int mode) -> Tensor");
   m.def("spec_augment(Tensor x, Tensor? draws, int[] axes, int[] params, int[] starts, int[] ends, bool time_inner, "
         "int value_bits, Tensor? value) -> Tensor");
+  m.def("add_noise(Tensor waveform, Tensor noise, Tensor snr, Tensor? lengths, Tensor workspace) -> Tensor");
+  m.def("add_noise_grad(Tensor cotangent, Tensor waveform, Tensor noise, Tensor snr, Tensor? lengths, Tensor workspace) -> Tensor");
+  m.def("preemphasis(Tensor waveform, float coeff, bool transposed) -> Tensor");
 }
 
 STABLE_TORCH_LIBRARY_IMPL(aamd, CUDA, m) {
@@ -976,6 +1076,9 @@ STABLE_TORCH_LIBRARY_IMPL(aamd, CUDA, m) {
   m.impl("sliding_window_cmn", TORCH_BOX(&sliding_window_cmn));
   m.impl("detect_pitch", TORCH_BOX(&detect_pitch));
   m.impl("spec_augment", TORCH_BOX(&spec_augment));
+  m.impl("add_noise", TORCH_BOX(&add_noise));
+  m.impl("add_noise_grad", TORCH_BOX(&add_noise_grad));
+  m.impl("preemphasis", TORCH_BOX(&preemphasis));
 }
 
 // The reference's op.  libtorchaudio (when present) has already run

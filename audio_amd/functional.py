@@ -32,6 +32,7 @@ __all__ = [
     "lowpass_biquad", "highpass_biquad", "allpass_biquad", "bandpass_biquad",
     "bandreject_biquad", "equalizer_biquad", "band_biquad", "treble_biquad", "bass_biquad", "deemph_biquad", "riaa_biquad",
     "compute_deltas", "sliding_window_cmn", "detect_pitch_frequency", "mask_along_axis", "mask_along_axis_iid",
+    "add_noise", "preemphasis", "deemphasis", "convolve",
 ]
 
 # --------------------------------------------------------------------------- #
@@ -2658,6 +2659,246 @@ def _spec_augment_eager(specgram: Tensor, n_time_masks: int, time_mask_param: in
 
 
 # --------------------------------------------------------------------------- #
+# waveform augmentation (csrc/wave_augment.h)                                 #
+# --------------------------------------------------------------------------- #
+
+WAVE_AUGMENT_CHUNK = 4096       # samples per workgroup of the add_noise / preemphasis kernels (wa::kChunk)
+_WA_FLOATS = (torch.float32, torch.float64, torch.float16, torch.bfloat16)
+
+
+def _wa_require(t: Tensor, what: str, floating: bool = True) -> None:
+    if floating and t.dtype not in _WA_FLOATS:
+        raise TypeError(f"audio_amd: {what} must be float16, bfloat16, float32 or float64 (got {t.dtype})")
+    if not floating and (t.is_complex() or t.dtype == torch.bool):
+        raise TypeError(f"audio_amd: {what} must be an integer or floating-point tensor (got {t.dtype})")
+    if not t.is_cuda:
+        raise RuntimeError(f"audio_amd: {what} must be on an MI355X (ROCm) device, got {t.device}. "
+                           "The HIP kernels have no CPU fallback.")
+
+
+def _wa_rows(t: Tensor, lead, L: int) -> Tensor:
+    """`t` broadcast to lead + (L,), as (rows, L) with unit stride along time and ONE row stride -- 0 for a broadcast row,
+    more than L for rows of a wider tensor -- without a copy wherever the strides collapse that way."""
+    e = t.expand(tuple(lead) + (L,))
+    if L > 1 and e.stride(-1) != 1:
+        e = e.contiguous()
+    rows = 1
+    for d in lead:
+        rows *= d
+    if e.dim() != 2:
+        try:
+            e = e.view(rows, L)
+        except RuntimeError:
+            e = e.contiguous().view(rows, L)
+    if rows > 1 and e.stride(0) < 0:
+        e = e.contiguous()
+    return e
+
+
+def _wa_stride(t: Tensor) -> int:
+    return t.stride(0) if t.shape[0] > 1 else 0
+
+
+def _add_noise_launch(w2: Tensor, n2: Tensor, snr1: Tensor, len1: Optional[Tensor], g2: Optional[Tensor] = None):
+    """The two launches over (rows, L) operands.  Forward: (out, workspace); with a cotangent g2: ((2, rows, L) = grad_w and
+    grad_n, workspace whose first `rows` elements hold the gradient to snr).  The workspace comes from torch's allocator,
+    so the call can be captured in a graph."""
+    rows, L = w2.shape
+    lib = _lib.lib()
+    ws = torch.empty((max(int(lib.aamd_add_noise_workspace(rows, L)) // 8, 1),), dtype=torch.float64, device=w2.device)
+    ops = _ops()
+    if ops is not None:
+        if g2 is None:
+            return ops.add_noise(w2, n2, snr1, len1, ws), ws
+        return ops.add_noise_grad(g2, w2, n2, snr1, len1, ws), ws
+    out = torch.empty((rows, L) if g2 is None else (2, rows, L), dtype=w2.dtype, device=w2.device)
+    if rows * L == 0:
+        return out, ws
+    args = (_lib.ptr(w2), _lib.ptr(n2), _lib.ptr(g2) if g2 is not None else None, out.data_ptr(),
+            out[1].data_ptr() if g2 is not None else None, ws.data_ptr(), rows, L, _wa_stride(w2), _wa_stride(n2),
+            _wa_stride(g2) if g2 is not None else 0, snr1.data_ptr(), _wa_stride(snr1),
+            len1.data_ptr() if len1 is not None else None, _wa_stride(len1) if len1 is not None else 0)
+    mode = 0 if g2 is None else 1
+    with torch.cuda.device(w2.device):
+        if w2.dtype == torch.float32:
+            _lib.check(lib.aamd_add_noise_f32(*args, mode, _lib.current_stream(w2.device)))
+        elif w2.dtype == torch.float64:
+            _lib.check(lib.aamd_add_noise_f64(*args, mode, _lib.current_stream(w2.device)))
+        else:
+            _lib.check(lib.aamd_add_noise_lp(*args, _SA_DTYPES[w2.dtype], mode, _lib.current_stream(w2.device)))
+    return out, ws
+
+
+def _add_noise_operands(waveform: Tensor, noise: Tensor, snr: Tensor, lengths: Optional[Tensor]):
+    """Leading shape and the kernel's operands: (rows, L) views of waveform and noise, snr as float64 (rows,), lengths as
+    int64 (rows,) -- floating lengths by a device-side ceil, which keeps `i < length`.  Nothing here waits for the device."""
+    L = waveform.size(-1)
+    lead = torch.broadcast_shapes(tuple(waveform.shape[:-1]), tuple(noise.shape[:-1]), tuple(snr.shape),
+                                  tuple(lengths.shape) if lengths is not None else ())
+    snr1 = snr.detach().to(torch.float64).expand(lead).reshape(-1)
+    len1 = None
+    if lengths is not None:
+        ln = lengths.detach()
+        ln = torch.ceil(ln).to(torch.int64) if ln.is_floating_point() else ln.to(torch.int64)
+        len1 = ln.expand(lead).reshape(-1)
+    return lead, L, _wa_rows(waveform.detach(), lead, L), _wa_rows(noise.detach(), lead, L), snr1, len1
+
+
+def _add_noise_forward(waveform: Tensor, noise: Tensor, snr: Tensor, lengths: Optional[Tensor]) -> Tensor:
+    lead, L, w2, n2, snr1, len1 = _add_noise_operands(waveform, noise, snr, lengths)
+    out, _ = _add_noise_launch(w2, n2, snr1, len1)
+    return out.view(tuple(lead) + (L,))
+
+
+class _AddNoiseFunction(torch.autograd.Function):
+    """out = w + s(w, n, snr) n.  First order: the gradient mode of the same two launches.  While the backward itself is
+    recorded (create_graph) the gradients come from the differentiable composition `_diff.add_noise_grads` instead."""
+
+    @staticmethod
+    def forward(ctx, waveform, noise, snr, lengths):
+        ctx.save_for_backward(waveform, noise, snr, lengths)
+        return _add_noise_forward(waveform, noise, snr, lengths)
+
+    @staticmethod
+    def backward(ctx, g):
+        waveform, noise, snr, lengths = ctx.saved_tensors
+        if torch.is_grad_enabled():
+            gw, gn, gs = _diff.add_noise_grads(g, waveform, noise, snr, lengths)
+        else:
+            lead, L, w2, n2, snr1, len1 = _add_noise_operands(waveform, noise, snr, lengths)
+            both, ws = _add_noise_launch(w2, n2, snr1, len1, _wa_rows(g, lead, L))
+            gw, gn = both[0].view(tuple(lead) + (L,)), both[1].view(tuple(lead) + (L,))
+            gs = ws[:w2.shape[0]].view(tuple(lead))
+        need = ctx.needs_input_grad
+        return (gw.sum_to_size(waveform.shape) if need[0] else None, gn.sum_to_size(noise.shape) if need[1] else None,
+                gs.sum_to_size(snr.shape).to(snr.dtype) if need[2] else None, None)
+
+
+def _add_noise_eager(waveform: Tensor, noise: Tensor, snr: Tensor, lengths: Optional[Tensor] = None) -> Tensor:
+    r"""Scale ``noise`` to the requested signal-to-noise ratio (dB) and add it to ``waveform`` (reference: F.add_noise).
+    The energies are float64 sums over the samples below ``lengths``; the scale is formed in float64 from the reference's
+    formula and rounded once; the whole row is mixed.  Leading dimensions broadcast.  Rows of zero energy give what IEEE
+    arithmetic gives the formula: scale 0 (silent signal), ``inf`` (silent noise) or NaN (both).  float16 and bfloat16
+    are read and written by the kernel and computed in float32.  Two launches, no temporaries, bit-reproducible."""
+    if not (waveform.ndim - 1 == noise.ndim - 1 == snr.ndim and (lengths is None or lengths.ndim == snr.ndim)):
+        raise ValueError("Input leading dimensions don't match.")
+    L = waveform.size(-1)
+    if L != noise.size(-1):
+        raise ValueError(f"Length dimensions of waveform and noise don't match (got {L} and {noise.size(-1)}).")
+    for t, what in ((waveform, "waveform"), (noise, "noise"), (snr, "snr")):
+        if t.dtype not in _WA_FLOATS:
+            raise TypeError(f"audio_amd: {what} must be float16, bfloat16, float32 or float64 (got {t.dtype})")
+    if waveform.dtype != noise.dtype:
+        raise TypeError(f"audio_amd: add_noise operands must share a dtype (got {waveform.dtype} and {noise.dtype})")
+    _wa_require(waveform, "waveform")
+    _wa_require(noise, "noise")
+    _wa_require(snr, "snr")
+    if lengths is not None:
+        _wa_require(lengths, "lengths", floating=False)
+    if torch.is_grad_enabled() and (waveform.requires_grad or noise.requires_grad or snr.requires_grad):
+        return _AddNoiseFunction.apply(waveform, noise, snr, lengths)
+    return _add_noise_forward(waveform, noise, snr, lengths)
+
+
+def _preemphasis_launch(x2: Tensor, coeff: float, transposed: bool) -> Tensor:
+    """(rows, L) of any row stride -> dense (rows, L): y[i] = x[i] - c x[i - 1] (transposed: x[i] - c x[i + 1]), one launch."""
+    ops = _ops()
+    if ops is not None:
+        return ops.preemphasis(x2, coeff, transposed)
+    out = torch.empty(x2.shape, dtype=x2.dtype, device=x2.device)
+    if out.numel() == 0:
+        return out
+    lib = _lib.lib()
+    head = (_lib.ptr(x2), out.data_ptr(), x2.shape[0], x2.shape[1], _wa_stride(x2), float(coeff))
+    with torch.cuda.device(x2.device):
+        if x2.dtype == torch.float32:
+            _lib.check(lib.aamd_preemphasis_f32(*head, int(transposed), _lib.current_stream(x2.device)))
+        elif x2.dtype == torch.float64:
+            _lib.check(lib.aamd_preemphasis_f64(*head, int(transposed), _lib.current_stream(x2.device)))
+        else:
+            _lib.check(lib.aamd_preemphasis_lp(*head, _SA_DTYPES[x2.dtype], int(transposed), _lib.current_stream(x2.device)))
+    return out
+
+
+class _PreemphasisFunction(torch.autograd.Function):
+    """The pre-emphasis stencil P (transposed=False) or P^T.  Linear: the backward is the other one, applied through this
+    Function again, so gradients of every order run on the kernel."""
+
+    @staticmethod
+    def forward(ctx, x2, coeff, transposed):
+        ctx.args = (coeff, transposed)
+        return _preemphasis_launch(x2, coeff, transposed)
+
+    @staticmethod
+    def backward(ctx, g):
+        coeff, transposed = ctx.args
+        g2 = _wa_rows(g, g.shape[:-1], g.shape[-1])
+        if torch.is_grad_enabled():
+            return _PreemphasisFunction.apply(g2, coeff, not transposed), None, None
+        return _preemphasis_launch(g2, coeff, not transposed), None, None
+
+
+def _preemphasis_eager(waveform: Tensor, coeff: float = 0.97) -> Tensor:
+    r"""``y[i] = x[i] - coeff * x[i - 1]`` along the last dim, ``y[0] = x[0]`` (reference: F.preemphasis).  ``coeff`` is
+    rounded to the compute type and the product and the difference are rounded separately, so float32 and float64 results
+    equal the reference's expression bit for bit; float16 and bfloat16 compute in float32 and round once.  Rows are read in
+    place through their stride; the result is a new contiguous tensor."""
+    _wa_require(waveform, "waveform")
+    if waveform.dim() < 1:
+        raise ValueError("audio_amd: preemphasis expects (..., time), got a 0-dimensional tensor")
+    shape = waveform.shape
+    x2 = _wa_rows(waveform, shape[:-1], shape[-1])
+    if torch.is_grad_enabled() and waveform.requires_grad:
+        out = _PreemphasisFunction.apply(x2, float(coeff), False)
+    else:
+        out = _preemphasis_launch(x2, float(coeff), False)
+    return out.view(shape)
+
+
+def _deemphasis_eager(waveform: Tensor, coeff: float = 0.97) -> Tensor:
+    r"""The inverse of pre-emphasis, ``y[i] = x[i] + coeff * y[i - 1]`` (reference: F.deemphasis): ``lfilter`` with
+    ``a = [1, -coeff]``, ``b = [1, 0]`` and its default clamp to [-1, 1]; gradients are lfilter's."""
+    _wa_require(waveform, "waveform")
+    dtype = waveform.dtype
+    coef = torch.stack([_cpu_scalar(v, dtype) for v in (1.0, -coeff, 1.0, 0.0)]).to(waveform.device)
+    return lfilter(waveform, coef[:2], coef[2:])
+
+
+@_reduced_precision_io
+def _convolve_eager(x: Tensor, y: Tensor, mode: str = "full") -> Tensor:
+    r"""Linear convolution along the last dim with broadcast leading dims and the reference's full / valid / same crops
+    (reference: F.convolve, a grouped conv1d).  The longer operand is taken as the signal, as the reference swaps them.
+    The product is evaluated by the package's convolution plans: up to 192 taps as a direct sum in the time domain, longer
+    kernels through the block FFT kernels, so those agree with the direct sum to rounding, not bit for bit.
+    Differentiable in both operands."""
+    _check_shape_compatible(x, y)
+    _check_convolve_mode(mode)
+    if not x.is_floating_point():
+        x = x.float()
+    if not y.is_floating_point():
+        y = y.float()
+    _require_device(x, "x", allow_grad=True, allow_f64=True)
+    _require_device(y, "y", allow_grad=True, allow_f64=True)
+    if x.dtype != y.dtype:
+        raise TypeError(f"audio_amd: convolve operands must share a dtype (got {x.dtype} and {y.dtype})")
+    x_size, y_size = x.size(-1), y.size(-1)
+    if x_size < y_size:
+        x, y = y, x
+    n_full = x_size + y_size - 1
+    if mode == "full":
+        start, out_len = 0, n_full
+    elif mode == "valid":
+        out_len = max(x_size, y_size) - min(x_size, y_size) + 1
+        start = (n_full - out_len) // 2
+    else:
+        out_len = x_size
+        start = (n_full - x_size) // 2
+    if torch.is_grad_enabled() and (x.requires_grad or y.requires_grad):
+        return _FFTConvolveFunction.apply(x, y, start, out_len)
+    return _conv_slice(x, y, start, out_len)
+
+
+# --------------------------------------------------------------------------- #
 # the public entry points                                                     #
 # --------------------------------------------------------------------------- #
 # Every public function is a small TorchScript-able front (the reference guarantees `torch.jit.script` on this surface:
@@ -3000,3 +3241,36 @@ def mask_along_axis(specgram: Tensor, mask_param: int, mask_value: float, axis: 
         if _get_mask_param(mask_param, p, specgram.size(axis)) < 1:
             return specgram
     return torch.ops.audio_amd.mask_along_axis(specgram, mask_param, mask_value, axis, p)
+
+
+def add_noise(waveform: Tensor, noise: Tensor, snr: Tensor, lengths: Optional[Tensor] = None) -> Tensor:
+    r"""Scale ``noise`` to the signal-to-noise ratio ``snr`` (dB) per row and add it to ``waveform`` (reference:
+    F.add_noise); see ``_add_noise_eager``."""
+    if not torch.jit.is_scripting():
+        if not torch.compiler.is_compiling():
+            return _add_noise_eager(waveform, noise, snr, lengths)
+    return torch.ops.audio_amd.add_noise(waveform, noise, snr, lengths)
+
+
+def preemphasis(waveform: Tensor, coeff: float = 0.97) -> Tensor:
+    r"""Pre-emphasis along the last dim (reference: F.preemphasis); see ``_preemphasis_eager``."""
+    if not torch.jit.is_scripting():
+        if not torch.compiler.is_compiling():
+            return _preemphasis_eager(waveform, coeff)
+    return torch.ops.audio_amd.preemphasis(waveform, coeff)
+
+
+def deemphasis(waveform: Tensor, coeff: float = 0.97) -> Tensor:
+    r"""De-emphasis along the last dim (reference: F.deemphasis); see ``_deemphasis_eager``."""
+    if not torch.jit.is_scripting():
+        if not torch.compiler.is_compiling():
+            return _deemphasis_eager(waveform, coeff)
+    return torch.ops.audio_amd.deemphasis(waveform, coeff)
+
+
+def convolve(x: Tensor, y: Tensor, mode: str = "full") -> Tensor:
+    r"""Linear convolution along the last dim (reference: F.convolve); see ``_convolve_eager``."""
+    if not torch.jit.is_scripting():
+        if not torch.compiler.is_compiling():
+            return _convolve_eager(x, y, mode)
+    return torch.ops.audio_amd.convolve(x, y, mode)

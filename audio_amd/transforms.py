@@ -1,6 +1,6 @@
 """Drop-in replacements for the hot-path modules of ``torchaudio.transforms``:
 Spectrogram, MelScale, MelSpectrogram, AmplitudeToDB, MFCC, Resample, FFTConvolve, ComputeDeltas, SlidingWindowCmn,
-FrequencyMasking, TimeMasking, SpecAugment.
+FrequencyMasking, TimeMasking, SpecAugment, AddNoise, Preemphasis, Deemphasis, Convolve.
 
 Constructor / forward signatures, registered buffer names (``window``, ``fb``, ``dct_mat``,
 ``kernel``), shapes, strides, warnings and error messages follow
@@ -33,7 +33,8 @@ _norm_mode = F._norm_mode      # `normalized` as the op schemas' integer: 0 none
 
 __all__ = ["Spectrogram", "InverseSpectrogram", "GriffinLim", "TimeStretch", "PitchShift", "Speed", "SpeedPerturbation",
            "MelScale", "MelSpectrogram", "AmplitudeToDB", "MFCC", "Resample", "FFTConvolve", "ComputeDeltas",
-           "SlidingWindowCmn", "FrequencyMasking", "TimeMasking", "SpecAugment"]
+           "SlidingWindowCmn", "FrequencyMasking", "TimeMasking", "SpecAugment", "AddNoise", "Preemphasis", "Deemphasis",
+           "Convolve"]
 
 
 class Spectrogram(torch.nn.Module):
@@ -675,3 +676,45 @@ class FFTConvolve(torch.nn.Module):
             if torch.compiler.is_compiling():
                 return torch.ops.audio_amd.fftconvolve(x, y, self.mode)
         return F.fftconvolve(x, y, mode=self.mode)
+
+
+class Convolve(torch.nn.Module):
+    r"""Convolution along the last dim, evaluated directly in the reference (reference: T.Convolve); here short kernels are a
+    direct sum and long ones go through the FFT plans (``F.convolve``)."""
+
+    def __init__(self, mode: str = "full") -> None:
+        super().__init__()
+        F._check_convolve_mode(mode)
+        self.mode = mode
+
+    def forward(self, x: Tensor, y: Tensor) -> Tensor:
+        return F.convolve(x, y, mode=self.mode)
+
+
+class AddNoise(torch.nn.Module):
+    r"""Scale noise to a signal-to-noise ratio per row and add it (reference: T.AddNoise); no buffers."""
+
+    def forward(self, waveform: Tensor, noise: Tensor, snr: Tensor, lengths: Optional[Tensor] = None) -> Tensor:
+        return F.add_noise(waveform, noise, snr, lengths)
+
+
+class Preemphasis(torch.nn.Module):
+    r"""``y[i] = x[i] - coeff * x[i - 1]`` along the last dim (reference: T.Preemphasis); no buffers."""
+
+    def __init__(self, coeff: float = 0.97) -> None:
+        super().__init__()
+        self.coeff = coeff
+
+    def forward(self, waveform: Tensor) -> Tensor:
+        return F.preemphasis(waveform, coeff=self.coeff)
+
+
+class Deemphasis(torch.nn.Module):
+    r"""The inverse of ``Preemphasis``, through ``lfilter`` (reference: T.Deemphasis); no buffers."""
+
+    def __init__(self, coeff: float = 0.97) -> None:
+        super().__init__()
+        self.coeff = coeff
+
+    def forward(self, waveform: Tensor) -> Tensor:
+        return F.deemphasis(waveform, coeff=self.coeff)

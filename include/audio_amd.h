@@ -48,6 +48,8 @@
  *   aamd_spec_augment_iid     F.mask_along_axis_iid / T.SpecAugment (a dozen element-wise launches and one masked_fill
  *   aamd_spec_augment_shared  per mask in the reference); F.mask_along_axis / T.FrequencyMasking / T.TimeMasking
  *                             -- additions to ABI 7 as well
+ *   aamd_add_noise_f32        F.add_noise / T.AddNoise (two masks, two norms, logs, a power, a multiply and an add in the
+ *   aamd_preemphasis_f32      reference); F.preemphasis / T.Preemphasis -- additions to ABI 7 as well
  *   aamd_detect_pitch_f32     F.detect_pitch_frequency (_compute_nccf + _find_max_per_frame + _median_smoothing in the
  *                             reference; an addition to ABI 7 as well)
  *
@@ -567,6 +569,51 @@ int aamd_spec_augment_shared(const void* x, void* out, int64_t examples, int64_t
                              int64_t stride_example, int64_t stride_outer, int64_t stride_inner, int32_t dtype,
                              int32_t time_inner, int32_t n_masks, const int32_t* axes, const int64_t* starts,
                              const int64_t* ends, uint64_t value_bits, const void* value_ptr, void* stream);
+
+/* ---- waveform augmentation (additions to ABI 7; csrc/wave_augment.h) ------------------------------------------------ */
+
+enum { AAMD_ADD_NOISE_FORWARD = 0, AAMD_ADD_NOISE_GRADIENT = 1 };
+
+/* F.add_noise (functional/functional.py, add_noise): out = waveform + scale * noise per row, with
+ *   scale = 10 ** ((10 (log10 Es - log10 En) - snr) / 20),   Es / En = the sums of waveform^2 / noise^2 over the samples
+ * below the row's length.  Two launches: float64 partial sums per (row, chunk) into `workspace`
+ * (aamd_add_noise_workspace() bytes, 8-byte aligned; no floating-point atomics, so two calls give the same bits), then the
+ * mix over the whole row.  The scale is formed in float64 and rounded once; the product and the sum are rounded separately.
+ * Zero energies give what IEEE arithmetic gives (scale 0, +inf or NaN).
+ * Operands are (rows, length) with unit stride along time and a row stride in elements each: 0 reads one row for every
+ * output row (a broadcast noise), length + k reads rows of a wider tensor; rows that start on a 16-byte boundary move with
+ * 16-byte accesses, others sample by sample, nothing is copied.  out (and out2) are dense.  snr[row * stride_snr] (dB) and
+ * lengths[row * stride_lengths] (NULL: nothing masked; clamped to [0, length]) are device arrays read by the kernels.
+ * mode AAMD_ADD_NOISE_FORWARD:  cotangent and out2 are unused (NULL).
+ * mode AAMD_ADD_NOISE_GRADIENT: with d = sum over the row of cotangent * noise and m the length mask,
+ *   out = cotangent + d (s / Es) m waveform, out2 = s cotangent - d (s / En) m noise, and the first `rows` doubles of
+ *   workspace receive the gradient to snr, -(ln 10 / 20) s d.
+ * _lp: float16 / bfloat16 storage (dtype AAMD_SA_F16 / AAMD_SA_BF16), float32 arithmetic, results rounded once. */
+int64_t aamd_add_noise_workspace(int64_t rows, int64_t length);
+int aamd_add_noise_f32(const float* waveform, const float* noise, const float* cotangent, float* out, float* out2,
+                       void* workspace, int64_t rows, int64_t length, int64_t stride_waveform, int64_t stride_noise,
+                       int64_t stride_cotangent, const double* snr, int64_t stride_snr, const int64_t* lengths,
+                       int64_t stride_lengths, int32_t mode, void* stream);
+int aamd_add_noise_f64(const double* waveform, const double* noise, const double* cotangent, double* out, double* out2,
+                       void* workspace, int64_t rows, int64_t length, int64_t stride_waveform, int64_t stride_noise,
+                       int64_t stride_cotangent, const double* snr, int64_t stride_snr, const int64_t* lengths,
+                       int64_t stride_lengths, int32_t mode, void* stream);
+int aamd_add_noise_lp(const void* waveform, const void* noise, const void* cotangent, void* out, void* out2, void* workspace,
+                      int64_t rows, int64_t length, int64_t stride_waveform, int64_t stride_noise, int64_t stride_cotangent,
+                      const double* snr, int64_t stride_snr, const int64_t* lengths, int64_t stride_lengths, int32_t dtype,
+                      int32_t mode, void* stream);
+
+/* F.preemphasis (functional/functional.py, preemphasis): out[i] = x[i] - coeff * x[i - 1], out[0] = x[0]; transposed = 1
+ * applies the transpose of that map (its gradient), out[i] = x[i] - coeff * x[i + 1], out[length - 1] = x[length - 1].
+ * coeff is rounded to the compute type first; the product and the difference are rounded separately, so float32 and
+ * float64 results equal the reference's expression bit for bit.  x is (rows, length) with unit stride along time and
+ * stride_row elements between rows (any alignment, not copied); out is dense. */
+int aamd_preemphasis_f32(const float* x, float* out, int64_t rows, int64_t length, int64_t stride_row, double coeff,
+                         int32_t transposed, void* stream);
+int aamd_preemphasis_f64(const double* x, double* out, int64_t rows, int64_t length, int64_t stride_row, double coeff,
+                         int32_t transposed, void* stream);
+int aamd_preemphasis_lp(const void* x, void* out, int64_t rows, int64_t length, int64_t stride_row, double coeff, int32_t dtype,
+                        int32_t transposed, void* stream);
 
 #ifdef __cplusplus
 }
