@@ -426,11 +426,32 @@ def _istft_launch(spec_fm: Tensor, window_padded: Tensor, desc, adjoint: bool, i
     return out
 
 
+_NOISE_FLOOR_POWER = 2.0 ** -40         # (2^-20)^2: a bin this far under its neighbourhood's peak is rounding, not signal
+
+
+def _silence_noise_floor(X: Tensor, n_freq: int) -> Tensor:
+    """In place: exact zeros for the bins of the recomputed spectrum X (rows, T, 2 * n_freq) that lie under the float32 noise
+    floor of the transform.  The STFT kernels transform two frames per complex FFT, so a SILENT frame (zero padding, digital
+    silence) comes back as the rounding cross-talk of its partner, ~ 2^-24 of that frame's peak, instead of 0.  For p < 2 the
+    cotangent p |X|^(p-2) X turns that into a unit-phase (p = 1) or huge (p < 1) random gradient where the reference's is 0
+    (sgn(0) = 0), and the adjoint's own pairing spreads it into the neighbouring frame.  A bin below 2^-20 of the largest bin
+    of its frame and the two frames next to it (whatever the kernel's pairing) has no correct digit: it is treated as the
+    zero it stands for, and the gradient kernels return 0 there."""
+    rows, T = X.shape[0], X.shape[1]
+    Xc = X.view(rows, T, n_freq, 2)
+    m2 = Xc.square().sum(-1)                                                                # (rows, T, n_freq)
+    near = torch.nn.functional.max_pool1d(m2.amax(-1).unsqueeze(1), 3, 1, 1).squeeze(1)    # (rows, T)
+    Xc.mul_((m2 > near.unsqueeze(-1) * _NOISE_FLOOR_POWER).unsqueeze(-1))
+    return X
+
+
 def _spectrum_cotangent(x2: Tensor, window_padded: Tensor, desc, dpower: Tensor, power: float) -> Tensor:
     """G = dP * p * |X|^(p-2) * X with X recomputed by the fast complex STFT kernel; (rows, T, 2 * n_freq) float32."""
     dX = _copy_desc(desc, power=0.0)
     G = _spectrogram_launch(x2, window_padded, dX, None)               # X: (rows, T, 2 * n_freq) interleaved complex
     n = G.numel() // 2
+    if n and power != 2.0:
+        _silence_noise_floor(G, desc.n_fft // 2 + 1)
     if n:
         L = _lib.lib()                                                 # in place: G <- dP p |X|^(p-2) X
         _lib.check(L.aamd_spectrogram_grad_f32(G.data_ptr(), dpower.contiguous().data_ptr(), G.data_ptr(), n, float(power),
@@ -472,6 +493,8 @@ class _MelSpectrogramFunction(torch.autograd.Function):
         bands_t = _tensor_cached(fb, ("bands_T", str(dev)), lambda: MelBandsOnDevice(fb.t().contiguous(), dev))
         dy = dy.contiguous()
         G = _spectrogram_launch(x2, wp, _copy_desc(desc, power=0.0), None)      # X: (rows, T, 2 * n_freq)
+        if G.numel() and power != 2.0:
+            _silence_noise_floor(G, n_freq)
         if G.numel():
             L = _lib.lib()                                                      # in place: X -> (fb dY) p |X|^(p-2) X
             _lib.check(L.aamd_melspectrogram_grad_f32(G.data_ptr(), dy.data_ptr(), C.byref(bands_t.struct), rows * T, n_freq,
