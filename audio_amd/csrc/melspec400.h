@@ -908,6 +908,19 @@ AAMD_HD void phase_c(const LaneConst& c, const MelTab& mt, const float* lds,
   }
 }
 
+// one float to `base` (wave-uniform: an SGPR pair) + `voff` bytes (per lane, 32 bits) + OFF bytes (immediate).  Written out
+// because the compiler hoists the widening of the lane offset out of the tile loop and then no longer sees the
+// `uniform + zext(lane)` form: it keeps a register PAIR per address and adds the tile pointer with a 64-bit VALU
+// instruction per store.  (Nothing waits for these stores: the kernel never reads its output.)
+template <int OFF>
+AAMD_HD void store_f32_saddr(float v, char* base, unsigned voff) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  asm volatile("global_store_dword %0, %1, %2 offset:%3" : : "v"(voff), "v"(v), "s"(base), "i"(OFF) : "memory");
+#else
+  *reinterpret_cast<float*>(base + (size_t)voff + OFF) = v;
+#endif
+}
+
 // narrow store path (any n_mels / alignment): 4-byte stores straight from the accumulators
 //   Addressing: ONE wave-uniform tile pointer (SGPRs) + a small per-lane 32-bit offset, so every
 //   store is `global_store_dword voffset, data, s[base]` with one v_add -- no per-lane 64-bit pointers.
@@ -920,13 +933,30 @@ AAMD_HD void store_direct(const LaneConst& c, const MelTab& mt, const float (&ac
   float* out_tile = out_row + t0 * (int64_t)mt.n_mels;   // wave-uniform
   const unsigned oa = 2u * (unsigned)c.p * (unsigned)mt.n_mels;
   if (SIG != 0) {      // every round and every table row is live: one EXEC region per frame instead of one per store
+    // n_mels = 20 NR (checked at kernel entry).  The lane's part of the address is a 32-bit BYTE offset that does not change
+    // from tile to tile, and frame b lies a constant behind frame a: `global_store_dword voffset, data, s[tile] offset:` with no
+    // address arithmetic per store.
+    constexpr unsigned nm = kMelSlots * NR;
+    char* const ob = reinterpret_cast<char*>(out_row + t0 * (int64_t)nm);
+    unsigned bo[NR];
+#pragma unroll
+    for (int r = 0; r < NR; ++r) bo[r] = 4u * (2u * (unsigned)c.p * nm + (unsigned)h->mel(r));
+    if (left >= kFramesPerWave) {      // interior tile (wave-uniform): both frames of every active lane
+      if (c.active) {
+#pragma unroll
+        for (int r = 0; r < NR; ++r) store_f32_saddr<0>(acc_a[r], ob, bo[r]);
+#pragma unroll
+        for (int r = 0; r < NR; ++r) store_f32_saddr<4 * (int)nm>(acc_b[r], ob, bo[r]);
+      }
+      return;
+    }
     if (va) {
 #pragma unroll
-      for (int r = 0; r < NR; ++r) out_tile[oa + (unsigned)h->mel(r)] = acc_a[r];
+      for (int r = 0; r < NR; ++r) store_f32_saddr<0>(acc_a[r], ob, bo[r]);
     }
     if (vb) {
 #pragma unroll
-      for (int r = 0; r < NR; ++r) out_tile[oa + (unsigned)mt.n_mels + (unsigned)h->mel(r)] = acc_b[r];
+      for (int r = 0; r < NR; ++r) store_f32_saddr<4 * (int)nm>(acc_b[r], ob, bo[r]);
     }
     return;
   }
@@ -1058,8 +1088,13 @@ __device__ __forceinline__ void glds16s(const void* sbase, unsigned voff_bytes, 
 __device__ __forceinline__ void stage_wait() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
 
 struct TileInfo {
-  int64_t row, t0;
+  int64_t row;
+  int t0;        // first frame of the tile (< n_frames + 6: 32-bit, so the per-tile tests are scalar compares)
   bool staged;   // fully inside the clip and 16-B aligned: gathered through the LDS staging area
+  // carried from claim to claim instead of multiplied out per tile (the tiles of a workgroup's run are consecutive):
+  unsigned tin;      // tile inside its row, t0 = 6 tin
+  int64_t in_off;    // element offset of the row's first sample in `wav`
+  int64_t out_off;   // element offset of the row's first output in `out`
 };
 
 // LAB != 0 builds profiling variants for tools/ubench/mel400_lab.hip (wrong results by design):
@@ -1250,6 +1285,9 @@ melspec400_kernel(const TIn* __restrict__ wav, const float* __restrict__ window,
   // Twiddle batches (of five columns) held in registers instead of re-read from the LDS table every tile: all four under lab
   // bit 14 (spills).  The signature instantiation runs at 136 registers, so three batches fit its 168 (164; - 3.0 % on the
   // headline batch, 67.3 -> 65.3 us, profiles/r03_i_mel400_lab_twiddle_regs.txt): 15 of the 20 ds_read_b64 per tile gone.
+  // (Since the row stores take a scalar base the signature instantiation runs at 150 registers and a fourth batch fits, 159; it is
+  // 0.6 us faster but NOT bit-identical -- the compiler contracts that batch's complex multiplies into other fma pairs, 9e-8 of the
+  // peak -- so it stays at three: profiles/r07_b_mel400_lab_trim_ab.txt.)
   // The other float-input hop-160 instantiations get what their register count leaves (tests/test_no_spills.py keeps every
   // one of them out of scratch): Spectrogram 144 -> 2 batches, generic mel 149 / 135 (NR 4 / 8) -> 1 / 3, mel + dB 154 -> 1.
 #ifndef AAMD_M400_TWREG_DB
@@ -1321,9 +1359,13 @@ melspec400_kernel(const TIn* __restrict__ wav, const float* __restrict__ window,
     blk_first = 0;
     blk_count = fix_cnt;
   }
+  // (the LDS atomic as written: through __hip_atomic_fetch_add the compiler's wave-aggregation of uniform atomics wraps the
+  // one-lane add in mbcnt / bcnt / a second EXEC region / an add -- seven more instructions per tile for a single lane)
+  const unsigned queue_addr = (unsigned)(uintptr_t)queue;      // LDS byte address
   auto claim = [&]() {   // wave-uniform
     int v = 0;
-    if (lane == 0) v = __hip_atomic_fetch_add(queue, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    if (lane == 0)
+      asm volatile("ds_add_rtn_u32 %0, %1, %2\n\ts_waitcnt lgkmcnt(0)" : "=v"(v) : "v"(queue_addr), "v"(1) : "memory");
     return (unsigned)__builtin_amdgcn_readfirstlane(v);
   };
 #if AAMD_M400_POOLS
@@ -1387,6 +1429,25 @@ melspec400_kernel(const TIn* __restrict__ wav, const float* __restrict__ window,
     return g_base;
   };
 
+  // Tiles 1 .. tin_hi of a row are gathered through the staging area: fully inside the clip (tile 0 reflects at the clip's
+  // start: 6 hop >= n_fft / 2) and 16-B aligned.  Worked out once, so that the per-tile test is two 32-bit scalar compares
+  // (the 64-bit compares against `length` ran on the vector ALU, four instructions per tile).
+  static_assert(kFramesPerWave * kHop >= kPad, "tile 1 starts inside the clip");
+  unsigned tin_hi = 0;
+  if (in_aligned && length >= kN - kPad) {
+    int64_t last = (length - (kN - kPad)) / kHop - (kFramesPerWave - 1);      // largest t0 whose last frame ends inside the clip
+    if (last > (int64_t)n_frames - kFramesPerWave) last = (int64_t)n_frames - kFramesPerWave;
+    if (last >= kFramesPerWave) tin_hi = (unsigned)(last / kFramesPerWave);
+  }
+  // elements of `out` per waveform row
+  const int64_t out_row_elems =
+      EPI == EPI400_SPEC   ? (int64_t)n_frames * (epi.power > 0.0f ? kSpecBins : 2 * kSpecBins)
+      : EPI == EPI400_MFCC ? (int64_t)n_frames * epi.n_mfcc
+                           : (EPI == EPI400_MEL_NORM ? epi.out_frames : (int64_t)n_frames) * (int64_t)mb.n_mels;
+  auto tile_fill = [&](TileInfo& ti, unsigned idx) {
+    ti.t0 = (int)ti.tin * kFramesPerWave;
+    ti.staged = AAMD_M400_IDX_OK(idx) && ti.tin - 1u < tin_hi;
+  };
   auto tile_info = [&](unsigned idx) {
     TileInfo ti;
     unsigned t = ((LAB & 131072) ? 0u : blk_first) + idx;
@@ -1394,14 +1455,37 @@ melspec400_kernel(const TIn* __restrict__ wav, const float* __restrict__ window,
       t = idx < blk_count ? (unsigned)__hip_atomic_load(epi.fix_list + fix_base + idx, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;
     const unsigned row = t / (unsigned)tiles_per_row;
     ti.row = row;
-    ti.t0 = (int64_t)(t - row * (unsigned)tiles_per_row) * kFramesPerWave;
-    ti.staged = AAMD_M400_IDX_OK(idx) && in_aligned && (ti.t0 * kHop - kPad >= 0) &&
-                ((ti.t0 + kFramesPerWave - 1) * kHop + (kN - kPad) <= length) &&
-                (ti.t0 + kFramesPerWave <= n_frames);
+    ti.tin = t - row * (unsigned)tiles_per_row;
+    ti.in_off = (ti.row / InTraits<TIn>::chans) * row_stride;      // stereo: rows 2 i, 2 i + 1 = clip i
+    ti.out_off = ti.row * out_row_elems;
+    tile_fill(ti, idx);
+    return ti;
+  };
+  // The claim after `from` (queue index from_idx) is a later tile of the same run: step (row, tile in row) and the two row
+  // offsets forward by the distance instead of dividing by tiles_per_row and multiplying the offsets out again.  A row
+  // boundary is crossed at most `distance / tiles_per_row + 1` times, so rows of fewer than kCarryMinTiles tiles (and the
+  // claims whose tile number comes from a list or a pool) keep the division.
+  constexpr bool kCarry = !(LAB & (131072 | 16777216)) && !AAMD_M400_POOLS && EPI != EPI400_MFCC && InTraits<TIn>::chans == 1;
+  constexpr unsigned kCarryMinTiles = 16;
+  auto tile_next = [&](const TileInfo& from, unsigned from_idx, unsigned idx) {
+    if (!kCarry || (unsigned)tiles_per_row < kCarryMinTiles) return tile_info(idx);
+    TileInfo ti = from;
+    if (!(AAMD_M400_IDX_OK(idx))) {      // the queue is empty: nothing of `ti` is used but `staged`
+      ti.staged = false;
+      return ti;
+    }
+    ti.tin = from.tin + (idx - from_idx);
+    while (ti.tin >= (unsigned)tiles_per_row) {
+      ti.tin -= (unsigned)tiles_per_row;
+      ti.row += 1;
+      ti.in_off += row_stride;
+      ti.out_off += out_row_elems;
+    }
+    tile_fill(ti, idx);
     return ti;
   };
   auto stage_issue = [&](const TileInfo& ti) {
-    const TIn* src = wav + (ti.row / InTraits<TIn>::chans) * row_stride + (ti.t0 * kHop - kPad);   // stereo: rows 2 i, 2 i + 1 = clip i
+    const TIn* src = wav + ti.in_off + ((int64_t)ti.t0 * kHop - kPad);
     if (LAB & 32) src = wav + 6 * kHop;                 // lab: always the same (cache-resident) tile
 #pragma unroll
     for (int k = 0; k < SG::ndma; ++k)
@@ -1440,7 +1524,7 @@ melspec400_kernel(const TIn* __restrict__ wav, const float* __restrict__ window,
           const TileInfo ti = tile_info(AAMD_M400_LOCAL(t));
           const unsigned dst = (unsigned)(uintptr_t)(smem400 + (t % (unsigned)kWavesPerBlock) * HC::lds_dwords + kSOff);
           if (ti.staged) {
-            const TIn* src = wav + (ti.row / InTraits<TIn>::chans) * row_stride + (ti.t0 * kHop - kPad);
+            const TIn* src = wav + ti.in_off + ((int64_t)ti.t0 * kHop - kPad);
 #pragma unroll
             for (int k = 0; k < SG::ndma; ++k) glds16(src + spiece[k], dst + 1024 * k);
           }
@@ -1484,7 +1568,7 @@ melspec400_kernel(const TIn* __restrict__ wav, const float* __restrict__ window,
   }
   float Xn[HC::nx];   // lab bit 15: the next tile's samples, in flight
   auto gload = [&](const TileInfo& ti) {
-    const TIn* src = wav + (ti.row / InTraits<TIn>::chans) * row_stride + (ti.t0 * kHop - kPad) + (HC::pair_stride * c.p + c.pi);
+    const TIn* src = wav + ti.in_off + ((int64_t)ti.t0 * kHop - kPad) + (HC::pair_stride * c.p + c.pi);
 #pragma unroll
     for (int q = 0; q < HC::nx; ++q) Xn[q] = InTraits<TIn>::get(src + 20 * q, (int)(ti.row % InTraits<TIn>::chans));
   };
@@ -1544,7 +1628,7 @@ melspec400_kernel(const TIn* __restrict__ wav, const float* __restrict__ window,
 #else
     const unsigned nxt_idx = (LAB & 131072) ? g_next() : claim();
 #endif
-    TileInfo nxt = tile_info(nxt_idx);
+    TileInfo nxt = tile_next(cur, cur_idx, nxt_idx);
     float fix_cut = -INFINITY;
     if (fix) {
       // fix-up pass: the tiles of the compacted list (smallest dB value under the cut-off) are redone, clamped; their samples
@@ -1566,7 +1650,7 @@ melspec400_kernel(const TIn* __restrict__ wav, const float* __restrict__ window,
         gather_lds<H, TIn>(c, reinterpret_cast<const TIn*>(lds + kSOff), X, (int)(cur.row % InTraits<TIn>::chans));
       }
     } else {
-      gather_global<H, TIn>(c, wav + (cur.row / InTraits<TIn>::chans) * row_stride, length, cur.t0, n_frames, X,
+      gather_global<H, TIn>(c, wav + cur.in_off, length, cur.t0, n_frames, X,
                             (int)(cur.row % InTraits<TIn>::chans));
     }
 #if AAMD_M400_POOLS
@@ -1601,7 +1685,7 @@ melspec400_kernel(const TIn* __restrict__ wav, const float* __restrict__ window,
       const int64_t left = n_frames - cur.t0;
       const int n_valid = left < kFramesPerWave ? (int)left : kFramesPerWave;
       if (epi.power > 0.0f) {
-        const int64_t a0 = (cur.row * n_frames + cur.t0) * (int64_t)kSpecBins;
+        const int64_t a0 = cur.out_off + (int64_t)cur.t0 * kSpecBins;
         phase_b2_spec(c, zr, zi, qr, qi, epi.power, (int)(a0 & 3), lds);
         wave_lds_fence();
         if (!(LAB & 2)) {
@@ -1612,7 +1696,7 @@ melspec400_kernel(const TIn* __restrict__ wav, const float* __restrict__ window,
       } else {   // complex output, two halves of 3 frames
 #pragma unroll
         for (int half = 0; half < 2; ++half) {
-          const int64_t a0 = (cur.row * n_frames + cur.t0 + 3 * half) * (int64_t)(2 * kSpecBins);
+          const int64_t a0 = cur.out_off + (int64_t)(cur.t0 + 3 * half) * (2 * kSpecBins);
           const int nv = n_valid - 3 * half < 3 ? n_valid - 3 * half : 3;
           phase_b2_spec_complex(c, zr, zi, qr, qi, half, (int)(a0 & 3), lds);
           wave_lds_fence();
@@ -1796,7 +1880,7 @@ melspec400_kernel(const TIn* __restrict__ wav, const float* __restrict__ window,
         }
       }
     }
-    float* out_row = out + cur.row * (EPI == EPI400_MEL_NORM ? epi.out_frames : (int64_t)n_frames) * (int64_t)mb.n_mels;
+    float* out_row = out + cur.out_off;
     if (LAB & 4194304) out_row = out + (int64_t)(wave + kWavesPerBlock * (blockIdx.x & 63)) * 6 * mb.n_mels - cur.t0 * (int64_t)mb.n_mels;   // lab bit 22: every store of a wave goes to one cache-resident tile
     if (out_wide) {
       wave_lds_fence();
