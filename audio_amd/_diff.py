@@ -333,3 +333,108 @@ def add_noise_grads(g: Tensor, waveform: Tensor, noise: Tensor, snr: Tensor, len
     gn = s.unsqueeze(-1) * g - (d * s / en).unsqueeze(-1) * nm
     gs = -(math.log(10.0) / 20.0) * s * d
     return gw, gn, gs
+
+
+# ---- MVDR beamforming: the differentiable compositions (csrc/beamform.h is the inference path) ----------------------------
+# Tensor arithmetic around ONE autograd Function, the batched small solve X = A^-1 B, whose forward is the HIP solve and whose
+# backward calls itself -- so every order of derivative runs on the kernel and nothing needs torch.linalg on the device.
+
+class _BfSolveFunction(torch.autograd.Function):
+    """X = A^-1 B for A (bins, C, C), B (bins, C, K), K <= C.  gB = (A^H)^-1 g, gA = -gB X^H."""
+
+    @staticmethod
+    def forward(ctx, a, b):
+        from . import functional as F
+        # (resolve_conj first: a lazily conjugated operand -- a.mH of one channel, a user's psd.conj() -- already counts as
+        # contiguous, and the launch reads memory, not the conjugate bit)
+        x = F._bf_weights_launch(F._BF_SOLVE, a.detach().resolve_conj().contiguous(), b.detach().resolve_conj().contiguous(), None,
+                                 a.shape[0], 1, -1, False, 0.0, 0.0)
+        ctx.save_for_backward(a, x)
+        return x
+
+    @staticmethod
+    def backward(ctx, g):
+        from . import functional as F
+        a, x = ctx.saved_tensors
+        if torch.is_grad_enabled():                         # the backward is being recorded: through the Function again
+            gb = _BfSolveFunction.apply(a.mH, g)
+        else:
+            gb = F._bf_weights_launch(F._BF_SOLVE, a.detach().resolve_conj().contiguous(), g.resolve_conj().contiguous(), None,
+                                      a.shape[0], 1, -1, False, 0.0, 0.0, 0, True)
+        ga = -_bf_mm(gb, x.mH) if ctx.needs_input_grad[0] else None
+        return ga, gb if ctx.needs_input_grad[1] else None
+
+
+def _bf_mm(a: Tensor, b: Tensor) -> Tensor:
+    """(..., m, k) @ (..., k, n) as a broadcast product and a sum (no BLAS: the matrices are 1 .. 16 wide)."""
+    return (a.unsqueeze(-1) * b.unsqueeze(-3)).sum(-2)
+
+
+def bf_solve(a: Tensor, b: Tensor) -> Tensor:
+    """A^-1 B for (..., C, C) and (..., C, K)."""
+    c, k = a.shape[-1], b.shape[-1]
+    x = _BfSolveFunction.apply(a.reshape(-1, c, c), b.expand(tuple(a.shape[:-2]) + (c, k)).reshape(-1, c, k))
+    return x.view(tuple(a.shape[:-2]) + (c, k))
+
+
+def bf_psd(specgram: Tensor, mask: Optional[Tensor], normalize: bool, eps: float) -> Tensor:
+    x = specgram.transpose(-3, -2)                                           # (..., F, C, T)
+    xm = x
+    if mask is not None:
+        if normalize:
+            mask = mask / (mask.sum(dim=-1, keepdim=True) + eps)
+        xm = x * mask.unsqueeze(-2)
+    return (xm.unsqueeze(-2) * x.conj().unsqueeze(-3)).sum(-1)
+
+
+def bf_loaded(psd_n: Tensor, diag_eps: float) -> Tensor:
+    c = psd_n.shape[-1]
+    tr = psd_n.diagonal(dim1=-1, dim2=-2).sum(-1).real
+    eye = torch.eye(c, dtype=psd_n.dtype, device=psd_n.device)
+    return psd_n + (tr * diag_eps + 1e-8)[..., None, None] * eye
+
+
+def _bf_times_ref(m: Tensor, reference_channel) -> Tensor:
+    """Column `ref` of (..., F, C, C), or its product with a reference vector (..., C)."""
+    if isinstance(reference_channel, Tensor):
+        return (m * reference_channel.to(m.dtype)[..., None, None, :]).sum(-1)
+    return m[..., :, reference_channel]
+
+
+def bf_souden(psd_s, psd_n, reference_channel, diagonal_loading, diag_eps, eps):
+    if diagonal_loading:
+        psd_n = bf_loaded(psd_n, diag_eps)
+    n = bf_solve(psd_n, psd_s)
+    w = n / (n.diagonal(dim1=-1, dim2=-2).sum(-1)[..., None, None] + eps)
+    return _bf_times_ref(w, reference_channel)
+
+
+def bf_rtf(rtf, psd_n, reference_channel, diagonal_loading, diag_eps, eps):
+    if diagonal_loading:
+        psd_n = bf_loaded(psd_n, diag_eps)
+    n = bf_solve(psd_n, rtf.unsqueeze(-1)).squeeze(-1)
+    w = n / ((rtf.conj() * n).sum(-1, keepdim=True).real + eps)
+    if isinstance(reference_channel, Tensor):
+        w = w * (rtf.conj() * reference_channel.to(rtf.dtype).unsqueeze(-2)).sum(-1, keepdim=True)
+    elif reference_channel is not None:
+        w = w * rtf[..., reference_channel, None].conj()
+    return w
+
+
+def bf_rtf_power(psd_s, psd_n, reference_channel, n_iter, diagonal_loading, diag_eps):
+    if diagonal_loading:
+        psd_n = bf_loaded(psd_n, diag_eps)
+    phi = bf_solve(psd_n, psd_s)
+    r = _bf_times_ref(phi, reference_channel).unsqueeze(-1)
+    if n_iter >= 2:
+        for _ in range(n_iter - 2):
+            r = _bf_mm(phi, r)
+        r = _bf_mm(psd_s, r)
+    else:
+        r = _bf_mm(psd_n, r)
+    return r.squeeze(-1)
+
+
+def bf_apply(beamform_weights: Tensor, specgram: Tensor) -> Tensor:
+    return (beamform_weights.conj().transpose(-1, -2).unsqueeze(-1) * specgram).sum(-3)
+

@@ -155,6 +155,13 @@ _SIGS = {
     "aamd_preemphasis_f32": (C.c_int, [_P, _P] + [C.c_int64] * 3 + [C.c_double, C.c_int32, _P]),
     "aamd_preemphasis_f64": (C.c_int, [_P, _P] + [C.c_int64] * 3 + [C.c_double, C.c_int32, _P]),
     "aamd_preemphasis_lp": (C.c_int, [_P, _P] + [C.c_int64] * 3 + [C.c_double, C.c_int32, C.c_int32, _P]),
+    # MVDR beamforming (additions to ABI 7)
+    "aamd_beamform_freq_tile": (C.c_int32, []),
+    "aamd_beamform_time_chunk": (C.c_int32, []),
+    "aamd_beamform_psd": (C.c_int, [C.c_int32, _P] + [C.c_int64] * 8 + [_P, _P, _P, _P, C.c_int32, C.c_double, _P, _P]),
+    "aamd_beamform_weights": (C.c_int, [C.c_int32, C.c_int32, _P, _P, _P, _P, C.c_int64, C.c_int64] + [C.c_int32] * 4 +
+                              [C.c_double, C.c_double, C.c_int32, C.c_int32, _P]),
+    "aamd_beamform_apply": (C.c_int, [C.c_int32, _P, _P] + [C.c_int64] * 8 + [_P, _P, _P]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS)

@@ -64,6 +64,15 @@ _DEF.define("add_noise(Tensor waveform, Tensor noise, Tensor snr, Tensor? length
 _DEF.define("preemphasis(Tensor waveform, float coeff) -> Tensor")
 _DEF.define("deemphasis(Tensor waveform, float coeff) -> Tensor")
 _DEF.define("convolve(Tensor x, Tensor y, str mode) -> Tensor")
+_DEF.define("psd(Tensor specgram, Tensor? mask, bool normalize, float eps) -> Tensor")
+_DEF.define("psd_pair(Tensor specgram, Tensor mask_s, Tensor mask_n, bool normalize, float eps) -> Tensor")
+_DEF.define("mvdr_weights_souden(Tensor psd_s, Tensor psd_n, int reference_channel, Tensor? reference_vector, "
+            "bool diagonal_loading, float diag_eps, float eps) -> Tensor")
+_DEF.define("mvdr_weights_rtf(Tensor rtf, Tensor psd_n, int? reference_channel, Tensor? reference_vector, "
+            "bool diagonal_loading, float diag_eps, float eps) -> Tensor")
+_DEF.define("rtf_power(Tensor psd_s, Tensor psd_n, int reference_channel, Tensor? reference_vector, int n_iter, "
+            "bool diagonal_loading, float diag_eps) -> Tensor")
+_DEF.define("apply_beamforming(Tensor beamform_weights, Tensor specgram) -> Tensor")
 _DEF.define("rnnt_features(Tensor waveform, Tensor window, Tensor fb, int n_fft, int hop_length, float gain, Tensor mean, "
             "Tensor invstddev, int right_padding) -> Tensor")
 
@@ -175,6 +184,21 @@ _register("add_noise", F._add_noise_eager)
 _register("preemphasis", F._preemphasis_eager)
 _register("deemphasis", F._deemphasis_eager)
 _register("convolve", F._convolve_eager)
+
+
+def _ref_of(reference_channel, reference_vector):
+    return reference_vector if reference_vector is not None else reference_channel
+
+
+_register("psd", F._psd_eager)
+_register("psd_pair", F._psd_pair_eager)
+_register("mvdr_weights_souden", lambda psd_s, psd_n, ref, vec, loading, diag_eps, eps:
+          F._mvdr_weights_souden_eager(psd_s, psd_n, _ref_of(ref, vec), loading, diag_eps, eps))
+_register("mvdr_weights_rtf", lambda rtf, psd_n, ref, vec, loading, diag_eps, eps:
+          F._mvdr_weights_rtf_eager(rtf, psd_n, _ref_of(ref, vec), loading, diag_eps, eps))
+_register("rtf_power", lambda psd_s, psd_n, ref, vec, n_iter, loading, diag_eps:
+          F._rtf_power_eager(psd_s, psd_n, _ref_of(ref, vec), n_iter, loading, diag_eps))
+_register("apply_beamforming", F._apply_beamforming_eager)
 
 
 # ---- Meta implementations: shapes / strides only ---------------------------------------------
@@ -337,3 +361,30 @@ _META.impl("add_noise", _add_noise_meta)
 _META.impl("preemphasis", lambda waveform, coeff: torch.empty_like(waveform, memory_format=torch.contiguous_format))
 _META.impl("deemphasis", lambda waveform, coeff: torch.empty_like(waveform, memory_format=torch.contiguous_format))
 _META.impl("convolve", _fftconvolve_meta)
+
+
+def _psd_meta(specgram, mask, normalize, eps):
+    c, f = specgram.shape[-3], specgram.shape[-2]
+    return specgram.new_empty(tuple(specgram.shape[:-3]) + (f, c, c))
+
+
+def _psd_pair_meta(specgram, mask_s, mask_n, normalize, eps):
+    c, f = specgram.shape[-3], specgram.shape[-2]
+    return specgram.new_empty((2,) + tuple(specgram.shape[:-3]) + (f, c, c))
+
+
+def _apply_beamforming_meta(beamform_weights, specgram):
+    """(..., freq, time) in the input's (freq, time) stride order: frame-major in, frame-major out."""
+    lead, f, t = tuple(specgram.shape[:-3]), specgram.shape[-2], specgram.shape[-1]
+    if t > 1 and specgram.stride(-1) != 1 and (f <= 1 or specgram.stride(-2) == 1):
+        return specgram.new_empty(lead + (t, f)).transpose(-1, -2)
+    return specgram.new_empty(lead + (f, t))
+
+
+_META.impl("psd", _psd_meta)
+_META.impl("psd_pair", _psd_pair_meta)
+_META.impl("mvdr_weights_souden", lambda psd_s, psd_n, *rest: psd_n.new_empty(tuple(psd_n.shape[:-1])))
+_META.impl("mvdr_weights_rtf", lambda rtf, psd_n, *rest: rtf.new_empty(tuple(rtf.shape)))
+_META.impl("rtf_power", lambda psd_s, psd_n, *rest: psd_n.new_empty(tuple(psd_n.shape[:-1])))
+_META.impl("apply_beamforming", _apply_beamforming_meta)
+

@@ -36,7 +36,10 @@ OPS = ("spectrogram", "mel_spectrogram", "mel_spectrogram_db", "mfcc_dct", "resa
        # SpecAugment masking: a whole policy in one launch (F.mask_along_axis[_iid], T.SpecAugment; an addition to ABI 7)
        "spec_augment",
        # waveform augmentation: the two launches of F.add_noise, forward and gradient, and F.preemphasis (additions to ABI 7)
-       "add_noise", "add_noise_grad", "preemphasis")
+       "add_noise", "add_noise_grad", "preemphasis",
+       # MVDR beamforming: F.psd (one or two masks), the per-bin solve of the weight functions, F.apply_beamforming
+       # (additions to ABI 7); complex tensors cross as their real views
+       "beamform_psd", "beamform_weights", "beamform_apply")
 
 _lock = threading.Lock()
 _handle = None
@@ -222,6 +225,20 @@ def _register_fakes() -> None:
     @reg("aamd::preemphasis")
     def _(waveform, coeff, transposed):
         return waveform.new_empty(waveform.shape)
+
+    @reg("aamd::beamform_psd")
+    def _(specgram, mask1, mask2, normalize, eps):
+        B, C, F = specgram.shape[0], specgram.shape[1], specgram.shape[2]
+        return specgram.new_empty((2 if mask2 is not None else 1, B, F, C, C, 2))
+
+    @reg("aamd::beamform_weights")
+    def _(mode, a, b, reference_vector, batch, freq, reference, loading, diag_eps, eps, n_iter, adjoint):
+        return a.new_empty(b.shape if mode == 0 else (a.shape[0], a.shape[1], 2))
+
+    @reg("aamd::beamform_apply")
+    def _(weights, specgram, frame_major):
+        B, F, T = specgram.shape[0], specgram.shape[2], specgram.shape[3]
+        return specgram.new_empty((B, T, F, 2) if frame_major else (B, F, T, 2))
 
 
 def available() -> bool:

@@ -34,6 +34,7 @@
 #include "spec_augment.h"
 #include "stft_generic.h"
 #include "wave_augment.h"
+#include "beamform.h"
 
 using namespace aamd;
 
@@ -2064,6 +2065,116 @@ int aamd_preemphasis_lp(const void* x, void* out, int64_t rows, int64_t length, 
                         int32_t transposed, void* stream) {
   AAMD_CHECK_ARG(dtype == AAMD_SA_F16 || dtype == AAMD_SA_BF16, "preemphasis: the low-precision entry takes AAMD_SA_F16 or AAMD_SA_BF16");
   return preemphasis(dtype, x, out, rows, length, stride_row, coeff, transposed, stream);
+}
+
+// ---- MVDR beamforming: psd, the per-bin solve, apply (csrc/beamform.h) ---------------------------------------------------
+int32_t aamd_beamform_freq_tile(void) { return bf::kFT; }
+int32_t aamd_beamform_time_chunk(void) { return bf::kTCMax; }
+
+static int bf_view(bf::SpecView& v, const void* x, int64_t B, int64_t C, int64_t F, int64_t T, int64_t sb, int64_t sc,
+                   int64_t sf, int64_t st, int32_t& fmajor) {
+  AAMD_CHECK_ARG(B >= 0 && F >= 0 && T >= 0, "beamform: bad sizes");
+  if (C > AAMD_BF_MAX_CHANNELS) return fail(AAMD_EINVAL, "audio_amd: beamform: more than 16 channels are not implemented");
+  AAMD_CHECK_ARG(C >= 1, "beamform: bad sizes");
+  AAMD_CHECK_ARG(sb >= 0 && sc >= 0 && sf >= 0 && st >= 0, "beamform: negative stride");
+  AAMD_CHECK_ARG(sf == 1 || st == 1 || F <= 1 || T <= 1, "beamform: the spectrogram needs unit stride along freq or time");
+  fmajor = st == 1 ? 0 : (sf == 1 ? 1 : (T <= 1 ? 0 : 1));      // the unit-stride axis; an axis of one element serves as well
+  v.p = x; v.sb = sb; v.sc = sc; v.sf = sf; v.st = st;
+  return AAMD_OK;
+}
+
+extern "C++" template <typename T>
+static void psd_launch(const bf::PsdArgs& a, int64_t blocks, hipStream_t s) {
+  const int no = bf::outputs_per_thread(a.C);
+  const dim3 grid((unsigned)blocks), block(bf::kThreads);
+  if (no <= 1) hipLaunchKernelGGL((bf::psd_kernel<T, 1>), grid, block, 0, s, a);
+  else if (no <= 3) hipLaunchKernelGGL((bf::psd_kernel<T, 3>), grid, block, 0, s, a);
+  else hipLaunchKernelGGL((bf::psd_kernel<T, 9>), grid, block, 0, s, a);
+}
+
+int aamd_beamform_psd(int32_t dtype, const void* x, int64_t batch, int64_t channels, int64_t freq, int64_t time,
+                      int64_t stride_b, int64_t stride_c, int64_t stride_f, int64_t stride_t, const void* mask1,
+                      const int64_t* mask1_strides, const void* mask2, const int64_t* mask2_strides, int32_t normalize,
+                      double eps, void* out, void* stream) {
+  DeviceScope dev_scope_(x);
+  AAMD_CHECK_ARG(dtype == AAMD_BF_C64 || dtype == AAMD_BF_C128, "beamform: unknown element type");
+  bf::PsdArgs a{};
+  int rc = bf_view(a.x, x, batch, channels, freq, time, stride_b, stride_c, stride_f, stride_t, a.fmajor);
+  if (rc != AAMD_OK) return rc;
+  AAMD_CHECK_ARG(mask1 || !mask2, "psd: a second mask needs a first one");
+  AAMD_CHECK_ARG((!mask1 || mask1_strides) && (!mask2 || mask2_strides), "psd: a mask needs its strides");
+  if (batch * freq == 0) return AAMD_OK;
+  AAMD_CHECK_ARG(out && (x || time == 0), "null buffer");
+  a.mask[0] = mask1; a.mask[1] = mask2;
+  const int64_t* ms[2] = {mask1_strides, mask2_strides};
+  for (int n = 0; n < 2; ++n)
+    if (a.mask[n]) {
+      AAMD_CHECK_ARG(ms[n][0] >= 0 && ms[n][1] >= 0 && ms[n][2] >= 0, "psd: negative mask stride");
+      a.mb[n] = ms[n][0]; a.mf[n] = ms[n][1]; a.mt[n] = ms[n][2];
+    }
+  a.out = out; a.B = batch; a.F = freq; a.T = time; a.C = (int32_t)channels;
+  a.n_out = mask2 ? 2 : 1; a.normalize = normalize ? 1 : 0; a.eps = eps;
+  const int64_t blocks = batch * bf::freq_tiles(freq);
+  AAMD_CHECK_ARG(blocks < (1ll << 31), "too many tiles for one launch");
+  if (dtype == AAMD_BF_C64) psd_launch<float>(a, blocks, (hipStream_t)stream);
+  else psd_launch<double>(a, blocks, (hipStream_t)stream);
+  return launch_check();
+}
+
+int aamd_beamform_weights(int32_t dtype, int32_t mode, const void* a_, const void* b, const void* reference_vector, void* out,
+                          int64_t batch, int64_t freq, int32_t channels, int32_t rhs, int32_t reference, int32_t loading,
+                          double diag_eps, double eps, int32_t n_iter, int32_t adjoint, void* stream) {
+  DeviceScope dev_scope_(a_);
+  AAMD_CHECK_ARG(dtype == AAMD_BF_C64 || dtype == AAMD_BF_C128, "beamform: unknown element type");
+  AAMD_CHECK_ARG(mode >= AAMD_BF_SOLVE && mode <= AAMD_BF_RTF_POWER, "beamform: unknown mode");
+  AAMD_CHECK_ARG(batch >= 0 && freq >= 0, "beamform: bad sizes");
+  if (channels > AAMD_BF_MAX_CHANNELS) return fail(AAMD_EINVAL, "audio_amd: beamform: more than 16 channels are not implemented");
+  AAMD_CHECK_ARG(channels >= 1, "beamform: bad sizes");
+  if (mode == AAMD_BF_SOUDEN || mode == AAMD_BF_RTF_POWER) rhs = channels;
+  if (mode == AAMD_BF_RTF) rhs = 1;
+  AAMD_CHECK_ARG(rhs >= 1 && rhs <= channels, "beamform: between 1 and `channels` right-hand sides");
+  AAMD_CHECK_ARG(reference < channels, "beamform: the reference channel is out of range");
+  AAMD_CHECK_ARG(mode == AAMD_BF_SOLVE || mode == AAMD_BF_RTF || reference >= 0 || reference_vector,
+                 "beamform: this mode needs a reference channel or vector");
+  AAMD_CHECK_ARG(mode != AAMD_BF_RTF_POWER || n_iter >= 1, "rtf_power: n_iter must be positive");
+  AAMD_CHECK_ARG(mode == AAMD_BF_SOLVE || !adjoint, "beamform: adjoint belongs to AAMD_BF_SOLVE");
+  const int64_t bins = batch * freq;
+  if (bins == 0) return AAMD_OK;
+  AAMD_CHECK_ARG(a_ && b && out, "null buffer");
+  bf::WArgs a{};
+  a.a = a_; a.b = b; a.u = reference >= 0 ? nullptr : reference_vector; a.out = out;
+  a.bins = bins; a.F = freq; a.C = channels; a.K = rhs; a.mode = mode; a.ref = reference >= 0 ? reference : -1;
+  a.loading = loading ? 1 : 0; a.n_iter = n_iter; a.adjoint = adjoint ? 1 : 0; a.diag_eps = diag_eps; a.eps = eps;
+  const int64_t blocks = (bins + bf::kTeams - 1) / bf::kTeams;
+  AAMD_CHECK_ARG(blocks < (1ll << 31), "too many bins for one launch");
+  const dim3 grid((unsigned)blocks), block(bf::kTeam * bf::kTeams);
+  if (dtype == AAMD_BF_C64) hipLaunchKernelGGL(bf::weights_kernel<float>, grid, block, 0, (hipStream_t)stream, a);
+  else hipLaunchKernelGGL(bf::weights_kernel<double>, grid, block, 0, (hipStream_t)stream, a);
+  return launch_check();
+}
+
+int aamd_beamform_apply(int32_t dtype, const void* w, const void* x, int64_t batch, int64_t channels, int64_t freq,
+                        int64_t time, int64_t stride_b, int64_t stride_c, int64_t stride_f, int64_t stride_t, void* out,
+                        const int64_t* out_strides, void* stream) {
+  DeviceScope dev_scope_(x);
+  AAMD_CHECK_ARG(dtype == AAMD_BF_C64 || dtype == AAMD_BF_C128, "beamform: unknown element type");
+  bf::ApplyArgs a{};
+  int rc = bf_view(a.x, x, batch, channels, freq, time, stride_b, stride_c, stride_f, stride_t, a.fmajor);
+  if (rc != AAMD_OK) return rc;
+  if (batch * freq * time == 0) return AAMD_OK;
+  AAMD_CHECK_ARG(w && x && out && out_strides, "null buffer");
+  AAMD_CHECK_ARG(out_strides[0] >= 0 && out_strides[1] >= 1 && out_strides[2] >= 1, "apply_beamforming: bad output strides");
+  AAMD_CHECK_ARG((a.fmajor ? out_strides[1] : out_strides[2]) == 1 || (a.fmajor ? freq : time) <= 1,
+                 "apply_beamforming: the output needs unit stride along the input's unit-stride axis");
+  a.w = w; a.out = out; a.ob = out_strides[0]; a.of = out_strides[1]; a.ot = out_strides[2];
+  a.B = batch; a.F = freq; a.T = time; a.C = (int32_t)channels;
+  const int U = dtype == AAMD_BF_C64 ? bf::unit_tile<float>() : bf::unit_tile<double>();
+  const int64_t blocks = batch * bf::apply_unit_tiles(a.fmajor ? freq : time, U) * bf::apply_line_tiles(a.fmajor ? time : freq);
+  AAMD_CHECK_ARG(blocks < (1ll << 31), "too many tiles for one launch");
+  const dim3 grid((unsigned)blocks), block(bf::kThreads);
+  if (dtype == AAMD_BF_C64) hipLaunchKernelGGL(bf::apply_kernel<float>, grid, block, 0, (hipStream_t)stream, a);
+  else hipLaunchKernelGGL(bf::apply_kernel<double>, grid, block, 0, (hipStream_t)stream, a);
+  return launch_check();
 }
 
 }  // extern "C"

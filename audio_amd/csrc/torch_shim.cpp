@@ -937,6 +937,99 @@ Tensor preemphasis(Tensor x, double coeff, bool transposed) {
   return out;
 }
 
+// ---- aamd::beamform_psd / beamform_weights / beamform_apply (F.psd, the MVDR weight solves, F.apply_beamforming;
+// csrc/beamform.h) -------------------------------------------------------------------------------------------------------
+// Complex tensors cross as their real views (..., 2): float32 for complex64, float64 for complex128.
+int32_t bf_dtype(const Tensor& x, const char* what) {
+  STD_TORCH_CHECK(x.is_cuda(), "audio_amd: ", what, " must be on an MI355X (ROCm) device; there is no CPU kernel");
+  STD_TORCH_CHECK(x.dim() >= 1 && x.size(x.dim() - 1) == 2 && x.stride(x.dim() - 1) == 1, "audio_amd: ", what,
+                  " must be the real view (..., 2) of a complex tensor");
+  if (x.scalar_type() == ScalarType::Float) return AAMD_BF_C64;
+  STD_TORCH_CHECK(x.scalar_type() == ScalarType::Double, "audio_amd: ", what, " must be complex64 or complex128");
+  return AAMD_BF_C128;
+}
+// strides of the real view (B, C, F, T, 2) in complex elements
+void bf_spec(const Tensor& x, int64_t st[4]) {
+  STD_TORCH_CHECK(x.dim() == 5, "audio_amd: specgram must be the real view of (batch, channel, freq, time)");
+  for (int d = 0; d < 4; ++d) {
+    STD_TORCH_CHECK(x.size(d) <= 1 || (x.stride(d) >= 0 && x.stride(d) % 2 == 0), "audio_amd: specgram strides must be even and non-negative");
+    st[d] = x.size(d) > 1 ? x.stride(d) / 2 : (d == 3 ? 1 : 0);
+  }
+}
+const void* bf_mask(const std::optional<Tensor>& m, const Tensor& x, int64_t st[3]) {
+  if (!m.has_value()) return nullptr;
+  STD_TORCH_CHECK(m->is_cuda() && m->scalar_type() == x.scalar_type() && m->dim() == 3 && m->size(0) == x.size(0) &&
+                  m->size(1) == x.size(2) && m->size(2) == x.size(3),
+                  "audio_amd: a mask must be a real (batch, freq, time) device tensor of the specgram's precision");
+  same_device(x, *m);
+  for (int d = 0; d < 3; ++d) {
+    STD_TORCH_CHECK(m->size(d) <= 1 || m->stride(d) >= 0, "audio_amd: a mask has a negative stride");
+    st[d] = m->size(d) > 1 ? m->stride(d) : 0;
+  }
+  return m->numel() ? m->data_ptr() : nullptr;
+}
+Tensor beamform_psd(Tensor x, std::optional<Tensor> mask1, std::optional<Tensor> mask2, bool normalize, double eps) {
+  const int32_t dtype = bf_dtype(x, "specgram");
+  int64_t sx[4], s1[3], s2[3];
+  bf_spec(x, sx);
+  STD_TORCH_CHECK(mask1.has_value() || !mask2.has_value(), "audio_amd: a second mask needs a first one");
+  const void* m1 = bf_mask(mask1, x, s1);
+  const void* m2 = bf_mask(mask2, x, s2);
+  const torch::stable::accelerator::DeviceGuard guard(x.get_device_index());
+  const int64_t n = mask2.has_value() ? 2 : 1, B = x.size(0), C = x.size(1), F = x.size(2), T = x.size(3);
+  STD_TORCH_CHECK(C <= AAMD_BF_MAX_CHANNELS, "audio_amd: beamform: more than 16 channels are not implemented");
+  Tensor out = torch::stable::new_empty(x, {n, B, F, C, C, 2});
+  if (out.numel() == 0) return out;
+  if (T == 0) { torch::stable::fill_(out, 0.0); return out; }
+  check(aamd_beamform_psd(dtype, x.data_ptr(), B, C, F, T, sx[0], sx[1], sx[2], sx[3], m1, s1, m2, s2, normalize ? 1 : 0, eps,
+                          out.data_ptr(), current_stream(x)));
+  return out;
+}
+Tensor beamform_weights(int64_t mode, Tensor a, Tensor b, std::optional<Tensor> ref_vec, int64_t batch, int64_t freq,
+                        int64_t reference, bool loading, double diag_eps, double eps, int64_t n_iter, bool adjoint) {
+  const int32_t dtype = bf_dtype(a, "psd_n");
+  STD_TORCH_CHECK(bf_dtype(b, "the right-hand side") == dtype, "audio_amd: beamform operands must share a dtype");
+  STD_TORCH_CHECK(a.dim() == 4 && a.is_contiguous() && b.is_contiguous() && a.size(1) == a.size(2) && a.size(0) == batch * freq,
+                  "audio_amd: psd_n must be a contiguous (bins, C, C) complex tensor");
+  same_device(a, b);
+  const int64_t bins = a.size(0), C = a.size(1);
+  STD_TORCH_CHECK(C <= AAMD_BF_MAX_CHANNELS, "audio_amd: beamform: more than 16 channels are not implemented");
+  const bool vec = mode == AAMD_BF_RTF;
+  STD_TORCH_CHECK(b.dim() == (vec ? 3 : 4) && b.size(0) == bins && b.size(1) == C, "audio_amd: the right-hand side does not belong to psd_n");
+  const int64_t K = vec ? 1 : b.size(2);
+  const void* u = nullptr;
+  if (ref_vec.has_value()) {
+    STD_TORCH_CHECK(bf_dtype(*ref_vec, "reference_channel") == dtype && ref_vec->is_contiguous() && ref_vec->dim() == 3 &&
+                    ref_vec->size(0) == batch && ref_vec->size(1) == C, "audio_amd: the reference vector must be (batch, C) complex");
+    same_device(a, *ref_vec);
+    u = ref_vec->data_ptr();
+  }
+  const torch::stable::accelerator::DeviceGuard guard(a.get_device_index());
+  Tensor out = mode == AAMD_BF_SOLVE ? torch::stable::new_empty(a, {bins, C, K, 2}) : torch::stable::new_empty(a, {bins, C, 2});
+  if (out.numel() == 0) return out;
+  check(aamd_beamform_weights(dtype, (int32_t)mode, a.data_ptr(), b.data_ptr(), u, out.data_ptr(), batch, freq, (int32_t)C,
+                              (int32_t)K, (int32_t)reference, loading ? 1 : 0, diag_eps, eps, (int32_t)n_iter, adjoint ? 1 : 0,
+                              current_stream(a)));
+  return out;
+}
+// out: the real view of (B, T, F) when frame_major (the caller transposes it back), of (B, F, T) otherwise
+Tensor beamform_apply(Tensor w, Tensor x, bool frame_major) {
+  const int32_t dtype = bf_dtype(x, "specgram");
+  int64_t sx[4];
+  bf_spec(x, sx);
+  const int64_t B = x.size(0), C = x.size(1), F = x.size(2), T = x.size(3);
+  STD_TORCH_CHECK(bf_dtype(w, "beamform_weights") == dtype && w.is_contiguous() && w.dim() == 4 && w.size(0) == B &&
+                  w.size(1) == F && w.size(2) == C, "audio_amd: beamform_weights must be a contiguous (batch, freq, channel) complex tensor");
+  same_device(x, w);
+  const torch::stable::accelerator::DeviceGuard guard(x.get_device_index());
+  Tensor out = frame_major ? torch::stable::new_empty(x, {B, T, F, 2}) : torch::stable::new_empty(x, {B, F, T, 2});
+  if (out.numel() == 0) return out;
+  const int64_t so[3] = {F * T, frame_major ? 1 : T, frame_major ? F : 1};
+  check(aamd_beamform_apply(dtype, w.data_ptr(), x.data_ptr(), B, C, F, T, sx[0], sx[1], sx[2], sx[3], out.data_ptr(), so,
+                            current_stream(x)));
+  return out;
+}
+
 // ---- torchaudio::_lfilter_core_loop on the CUDA key (lfilter.cpp:118-134, iir_cuda.cu:37-79) ------------------------
 //   padded_out[n][c][i + n_order - 1] = in[n][c][i] - sum_{j < n_order-1} a_flipped[c][j] * padded_out[n][c][i + j]
 // = the pure recursion y = IIR(in; a) with a = flip(a_flipped), b = (1, 0, ...), no clamp: aamd_lfilter_f32 runs it as a
@@ -1041,6 +1134,10 @@ STABLE_TORCH_LIBRARY(aamd, m) {
   m.def("add_noise(Tensor waveform, Tensor noise, Tensor snr, Tensor? lengths, Tensor workspace) -> Tensor");
   m.def("add_noise_grad(Tensor cotangent, Tensor waveform, Tensor noise, Tensor snr, Tensor? lengths, Tensor workspace) -> Tensor");
   m.def("preemphasis(Tensor waveform, float coeff, bool transposed) -> Tensor");
+  m.def("beamform_psd(Tensor specgram, Tensor? mask1, Tensor? mask2, bool normalize, float eps) -> Tensor");
+  m.def("beamform_weights(int mode, Tensor a, Tensor b, Tensor? reference_vector, int batch, int freq, int reference, "
+        "bool loading, float diag_eps, float eps, int n_iter, bool adjoint) -> Tensor");
+  m.def("beamform_apply(Tensor weights, Tensor specgram, bool frame_major) -> Tensor");
 }
 
 STABLE_TORCH_LIBRARY_IMPL(aamd, CUDA, m) {
@@ -1079,6 +1176,9 @@ STABLE_TORCH_LIBRARY_IMPL(aamd, CUDA, m) {
   m.impl("add_noise", TORCH_BOX(&add_noise));
   m.impl("add_noise_grad", TORCH_BOX(&add_noise_grad));
   m.impl("preemphasis", TORCH_BOX(&preemphasis));
+  m.impl("beamform_psd", TORCH_BOX(&beamform_psd));
+  m.impl("beamform_weights", TORCH_BOX(&beamform_weights));
+  m.impl("beamform_apply", TORCH_BOX(&beamform_apply));
 }
 
 // The reference's op.  libtorchaudio (when present) has already run

@@ -33,6 +33,7 @@ __all__ = [
     "bandreject_biquad", "equalizer_biquad", "band_biquad", "treble_biquad", "bass_biquad", "deemph_biquad", "riaa_biquad",
     "compute_deltas", "sliding_window_cmn", "detect_pitch_frequency", "mask_along_axis", "mask_along_axis_iid",
     "add_noise", "preemphasis", "deemphasis", "convolve",
+    "psd", "mvdr_weights_souden", "mvdr_weights_rtf", "rtf_power", "rtf_evd", "apply_beamforming",
 ]
 
 # --------------------------------------------------------------------------- #
@@ -2887,6 +2888,328 @@ def _deemphasis_eager(waveform: Tensor, coeff: float = 0.97) -> Tensor:
     return lfilter(waveform, coef[:2], coef[2:])
 
 
+# --------------------------------------------------------------------------- #
+# MVDR beamforming (csrc/beamform.h)                                          #
+# --------------------------------------------------------------------------- #
+
+BEAMFORM_MAX_CHANNELS = 16      # bf::kMaxC
+_BF_DTYPES = {torch.complex64: 0, torch.complex128: 1}
+_BF_REAL = {torch.complex64: torch.float32, torch.complex128: torch.float64}
+_BF_SOLVE, _BF_SOUDEN, _BF_RTF, _BF_RTF_POWER = 0, 1, 2, 3
+
+
+def beamform_tiles() -> Tuple[int, int]:
+    """(frequencies per workgroup, largest time chunk) of the PSD kernel (bf::kFT, bf::kTCMax)."""
+    lib = _lib.lib()
+    return int(lib.aamd_beamform_freq_tile()), int(lib.aamd_beamform_time_chunk())
+
+
+def _bf_require(t: Tensor, what: str) -> None:
+    if t.dtype not in _BF_DTYPES:
+        raise TypeError(f"audio_amd: {what} must be complex64 or complex128 (got {t.dtype})")
+    if not t.is_cuda:
+        raise RuntimeError(f"audio_amd: {what} must be on an MI355X (ROCm) device, got {t.device}. "
+                           "The HIP kernels have no CPU fallback.")
+
+
+def _bf_channels(c: int) -> None:
+    if c > BEAMFORM_MAX_CHANNELS:
+        raise NotImplementedError(f"audio_amd: beamforming kernels take up to {BEAMFORM_MAX_CHANNELS} channels (got {c})")
+
+
+def _bf_wants_grad(*tensors) -> bool:
+    return torch.is_grad_enabled() and any(isinstance(t, Tensor) and t.requires_grad for t in tensors)
+
+
+def _bf_frame_major(x4: Tensor) -> bool:
+    """The unit-stride axis of a (B, C, F, T) view the kernels accept: True = freq (bf_view of csrc/c_api.hip)."""
+    F_, T_ = x4.shape[2], x4.shape[3]
+    sf, st = (x4.stride(2) if F_ > 1 else 1), (x4.stride(3) if T_ > 1 else 1)
+    return False if st == 1 else (True if sf == 1 else T_ > 1)
+
+
+def _bf_spec(specgram: Tensor):
+    """(..., C, F, T) -> (leading shape, (B, C, F, T) view).  Unit stride along freq (the frame-major view that
+    Spectrogram(power=None) returns) or along time is read in place; anything else is gathered into a contiguous tensor."""
+    lead = tuple(specgram.shape[:-3])
+    x4 = specgram.detach().resolve_conj().reshape((-1,) + tuple(specgram.shape[-3:]))
+    F_, T_ = x4.shape[2], x4.shape[3]
+    if not (T_ <= 1 or F_ <= 1 or x4.stride(3) == 1 or x4.stride(2) == 1):
+        x4 = x4.contiguous()
+    return lead, x4
+
+
+def _bf_strides(t: Tensor):
+    return (C.c_int64 * t.dim())(*[t.stride(d) if t.shape[d] > 1 else 0 for d in range(t.dim())])
+
+
+def _bf_spec_strides(x4: Tensor):
+    return [x4.stride(d) if x4.shape[d] > 1 else (1 if d == 3 else 0) for d in range(4)]
+
+
+def _bf_mask3(mask: Tensor, x4: Tensor) -> Tensor:
+    return mask.detach().to(_BF_REAL[x4.dtype]).reshape(x4.shape[0], x4.shape[2], x4.shape[3])
+
+
+def _bf_psd_launch(x4: Tensor, m1: Optional[Tensor], m2: Optional[Tensor], normalize: bool, eps: float) -> Tensor:
+    """(B, C, F, T) and none, one or two (B, F, T) masks -> (n, B, F, C, C), one launch."""
+    B, Cc, F_, T_ = x4.shape
+    n = 2 if m2 is not None else 1
+    ops = _ops()
+    if ops is not None:
+        return torch.view_as_complex(ops.beamform_psd(torch.view_as_real(x4), m1, m2, bool(normalize), float(eps)))
+    out = torch.empty((n, B, F_, Cc, Cc), dtype=x4.dtype, device=x4.device)
+    if out.numel() == 0:
+        return out
+    if T_ == 0:
+        return out.zero_()
+    lib = _lib.lib()
+    with torch.cuda.device(x4.device):
+        _lib.check(lib.aamd_beamform_psd(_BF_DTYPES[x4.dtype], _lib.ptr(x4), B, Cc, F_, T_, *_bf_spec_strides(x4),
+                                         _lib.ptr(m1) if m1 is not None else None, _bf_strides(m1) if m1 is not None else None,
+                                         _lib.ptr(m2) if m2 is not None else None, _bf_strides(m2) if m2 is not None else None,
+                                         int(bool(normalize)), float(eps), out.data_ptr(), _lib.current_stream(x4.device)))
+    return out
+
+
+def _bf_weights_launch(mode: int, a3: Tensor, b: Tensor, u2: Optional[Tensor], batch: int, freq: int, ref: int, loading: bool,
+                       diag_eps: float, eps: float, n_iter: int = 0, adjoint: bool = False) -> Tensor:
+    """The per-bin solve: a3 (bins, C, C), b (bins, C, K) or (bins, C), u2 (batch, C) or None -> (bins, C, K) or (bins, C)."""
+    ops = _ops()
+    if ops is not None:
+        return torch.view_as_complex(ops.beamform_weights(mode, torch.view_as_real(a3), torch.view_as_real(b),
+                                                          torch.view_as_real(u2) if u2 is not None else None, batch, freq, ref,
+                                                          bool(loading), float(diag_eps), float(eps), n_iter, adjoint))
+    bins, Cc = a3.shape[0], a3.shape[1]
+    K = 1 if mode == _BF_RTF else b.shape[2]
+    out = torch.empty(tuple(b.shape) if mode == _BF_SOLVE else (bins, Cc), dtype=a3.dtype, device=a3.device)
+    if out.numel() == 0:
+        return out
+    lib = _lib.lib()
+    with torch.cuda.device(a3.device):
+        _lib.check(lib.aamd_beamform_weights(_BF_DTYPES[a3.dtype], mode, _lib.ptr(a3), _lib.ptr(b),
+                                             _lib.ptr(u2) if u2 is not None else None, out.data_ptr(), batch, freq, Cc, K, ref,
+                                             int(bool(loading)), float(diag_eps), float(eps), n_iter, int(adjoint),
+                                             _lib.current_stream(a3.device)))
+    return out
+
+
+def _bf_apply_launch(w3: Tensor, x4: Tensor) -> Tensor:
+    """(B, F, C) weights and a (B, C, F, T) view -> (B, F, T) in the input's (freq, time) stride order, one launch."""
+    B, Cc, F_, T_ = x4.shape
+    fm = _bf_frame_major(x4)
+    ops = _ops()
+    if ops is not None:
+        out = torch.view_as_complex(ops.beamform_apply(torch.view_as_real(w3), torch.view_as_real(x4), fm))
+        return out.transpose(1, 2) if fm else out
+    out = torch.empty((B, T_, F_) if fm else (B, F_, T_), dtype=x4.dtype, device=x4.device)
+    res = out.transpose(1, 2) if fm else out
+    if out.numel() == 0:
+        return res
+    lib = _lib.lib()
+    so = (C.c_int64 * 3)(F_ * T_, 1 if fm else T_, F_ if fm else 1)
+    with torch.cuda.device(x4.device):
+        _lib.check(lib.aamd_beamform_apply(_BF_DTYPES[x4.dtype], _lib.ptr(w3), _lib.ptr(x4), B, Cc, F_, T_, *_bf_spec_strides(x4),
+                                           out.data_ptr(), so, _lib.current_stream(x4.device)))
+    return res
+
+
+def _bf_check_mask(specgram: Tensor, mask: Tensor, what: str = "mask") -> None:
+    want = tuple(specgram.shape[:-3]) + tuple(specgram.shape[-2:])
+    if tuple(mask.shape) != want:
+        raise ValueError(f"The shape of {what} must be the specgram's without the channel dimension: expected {want}, "
+                         f"got {tuple(mask.shape)}.")
+    if mask.is_complex():
+        raise TypeError(f"audio_amd: {what} must be a real tensor (got {mask.dtype})")
+    if mask.device != specgram.device:
+        raise RuntimeError(f"audio_amd: {what} must be on the specgram's device")
+
+
+def _psd_pair_eager(specgram: Tensor, mask_s: Tensor, mask_n: Tensor, normalize: bool = True, eps: float = 1e-10) -> Tensor:
+    """Both PSD matrices of T.MVDR, stacked as (2, ..., freq, ch, ch): one launch reads the spectrogram once."""
+    if specgram.dim() < 3:
+        raise ValueError(f"Expected at least 3D tensor (..., channel, freq, time). Found: {tuple(specgram.shape)}")
+    _bf_check_mask(specgram, mask_s, "mask_s")
+    _bf_check_mask(specgram, mask_n, "mask_n")
+    _bf_channels(specgram.shape[-3])
+    _bf_require(specgram, "specgram")
+    if _bf_wants_grad(specgram, mask_s, mask_n):
+        return torch.stack([_diff.bf_psd(specgram, mask_s, normalize, eps), _diff.bf_psd(specgram, mask_n, normalize, eps)])
+    lead, x4 = _bf_spec(specgram)
+    out = _bf_psd_launch(x4, _bf_mask3(mask_s, x4), _bf_mask3(mask_n, x4), normalize, eps)
+    return out.view((2,) + lead + tuple(out.shape[2:]))
+
+
+def _psd_eager(specgram: Tensor, mask: Optional[Tensor] = None, normalize: bool = True, eps: float = 1e-10) -> Tensor:
+    r"""Power spectral density matrix of a multi-channel complex spectrogram ``(..., ch, freq, time)`` (reference: F.psd):
+    ``psd[f] = sum_t m'[f, t] x[:, f, t] x[:, f, t]^H`` with ``m' = mask / (mask.sum(time) + eps)`` when ``normalize``,
+    the plain sum without a mask.  One launch and one pass, no ``(..., time, ch, ch)`` temporary; float64 sums in a fixed
+    order, so two calls give the same bits; the result ``(..., freq, ch, ch)`` is exactly Hermitian."""
+    if specgram.dim() < 3:
+        raise ValueError(f"Expected at least 3D tensor (..., channel, freq, time). Found: {tuple(specgram.shape)}")
+    if mask is not None:
+        _bf_check_mask(specgram, mask)
+    _bf_channels(specgram.shape[-3])
+    _bf_require(specgram, "specgram")
+    if _bf_wants_grad(specgram, mask):
+        return _diff.bf_psd(specgram, mask, normalize, eps)
+    lead, x4 = _bf_spec(specgram)
+    out = _bf_psd_launch(x4, _bf_mask3(mask, x4) if mask is not None else None, None, normalize, eps)
+    return out.view(lead + tuple(out.shape[2:]))
+
+
+def _assert_psd_matrices(psd_s: Tensor, psd_n: Tensor) -> None:
+    if psd_s.ndim < 3 or psd_n.ndim < 3:
+        raise ValueError("Expected at least 3D Tensor (..., channel, channel) for psd_s and psd_n. "
+                         f"Found {tuple(psd_s.shape)} for psd_s and {tuple(psd_n.shape)} for psd_n.")
+    if not (psd_s.is_complex() and psd_n.is_complex()):
+        raise TypeError("The type of psd_s and psd_n must be ``torch.cfloat`` or ``torch.cdouble``. "
+                        f"Found {psd_s.dtype} for psd_s and {psd_n.dtype} for psd_n.")
+    if psd_s.shape != psd_n.shape:
+        raise ValueError(f"The dimensions of psd_s and psd_n should be the same. Found {tuple(psd_s.shape)} and {tuple(psd_n.shape)}.")
+    if psd_s.shape[-1] != psd_s.shape[-2]:
+        raise ValueError(f"The last two dimensions of psd_s should be the same. Found {tuple(psd_s.shape)}.")
+
+
+def _bf_reference(reference_channel, psd: Tensor, optional: bool = False):
+    """(index or -1, (batch, C) complex tensor or None) of an int / Tensor reference for PSD matrices (..., F, C, C)."""
+    Cc = psd.shape[-1]
+    if reference_channel is None and optional:
+        return -1, None
+    if isinstance(reference_channel, Tensor):
+        lead = tuple(psd.shape[:-3])
+        if tuple(reference_channel.shape) != lead + (Cc,):
+            raise ValueError(f"Expected a reference vector of shape {lead + (Cc,)}, got {tuple(reference_channel.shape)}.")
+        if reference_channel.device != psd.device:
+            raise RuntimeError("audio_amd: reference_channel must be on the PSD matrices' device")
+        return -1, reference_channel.detach().to(psd.dtype).reshape(-1, Cc).contiguous()
+    if isinstance(reference_channel, int) and not isinstance(reference_channel, bool):
+        if not -Cc <= reference_channel < Cc:
+            raise IndexError(f"reference_channel {reference_channel} is out of range for {Cc} channels")
+        return reference_channel % Cc, None
+    raise RuntimeError(f'Expected "int" or "Tensor" for reference_channel. Found: {type(reference_channel)}.')
+
+
+def _bf_bins(psd: Tensor):
+    """(..., F, C, C) -> (batch, F, contiguous (bins, C, C))."""
+    Cc, F_ = psd.shape[-1], psd.shape[-3]
+    a3 = psd.detach().resolve_conj().reshape(-1, Cc, Cc).contiguous()
+    return a3.shape[0] // F_ if F_ else 0, F_, a3
+
+
+def _mvdr_weights_souden_eager(psd_s: Tensor, psd_n: Tensor, reference_channel, diagonal_loading: bool = True,
+                               diag_eps: float = 1e-7, eps: float = 1e-8) -> Tensor:
+    r"""MVDR weights by Souden's method (reference: F.mvdr_weights_souden): ``W = N / (tr N + eps)`` with
+    ``N = psd_n^-1 psd_s`` (``psd_n`` loaded with ``(Re tr psd_n * diag_eps + 1e-8) I`` first), column ``reference_channel``
+    of it or ``W u`` for a vector.  One launch: an LU solve with partial pivoting per (batch, freq) bin, in float64."""
+    _assert_psd_matrices(psd_s, psd_n)
+    _bf_channels(psd_s.shape[-1])
+    _bf_require(psd_s, "psd_s")
+    _bf_require(psd_n, "psd_n")
+    if psd_s.dtype != psd_n.dtype:
+        raise TypeError(f"audio_amd: psd_s and psd_n must share a dtype (got {psd_s.dtype} and {psd_n.dtype})")
+    ref, u = _bf_reference(reference_channel, psd_n)
+    if _bf_wants_grad(psd_s, psd_n, reference_channel):
+        return _diff.bf_souden(psd_s, psd_n, reference_channel, diagonal_loading, diag_eps, eps)
+    batch, F_, a3 = _bf_bins(psd_n)
+    out = _bf_weights_launch(_BF_SOUDEN, a3, _bf_bins(psd_s)[2], u, batch, F_, ref, diagonal_loading, diag_eps, eps)
+    return out.view(tuple(psd_n.shape[:-1]))
+
+
+def _mvdr_weights_rtf_eager(rtf: Tensor, psd_n: Tensor, reference_channel=None, diagonal_loading: bool = True,
+                            diag_eps: float = 1e-7, eps: float = 1e-8) -> Tensor:
+    r"""MVDR weights from a relative transfer function (reference: F.mvdr_weights_rtf): ``w = n / (Re(r^H n) + eps)`` with
+    ``n = psd_n^-1 r``, times ``conj(r[ref])`` (or ``sum_c conj(r_c) u_c``) when a reference is given.  One launch."""
+    if rtf.ndim < 2:
+        raise ValueError(f"Expected at least 2D Tensor (..., freq, channel) for rtf. Found {tuple(rtf.shape)}.")
+    if psd_n.ndim < 3:
+        raise ValueError(f"Expected at least 3D Tensor (..., freq, channel, channel) for psd_n. Found {tuple(psd_n.shape)}.")
+    if not (rtf.is_complex() and psd_n.is_complex()):
+        raise TypeError("The type of rtf and psd_n must be ``torch.cfloat`` or ``torch.cdouble``. "
+                        f"Found {rtf.dtype} for rtf and {psd_n.dtype} for psd_n.")
+    if rtf.shape != psd_n.shape[:-1]:
+        raise ValueError("The dimensions of rtf and the dimensions without the last dimension of psd_n should be the same. "
+                         f"Found {tuple(rtf.shape)} for rtf and {tuple(psd_n.shape)} for psd_n.")
+    if psd_n.shape[-1] != psd_n.shape[-2]:
+        raise ValueError(f"The last two dimensions of psd_n should be the same. Found {tuple(psd_n.shape)}.")
+    _bf_channels(psd_n.shape[-1])
+    _bf_require(rtf, "rtf")
+    _bf_require(psd_n, "psd_n")
+    if rtf.dtype != psd_n.dtype:
+        raise TypeError(f"audio_amd: rtf and psd_n must share a dtype (got {rtf.dtype} and {psd_n.dtype})")
+    ref, u = _bf_reference(reference_channel, psd_n, optional=True)
+    if _bf_wants_grad(rtf, psd_n, reference_channel):
+        return _diff.bf_rtf(rtf, psd_n, reference_channel, diagonal_loading, diag_eps, eps)
+    batch, F_, a3 = _bf_bins(psd_n)
+    r2 = rtf.detach().resolve_conj().reshape(-1, rtf.shape[-1]).contiguous()
+    out = _bf_weights_launch(_BF_RTF, a3, r2, u, batch, F_, ref, diagonal_loading, diag_eps, eps)
+    return out.view(tuple(rtf.shape))
+
+
+def _rtf_power_eager(psd_s: Tensor, psd_n: Tensor, reference_channel, n_iter: int = 3, diagonal_loading: bool = True,
+                     diag_eps: float = 1e-7) -> Tensor:
+    r"""Relative transfer function by the power method (reference: F.rtf_power): ``phi = psd_n^-1 psd_s`` (loaded ``psd_n``),
+    ``r = phi[:, ref]`` (or ``phi u``), ``n_iter - 2`` times ``r <- phi r``, then ``r <- psd_s r``; ``n_iter == 1`` multiplies
+    by the loaded ``psd_n`` instead.  One launch."""
+    _assert_psd_matrices(psd_s, psd_n)
+    if n_iter <= 0:
+        raise ValueError(f"The number of iteration must be greater than 0. Found {n_iter}.")
+    _bf_channels(psd_s.shape[-1])
+    _bf_require(psd_s, "psd_s")
+    _bf_require(psd_n, "psd_n")
+    if psd_s.dtype != psd_n.dtype:
+        raise TypeError(f"audio_amd: psd_s and psd_n must share a dtype (got {psd_s.dtype} and {psd_n.dtype})")
+    ref, u = _bf_reference(reference_channel, psd_n)
+    if _bf_wants_grad(psd_s, psd_n, reference_channel):
+        return _diff.bf_rtf_power(psd_s, psd_n, reference_channel, n_iter, diagonal_loading, diag_eps)
+    batch, F_, a3 = _bf_bins(psd_n)
+    out = _bf_weights_launch(_BF_RTF_POWER, a3, _bf_bins(psd_s)[2], u, batch, F_, ref, diagonal_loading, diag_eps, 0.0, int(n_iter))
+    return out.view(tuple(psd_n.shape[:-1]))
+
+
+def _apply_beamforming_eager(beamform_weights: Tensor, specgram: Tensor) -> Tensor:
+    r"""``y[f, t] = sum_c conj(w[f, c]) x[c, f, t]`` (reference: F.apply_beamforming): weights ``(..., freq, ch)``, spectrogram
+    ``(..., ch, freq, time)``, result ``(..., freq, time)`` in the spectrogram's (freq, time) stride order -- a frame-major
+    input gives a frame-major output, which ``InverseSpectrogram`` takes as it is.  One streaming launch."""
+    if specgram.dim() < 3:
+        raise ValueError(f"Expected at least 3D tensor (..., channel, freq, time). Found: {tuple(specgram.shape)}")
+    if beamform_weights.shape[:-2] != specgram.shape[:-3]:
+        raise ValueError("The dimensions except the last two dimensions of beamform_weights should be the same as the "
+                         f"dimensions except the last three dimensions of specgram. Found {tuple(beamform_weights.shape)} for "
+                         f"beamform_weights and {tuple(specgram.shape)} for specgram.")
+    if beamform_weights.shape[-2:] != (specgram.shape[-2], specgram.shape[-3]):
+        raise ValueError(f"Expected beamform_weights (..., freq, channel) = {(specgram.shape[-2], specgram.shape[-3])}, "
+                         f"got {tuple(beamform_weights.shape[-2:])}.")
+    if not (beamform_weights.is_complex() and specgram.is_complex()):
+        raise TypeError("The type of beamform_weights and specgram must be ``torch.cfloat`` or ``torch.cdouble``. "
+                        f"Found {beamform_weights.dtype} for beamform_weights and {specgram.dtype} for specgram.")
+    _bf_channels(specgram.shape[-3])
+    _bf_require(beamform_weights, "beamform_weights")
+    _bf_require(specgram, "specgram")
+    if beamform_weights.dtype != specgram.dtype:
+        raise TypeError(f"audio_amd: beamform_weights and specgram must share a dtype (got {beamform_weights.dtype} and "
+                        f"{specgram.dtype})")
+    if _bf_wants_grad(beamform_weights, specgram):
+        return _diff.bf_apply(beamform_weights, specgram)
+    lead, x4 = _bf_spec(specgram)
+    w3 = beamform_weights.detach().resolve_conj().reshape((-1,) + tuple(beamform_weights.shape[-2:])).contiguous()
+    out = _bf_apply_launch(w3, x4)
+    if len(lead) == 1:
+        return out
+    if not lead:
+        return out[0]
+    fm = out.stride(1) == 1 and out.shape[1] > 1
+    if fm:
+        return out.transpose(1, 2).reshape(lead + (out.shape[2], out.shape[1])).transpose(-1, -2)
+    return out.reshape(lead + tuple(out.shape[1:]))
+
+
+def rtf_evd(psd_s: Tensor) -> Tensor:
+    r"""Not part of this package yet: the eigenvalue-decomposition RTF needs a Hermitian eigen-solver kernel."""
+    raise NotImplementedError("audio_amd: rtf_evd is not implemented: it needs a Hermitian eigen-solver kernel, which this "
+                              "package does not have yet; use rtf_power")
+
+
 @_reduced_precision_io
 def _convolve_eager(x: Tensor, y: Tensor, mode: str = "full") -> Tensor:
     r"""Linear convolution along the last dim with broadcast leading dims and the reference's full / valid / same crops
@@ -3297,3 +3620,65 @@ def convolve(x: Tensor, y: Tensor, mode: str = "full") -> Tensor:
         if not torch.compiler.is_compiling():
             return _convolve_eager(x, y, mode)
     return torch.ops.audio_amd.convolve(x, y, mode)
+
+
+def psd(specgram: Tensor, mask: Optional[Tensor] = None, normalize: bool = True, eps: float = 1e-10) -> Tensor:
+    r"""Power spectral density matrix of ``(..., ch, freq, time)`` (reference: F.psd); see ``_psd_eager``."""
+    if not torch.jit.is_scripting():
+        if not torch.compiler.is_compiling():
+            return _psd_eager(specgram, mask, normalize, eps)
+    return torch.ops.audio_amd.psd(specgram, mask, normalize, eps)
+
+
+def _psd_pair(specgram: Tensor, mask_s: Tensor, mask_n: Tensor, normalize: bool = True, eps: float = 1e-10) -> Tensor:
+    if not torch.jit.is_scripting():
+        if not torch.compiler.is_compiling():
+            return _psd_pair_eager(specgram, mask_s, mask_n, normalize, eps)
+    return torch.ops.audio_amd.psd_pair(specgram, mask_s, mask_n, normalize, eps)
+
+
+def mvdr_weights_souden(psd_s: Tensor, psd_n: Tensor, reference_channel: Union[int, Tensor], diagonal_loading: bool = True,
+                        diag_eps: float = 1e-7, eps: float = 1e-8) -> Tensor:
+    r"""MVDR weights by Souden's method (reference: F.mvdr_weights_souden); see ``_mvdr_weights_souden_eager``."""
+    if not torch.jit.is_scripting():
+        if not torch.compiler.is_compiling():
+            return _mvdr_weights_souden_eager(psd_s, psd_n, reference_channel, diagonal_loading, diag_eps, eps)
+    if isinstance(reference_channel, int):
+        return torch.ops.audio_amd.mvdr_weights_souden(psd_s, psd_n, reference_channel, None, diagonal_loading, diag_eps, eps)
+    else:
+        return torch.ops.audio_amd.mvdr_weights_souden(psd_s, psd_n, -1, reference_channel, diagonal_loading, diag_eps, eps)
+
+
+def mvdr_weights_rtf(rtf: Tensor, psd_n: Tensor, reference_channel: Optional[Union[int, Tensor]] = None,
+                     diagonal_loading: bool = True, diag_eps: float = 1e-7, eps: float = 1e-8) -> Tensor:
+    r"""MVDR weights from a relative transfer function (reference: F.mvdr_weights_rtf); see ``_mvdr_weights_rtf_eager``."""
+    if not torch.jit.is_scripting():
+        if not torch.compiler.is_compiling():
+            return _mvdr_weights_rtf_eager(rtf, psd_n, reference_channel, diagonal_loading, diag_eps, eps)
+    if reference_channel is None:
+        return torch.ops.audio_amd.mvdr_weights_rtf(rtf, psd_n, None, None, diagonal_loading, diag_eps, eps)
+    elif isinstance(reference_channel, int):
+        return torch.ops.audio_amd.mvdr_weights_rtf(rtf, psd_n, reference_channel, None, diagonal_loading, diag_eps, eps)
+    else:
+        return torch.ops.audio_amd.mvdr_weights_rtf(rtf, psd_n, None, reference_channel, diagonal_loading, diag_eps, eps)
+
+
+def rtf_power(psd_s: Tensor, psd_n: Tensor, reference_channel: Union[int, Tensor], n_iter: int = 3,
+              diagonal_loading: bool = True, diag_eps: float = 1e-7) -> Tensor:
+    r"""Relative transfer function by the power method (reference: F.rtf_power); see ``_rtf_power_eager``."""
+    if not torch.jit.is_scripting():
+        if not torch.compiler.is_compiling():
+            return _rtf_power_eager(psd_s, psd_n, reference_channel, n_iter, diagonal_loading, diag_eps)
+    if isinstance(reference_channel, int):
+        return torch.ops.audio_amd.rtf_power(psd_s, psd_n, reference_channel, None, n_iter, diagonal_loading, diag_eps)
+    else:
+        return torch.ops.audio_amd.rtf_power(psd_s, psd_n, -1, reference_channel, n_iter, diagonal_loading, diag_eps)
+
+
+def apply_beamforming(beamform_weights: Tensor, specgram: Tensor) -> Tensor:
+    r"""Apply beamforming weights to a multi-channel spectrogram (reference: F.apply_beamforming); see
+    ``_apply_beamforming_eager``."""
+    if not torch.jit.is_scripting():
+        if not torch.compiler.is_compiling():
+            return _apply_beamforming_eager(beamform_weights, specgram)
+    return torch.ops.audio_amd.apply_beamforming(beamform_weights, specgram)

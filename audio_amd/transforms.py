@@ -1,6 +1,6 @@
 """Drop-in replacements for the hot-path modules of ``torchaudio.transforms``:
 Spectrogram, MelScale, MelSpectrogram, AmplitudeToDB, MFCC, Resample, FFTConvolve, ComputeDeltas, SlidingWindowCmn,
-FrequencyMasking, TimeMasking, SpecAugment, AddNoise, Preemphasis, Deemphasis, Convolve.
+FrequencyMasking, TimeMasking, SpecAugment, AddNoise, Preemphasis, Deemphasis, Convolve, PSD, MVDR, SoudenMVDR, RTFMVDR.
 
 Constructor / forward signatures, registered buffer names (``window``, ``fb``, ``dct_mat``,
 ``kernel``), shapes, strides, warnings and error messages follow
@@ -34,7 +34,7 @@ _norm_mode = F._norm_mode      # `normalized` as the op schemas' integer: 0 none
 __all__ = ["Spectrogram", "InverseSpectrogram", "GriffinLim", "TimeStretch", "PitchShift", "Speed", "SpeedPerturbation",
            "MelScale", "MelSpectrogram", "AmplitudeToDB", "MFCC", "Resample", "FFTConvolve", "ComputeDeltas",
            "SlidingWindowCmn", "FrequencyMasking", "TimeMasking", "SpecAugment", "AddNoise", "Preemphasis", "Deemphasis",
-           "Convolve"]
+           "Convolve", "PSD", "MVDR", "SoudenMVDR", "RTFMVDR"]
 
 
 class Spectrogram(torch.nn.Module):
@@ -718,3 +718,90 @@ class Deemphasis(torch.nn.Module):
 
     def forward(self, waveform: Tensor) -> Tensor:
         return F.deemphasis(waveform, coeff=self.coeff)
+
+
+class PSD(torch.nn.Module):
+    r"""Cross-channel power spectral density matrix ``(..., freq, ch, ch)`` of a complex ``(..., ch, freq, time)``
+    spectrogram (reference: T.PSD); one launch (``F.psd``).  A multi-channel mask ``(..., ch, freq, time)`` is averaged over
+    its channels first."""
+
+    def __init__(self, multi_mask: bool = False, normalize: bool = True, eps: float = 1e-15) -> None:
+        super().__init__()
+        self.multi_mask = multi_mask
+        self.normalize = normalize
+        self.eps = eps
+
+    def forward(self, specgram: Tensor, mask: Optional[Tensor] = None) -> Tensor:
+        if mask is not None:
+            if self.multi_mask:
+                mask = mask.mean(dim=-3)
+        return F.psd(specgram, mask, self.normalize, self.eps)
+
+
+class SoudenMVDR(torch.nn.Module):
+    r"""MVDR beamforming by Souden's method from given PSD matrices (reference: T.SoudenMVDR): two launches, the weights
+    (``F.mvdr_weights_souden``) and their application (``F.apply_beamforming``); no buffers."""
+
+    def forward(self, specgram: Tensor, psd_s: Tensor, psd_n: Tensor, reference_channel: Union[int, Tensor],
+                diagonal_loading: bool = True, diag_eps: float = 1e-7, eps: float = 1e-8) -> Tensor:
+        w_mvdr = F.mvdr_weights_souden(psd_s, psd_n, reference_channel, diagonal_loading, diag_eps, eps)
+        return F.apply_beamforming(w_mvdr, specgram)
+
+
+class RTFMVDR(torch.nn.Module):
+    r"""MVDR beamforming from a relative transfer function and the noise PSD (reference: T.RTFMVDR): two launches; no
+    buffers."""
+
+    def forward(self, specgram: Tensor, rtf: Tensor, psd_n: Tensor, reference_channel: Union[int, Tensor],
+                diagonal_loading: bool = True, diag_eps: float = 1e-7, eps: float = 1e-8) -> Tensor:
+        w_mvdr = F.mvdr_weights_rtf(rtf, psd_n, reference_channel, diagonal_loading, diag_eps, eps)
+        return F.apply_beamforming(w_mvdr, specgram)
+
+
+class MVDR(torch.nn.Module):
+    r"""Mask-based MVDR beamformer (reference: T.MVDR): both PSD matrices from one pass over the spectrogram, the weights,
+    the application -- three launches for ``solution="ref_channel"`` (Souden), four for ``"stv_power"`` (``F.rtf_power`` then
+    ``F.mvdr_weights_rtf``).  Computed in complex128, returned in the input's dtype and (freq, time) stride order.
+    ``solution="stv_evd"`` needs a Hermitian eigen-solver and ``online=True`` running state: neither is implemented."""
+
+    def __init__(self, ref_channel: int = 0, solution: str = "ref_channel", multi_mask: bool = False, diag_loading: bool = True,
+                 diag_eps: float = 1e-7, online: bool = False) -> None:
+        super().__init__()
+        if solution not in ["ref_channel", "stv_evd", "stv_power"]:
+            raise ValueError('`solution` must be one of ["ref_channel", "stv_evd", "stv_power"]. Given {}'.format(solution))
+        if solution == "stv_evd":
+            raise NotImplementedError('audio_amd: MVDR(solution="stv_evd") is not implemented: it needs a Hermitian '
+                                      'eigen-solver kernel; use "stv_power" or "ref_channel"')
+        if online:
+            raise NotImplementedError("audio_amd: MVDR(online=True) is not implemented: the recursive update of the PSD "
+                                      "matrices needs running state this package does not keep")
+        self.ref_channel = ref_channel
+        self.solution = solution
+        self.multi_mask = multi_mask
+        self.diag_loading = diag_loading
+        self.diag_eps = diag_eps
+        self.online = online
+
+    def forward(self, specgram: Tensor, mask_s: Tensor, mask_n: Optional[Tensor] = None) -> Tensor:
+        dtype = specgram.dtype
+        if specgram.ndim < 3:
+            raise ValueError(f"Expected at least 3D tensor (..., channel, freq, time). Found: {specgram.shape}")
+        if not specgram.is_complex():
+            raise ValueError(f"The type of ``specgram`` tensor must be ``torch.cfloat`` or ``torch.cdouble``. Found: {specgram.dtype}")
+        if specgram.dtype == torch.cfloat:
+            specgram = specgram.cdouble()          # Convert specgram to ``torch.cdouble``.
+        if mask_n is None:
+            warnings.warn("``mask_n`` is not provided, use ``1 - mask_s`` as ``mask_n``.")
+            mask_n = 1 - mask_s
+        if self.multi_mask:
+            mask_s = mask_s.mean(dim=-3)
+            mask_n = mask_n.mean(dim=-3)
+        both = F._psd_pair(specgram, mask_s.to(torch.float64), mask_n.to(torch.float64), True, 1e-15)
+        psd_s, psd_n = both[0], both[1]
+        if self.solution == "ref_channel":
+            w_mvdr = F.mvdr_weights_souden(psd_s, psd_n, self.ref_channel, self.diag_loading, self.diag_eps, 1e-8)
+        else:
+            stv = F.rtf_power(psd_s, psd_n, self.ref_channel, 3, self.diag_loading, self.diag_eps)
+            w_mvdr = F.mvdr_weights_rtf(stv, psd_n, self.ref_channel, self.diag_loading, self.diag_eps, 1e-8)
+        return F.apply_beamforming(w_mvdr, specgram).to(dtype)
+

@@ -50,6 +50,9 @@
  *                             -- additions to ABI 7 as well
  *   aamd_add_noise_f32        F.add_noise / T.AddNoise (two masks, two norms, logs, a power, a multiply and an add in the
  *   aamd_preemphasis_f32      reference); F.preemphasis / T.Preemphasis -- additions to ABI 7 as well
+ *   aamd_beamform_psd         F.psd / T.PSD, the weight solves and F.apply_beamforming / T.MVDR (einsum + linalg.solve
+ *   aamd_beamform_weights     compositions over a (..., freq, time, ch, ch) temporary in the reference) -- additions to
+ *   aamd_beamform_apply       ABI 7 as well
  *   aamd_detect_pitch_f32     F.detect_pitch_frequency (_compute_nccf + _find_max_per_frame + _median_smoothing in the
  *                             reference; an addition to ABI 7 as well)
  *
@@ -614,6 +617,46 @@ int aamd_preemphasis_f64(const double* x, double* out, int64_t rows, int64_t len
                          int32_t transposed, void* stream);
 int aamd_preemphasis_lp(const void* x, void* out, int64_t rows, int64_t length, int64_t stride_row, double coeff, int32_t dtype,
                         int32_t transposed, void* stream);
+
+/* ---- MVDR beamforming (additions to ABI 7; csrc/beamform.h) ------------------------------------------------------------ */
+
+enum { AAMD_BF_C64 = 0, AAMD_BF_C128 = 1 };
+enum { AAMD_BF_SOLVE = 0, AAMD_BF_SOUDEN = 1, AAMD_BF_RTF = 2, AAMD_BF_RTF_POWER = 3 };
+#define AAMD_BF_MAX_CHANNELS 16
+
+/* Frequencies per workgroup of the PSD kernel, and its largest time chunk (frames staged at a time; complex128 uses half). */
+int32_t aamd_beamform_freq_tile(void);
+int32_t aamd_beamform_time_chunk(void);
+
+/* F.psd / T.PSD: out[n][b][f] = sum_t m'_n[b][f][t] x[b][:, f, t] x[b][:, f, t]^H for n < n_masks (or one unweighted sum when
+ * mask1 is NULL), m' = m / (sum_t m + eps) when `normalize`.  x is (batch, channels, freq, time) complex (interleaved re, im)
+ * read through strides counted in complex elements; stride_f == 1 (frame-major) or stride_t == 1 is read coalesced, anything
+ * else is the caller's to gather first (AAMD_EINVAL).  Masks are real (batch, freq, time) of the matching precision, any
+ * non-negative strides (in elements), two of them give both matrices from one pass.  out is dense
+ * (n, batch, freq, channels, channels), exactly Hermitian.  One launch, float64 sums in a fixed order, no atomics. */
+int aamd_beamform_psd(int32_t dtype, const void* x, int64_t batch, int64_t channels, int64_t freq, int64_t time,
+                      int64_t stride_b, int64_t stride_c, int64_t stride_f, int64_t stride_t, const void* mask1,
+                      const int64_t* mask1_strides, const void* mask2, const int64_t* mask2_strides, int32_t normalize,
+                      double eps, void* out, void* stream);
+
+/* The per-bin small solve behind F.mvdr_weights_souden, F.mvdr_weights_rtf and F.rtf_power: one launch, LU with partial
+ * pivoting in float64, bins = batch * freq.  a is (bins, C, C) dense; with `loading`, a + (Re tr a * diag_eps + 1e-8) I is
+ * used wherever a is.  `reference` >= 0 selects a channel; otherwise reference_vector (batch, C) complex is used (both absent:
+ * AAMD_BF_RTF without a reference).
+ *   AAMD_BF_SOLVE      b (bins, C, K), K <= C: out (bins, C, K) = a^-1 b; adjoint = 1 inverts a^H instead
+ *   AAMD_BF_SOUDEN     b (bins, C, C): N = a^-1 b, out (bins, C) = N[:, ref] / (tr N + eps)   (or N u / ...)
+ *   AAMD_BF_RTF        b (bins, C) = r: n = a^-1 r, out = n / (Re(r^H n) + eps) [* conj(r[ref]) or sum_c conj(r_c) u_c]
+ *   AAMD_BF_RTF_POWER  b (bins, C, C): phi = a^-1 b, r = phi[:, ref] (or phi u), n_iter - 2 times r <- phi r, then
+ *                      r <- b r (n_iter >= 2) or r <- a r (n_iter == 1); out (bins, C) = r */
+int aamd_beamform_weights(int32_t dtype, int32_t mode, const void* a, const void* b, const void* reference_vector, void* out,
+                          int64_t batch, int64_t freq, int32_t channels, int32_t rhs, int32_t reference, int32_t loading,
+                          double diag_eps, double eps, int32_t n_iter, int32_t adjoint, void* stream);
+
+/* F.apply_beamforming: out[b][f][t] = sum_c conj(w[b][f][c]) x[b][c][f][t].  w dense (batch, freq, channels); x as for
+ * aamd_beamform_psd; out (batch, freq, time) through out_strides (complex elements), unit stride along the same axis as x. */
+int aamd_beamform_apply(int32_t dtype, const void* w, const void* x, int64_t batch, int64_t channels, int64_t freq,
+                        int64_t time, int64_t stride_b, int64_t stride_c, int64_t stride_f, int64_t stride_t, void* out,
+                        const int64_t* out_strides, void* stream);
 
 #ifdef __cplusplus
 }
