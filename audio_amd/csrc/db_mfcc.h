@@ -7,15 +7,19 @@
 
 namespace aamd {
 
+// torch.clamp(x, min=amin) and torch.max(y, cut) keep a NaN operand; fmax() returns the other one, so neither is an fmax
 AAMD_HD float to_db(float x, float multiplier, float amin, float db_multiplier) {
-  return multiplier * log10(fmax(x, amin)) - multiplier * db_multiplier;
+  const float c = x < amin ? amin : x;
+  return multiplier * log10(c) - multiplier * db_multiplier;
 }
+
+AAMD_HD float db_floor(float y, float cut) { return y < cut ? cut : y; }
 
 // y for one mel value under the three MFCC log modes (see audio_amd.h)
 AAMD_HD float mfcc_log(float v, int log_mode, float cut) {
   if (log_mode == 1) return log(v + 1e-6f);
   float y = (log_mode == 0) ? to_db(v, 10.0f, 1e-10f, 0.0f) : v;
-  return fmax(y, cut);
+  return db_floor(y, cut);
 }
 
 // fragment geometry of the matrix-core DCT kernel below (shared with tests/cpu_sim)
@@ -86,12 +90,13 @@ db_clamp_kernel(const float* __restrict__ x, float* __restrict__ out, int64_t n,
                 const float* __restrict__ group_max, int64_t group_size, float top_db) {
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride)
-    out[i] = fmaxf(x[i], group_max[i / group_size] - top_db);
+    out[i] = db_floor(x[i], group_max[i / group_size] - top_db);
 }
 
 // amplitude_to_DB, second version: one workgroup = one chunk of ONE cut-off group, so there is no per-element 64-bit
 // division, the body moves 16 bytes per lane, and the group maximum costs one atomic per workgroup.
 //   STORE  write the dB values;  REDUCE  max-reduce them into group_max[g];  CLAMP  y = max(y, group_max[g] - top_db)
+// A NaN element comes out NaN (to_db, db_floor); the group maximum is taken over the group's other elements (fmaxf).
 // (REDUCE without STORE = the first pass of a top_db conversion: it reads x once and writes nothing; the second pass
 // recomputes the logarithm, clamps and stores -- 3 instead of 4 sweeps over the tensor.)
 constexpr int kDbChunk = 8192;
@@ -111,7 +116,7 @@ db_group_kernel(const float* __restrict__ x, float* __restrict__ out, int64_t n,
   auto one = [&](int64_t i) {
     float v = to_db(x[i], multiplier, amin, db_multiplier);
     if (REDUCE) run = fmaxf(run, v);
-    if (CLAMP) v = fmaxf(v, cut);
+    if (CLAMP) v = db_floor(v, cut);
     if (STORE) out[i] = v;
   };
   // scalar head up to the next 16-byte boundary of x (out shares the index, hence the alignment, when both bases are
@@ -137,7 +142,7 @@ db_group_kernel(const float* __restrict__ x, float* __restrict__ out, int64_t n,
     y.z = to_db(xv.z, multiplier, amin, db_multiplier);
     y.w = to_db(xv.w, multiplier, amin, db_multiplier);
     if (REDUCE) run = fmaxf(run, fmaxf(fmaxf(y.x, y.y), fmaxf(y.z, y.w)));
-    if (CLAMP) { y.x = fmaxf(y.x, cut); y.y = fmaxf(y.y, cut); y.z = fmaxf(y.z, cut); y.w = fmaxf(y.w, cut); }
+    if (CLAMP) { y.x = db_floor(y.x, cut); y.y = db_floor(y.y, cut); y.z = db_floor(y.z, cut); y.w = db_floor(y.w, cut); }
     if (STORE) ov4[j] = y;
   }
 #pragma clang loop vectorize(disable) unroll(disable)

@@ -345,6 +345,12 @@ int sim_griffinlim_update(const float* rebuilt, float* tprev, const float* mag, 
   return 0;
 }
 
+// db_group_kernel's per-element arithmetic: y = db_floor(to_db(x), cut) (cut = -inf: no top_db)
+int sim_db_values(const float* x, float* out, int64_t n, float multiplier, float amin, float db_multiplier, float cut) {
+  for (int64_t i = 0; i < n; ++i) out[i] = db_floor(to_db(x[i], multiplier, amin, db_multiplier), cut);
+  return 0;
+}
+
 void sim_trace_writes(const float* base, int32_t* stores, int32_t* adds) {
   g_trace_base = base; g_trace_store = stores; g_trace_add = adds;
 }

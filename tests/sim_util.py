@@ -187,6 +187,16 @@ def sim_mfcc_dct_mfma(mel_fm, dct, log_mode, group_max=None, vec_per_group=1, to
     return out
 
 
+def sim_db_values(x, multiplier, amin, db_multiplier, cut=-np.inf):
+    """to_db + the top_db floor of csrc/db_mfcc.h, element by element."""
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    out = np.zeros_like(x)
+    f = sim().sim_db_values
+    f.argtypes = [C.c_void_p, C.c_void_p, C.c_int64] + [C.c_float] * 4
+    assert f(fptr(x), fptr(out), x.size, multiplier, amin, db_multiplier, cut) == 0
+    return out
+
+
 def sim_resample(x, kernel, orig, new, width, qt=None, use_lds=1):
     x = np.ascontiguousarray(x, dtype=np.float32)
     rows, length = x.shape

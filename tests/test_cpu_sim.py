@@ -338,6 +338,32 @@ def test_sim_mfcc_dct_mfma_fragments(n_mels, n_mfcc, log_mode):
     assert peak_rel_err(got, exp) <= 1e-5
 
 
+def test_sim_db_and_mfcc_log_keep_a_nan():
+    """to_db / db_floor / mfcc_log (csrc/db_mfcc.h, shared with the kernels): a NaN element stays NaN, as torch.clamp(x, min=amin)
+    and torch.max(y, cut) leave it -- fmax() returned the other operand, i.e. amin's -100 dB or the cut-off.  Everything else is
+    the reference formula, the clamp at amin and the top_db floor included."""
+    x = np.array([0.0, -1.0, 1e-40, 1e-10, 3e-3, np.nan, 1.0, 250.0, np.inf], dtype=np.float32)
+    for mult in (10.0, 20.0):
+        for cut in (-np.inf, -20.0, 5.0):
+            got = S.sim_db_values(x, mult, 1e-10, 0.0, cut)
+            exp = np.maximum(mult * np.log10(np.maximum(x.astype(np.float64), 1e-10)), cut)      # numpy's maximum keeps a NaN
+            assert np.isnan(got).tolist() == np.isnan(x).tolist(), (mult, cut, got)
+            np.testing.assert_allclose(got, exp, rtol=0, atol=1e-4, equal_nan=True)
+    rng = np.random.default_rng(7)
+    for n_mels, n_mfcc in ((40, 13), (36, 20)):
+        dct = O.create_dct(n_mfcc, n_mels, "ortho").astype(np.float32)
+        p = (rng.standard_normal((21, n_mels)) ** 2).astype(np.float32)
+        p[4, 9] = np.nan
+        db = 10 * np.log10(np.maximum(p.astype(np.float64), 1e-10))
+        got0 = S.sim_mfcc_dct_mfma(p, dct, 0)                                                   # dB in the tail
+        gmax = np.array([np.nanmax(db)], dtype=np.float32)
+        got2 = S.sim_mfcc_dct_mfma(db.astype(np.float32), dct, 2, gmax, 21, 30.0)                # dB in, top_db floor in the tail
+        got1 = S.sim_mfcc_dct_mfma(p, dct, 1)                                                   # log(mel + 1e-6)
+        for got, y in ((got0, db), (got2, np.maximum(db, gmax[0] - 30.0)), (got1, np.log(p.astype(np.float64) + 1e-6))):
+            assert np.isnan(got[4]).all() and np.isnan(got).sum() == n_mfcc
+            np.testing.assert_allclose(got, y @ dct.astype(np.float64), rtol=0, atol=1e-3, equal_nan=True)
+
+
 def test_sim_resample_mfma_kaiser_best_headline():
     """BASELINE config 3 parameters (44.1k -> 16k kaiser_best: 160 phases x 815 taps, band 417):
     10 phase tiles, KS = 112, one q-group; ragged length so the last chunk / q-tile are partial."""
