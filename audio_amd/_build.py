@@ -1,5 +1,10 @@
 """Build libaudio_amd.so in-tree with hipcc for gfx950:  python -m audio_amd._build [--force] [-v] [--lab]
 
+One object per source of SOURCES (csrc/api_*.hip: one per kernel family), compiled in parallel (MAX_JOBS, else the CPUs, at
+most 16) and linked by one hipcc call.  An object is kept while the SHA-256 of its flags and of the files its dependency
+file (-MD) lists is the one stored beside it, so editing one header recompiles the sources that include it; --force
+recompiles everything.
+
 Staleness is decided by CONTENT, not by modification times (a fresh clone's checkout order must not
 decide whether the library is rebuilt): the SHA-256 of every source under csrc/, of include/audio_amd.h and of the compile
 command is stored beside each library (``<lib>.buildhash``); the library is current when the stored value equals the one
@@ -9,17 +14,20 @@ instantiations and their environment switches (AAMD_LFW_LAB, AAMD_RSM_LAB, AAMD_
 """
 from __future__ import annotations
 
+import concurrent.futures
 import hashlib
 import os
 import shutil
 import subprocess
 import sys
+import time
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "lib", "libaudio_amd.so")
 LAB_OUT = os.path.join(HERE, "lib", "libaudio_amd_lab.so")
-SOURCES = ["c_api.hip"]
+SOURCES = ["api_common.hip", "api_stft.hip", "api_mel400_lowp.hip", "api_istft.hip", "api_kaldi.hip", "api_f64.hip",
+           "api_specdomain.hip", "api_resample.hip", "api_lfilter.hip", "api_fftconv.hip", "api_post.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=fast",
          # packed fp32 VALU ops run at half rate on gfx950 (no gain) and cost v_mov shuffles
          "-fno-slp-vectorize"]
@@ -119,16 +127,62 @@ def stale(lab: bool = False) -> bool:
     return not os.path.exists(out) or _stored(out) != source_digest(lab)
 
 
+def _jobs() -> int:
+    try:
+        n = int(os.environ.get("MAX_JOBS", ""))
+    except ValueError:
+        n = os.cpu_count() or 1
+    return max(1, min(16, n))
+
+
+def _deps(depfile: str):
+    """The files a compiler-written dependency file (-MD -MF) lists, or None when it cannot be read."""
+    try:
+        with open(depfile, encoding="utf-8") as f:
+            words = f.read().replace("\\\n", " ").split()
+    except OSError:
+        return None
+    return [w for w in words[1:] if not w.endswith(":")]
+
+
+def _compile(src: str, obj: str, flags, force: bool, verbose: bool) -> bool:
+    """csrc/<src> -> <obj>, unless the object's stored digest (flags + every file of its dependency file) still holds."""
+    deps = None if force or not os.path.exists(obj) else _deps(obj + ".d")
+    try:
+        if deps and _stored(obj) == _digest(deps, flags):
+            return False
+    except OSError:                                 # a listed file is gone: compile
+        pass
+    tmp, started = obj + _tmp_suffix(), time.time()
+    cmd = [hipcc()] + flags + ["-MD", "-MF", tmp + ".d", "-c", os.path.join(CSRC, src), "-o", tmp]
+    if verbose:
+        cmd.insert(1, "-Rpass-analysis=kernel-resource-usage")
+        print(" ".join(cmd))
+    subprocess.check_call(cmd)
+    deps = _deps(tmp + ".d")
+    os.replace(tmp + ".d", obj + ".d")
+    os.replace(tmp, obj)
+    if all(os.path.getmtime(d) < started for d in deps):
+        _store(obj, _digest(deps, flags))
+    elif os.path.exists(obj + ".buildhash"):        # a file was edited during the compile: no digest, the next build compiles again
+        os.remove(obj + ".buildhash")
+    return True
+
+
 def build(force: bool = False, verbose: bool = False, lab: bool = False) -> str:
     out = LAB_OUT if lab else OUT
     if not force and not stale(lab):
         return out
-    os.makedirs(os.path.dirname(out), exist_ok=True)
+    objdir = os.path.join(os.path.dirname(out), "obj-lab" if lab else "obj")
+    os.makedirs(objdir, exist_ok=True)
     digest = source_digest(lab)                     # of what is compiled now (a source edited during the build shows up next time)
-    cmd = [hipcc()] + FLAGS + (["-DAAMD_LAB"] if lab else []) + _extra_flags() + \
-        [os.path.join(CSRC, s) for s in SOURCES] + ["-o", out + _tmp_suffix()]
+    flags = [f for f in FLAGS if f != "-shared"] + (["-DAAMD_LAB"] if lab else []) + _extra_flags()
+    objs = [os.path.join(objdir, os.path.splitext(s)[0] + ".o") for s in SOURCES]
+    with concurrent.futures.ThreadPoolExecutor(_jobs()) as pool:
+        for f in [pool.submit(_compile, s, o, flags, force, verbose) for s, o in zip(SOURCES, objs)]:
+            f.result()
+    cmd = [hipcc(), "--offload-arch=gfx950", "-shared"] + objs + ["-o", out + _tmp_suffix()]
     if verbose:
-        cmd.insert(1, "-Rpass-analysis=kernel-resource-usage")
         print(" ".join(cmd))
     subprocess.check_call(cmd)
     os.replace(out + _tmp_suffix(), out)

@@ -996,7 +996,7 @@ def _mel_lognorm(waveform: Tensor, window: Tensor, fb: Tensor, n_fft: int, hop_l
                             invstddev, right_padding, bands)
     T = desc.n_frames
     # Rows of T + right_padding frames come straight from the kernel only on the radix-20x20 fast path.  Its
-    # eligibility (csrc/c_api.hip: mel400_eligible -- hop, clip length, filterbank geometry, kernel policy) is mirrored
+    # eligibility (csrc/mel400_launch.h: mel400_eligible -- hop, clip length, filterbank geometry, kernel policy) is mirrored
     # here; every other shape writes T frames and is padded afterwards, as the reference does.
     n_time = x2.shape[-2] if interleaved_channels else x2.shape[1]
     fused_pad = (right_padding > 0 and n_fft == 400 and hop_length in (100, 160, 200) and n_time > 400
@@ -2922,7 +2922,7 @@ def _bf_wants_grad(*tensors) -> bool:
 
 
 def _bf_frame_major(x4: Tensor) -> bool:
-    """The unit-stride axis of a (B, C, F, T) view the kernels accept: True = freq (bf_view of csrc/c_api.hip)."""
+    """The unit-stride axis of a (B, C, F, T) view the kernels accept: True = freq (bf_view of csrc/api_post.hip)."""
     F_, T_ = x4.shape[2], x4.shape[3]
     sf, st = (x4.stride(2) if F_ > 1 else 1), (x4.stride(3) if T_ > 1 else 1)
     return False if st == 1 else (True if sf == 1 else T_ > 1)

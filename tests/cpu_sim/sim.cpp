@@ -542,7 +542,7 @@ static int sim_melspec400_h(const TIn* wav, const float* window, const float* tw
   LaneConst c[64];
   for (int l = 0; l < 64; ++l) lane_init(l, ctab, c[l]);
   const int tiles_per_row = (n_frames + kFramesPerWave - 1) / kFramesPerWave;
-  // same launch-time switches as launch_mel400() in c_api.hip
+  // same launch-time switches as launch_fft400_nr() in mel400_launch.h
   const bool in_aligned = (row_stride % (16 / (int)sizeof(TIn)) == 0);
   const bool out_wide = (epi_mode == EPI400_SPEC) || (want_wide && mb.n_mels % 4 == 0);
   static float X[64][HC::nx], vr[64][20], vi[64][20], zr[64][20], zi[64][20], qr[64][10], qi[64][10];

@@ -26,6 +26,16 @@ ALLOW = [(r"aamd14lfilter_kernelILi(8|12|16)E", 4200), (r"aamd2p217kaldi_pow2_ke
          (r"aamd3fdr17delay_line_kernelILi4E", 16)]
 
 
+def _bundles(so, d):
+    """The gfx950 code objects of the library, extracted into directory d: one per source it was linked from."""
+    local = os.path.join(d, "lib.so")
+    shutil.copy(so, local)
+    subprocess.run([os.path.join(LLVM, "llvm-objdump"), "--offloading", local], check=True, capture_output=True, cwd=d)
+    objs = sorted(os.path.join(d, f) for f in os.listdir(d) if "gfx950" in f)
+    assert objs, os.listdir(d)
+    return objs
+
+
 def _kernels():
     from audio_amd import _build
     so = _build.OUT
@@ -33,24 +43,22 @@ def _kernels():
         pytest.skip("libaudio_amd.so is not built")
     if not (os.path.exists(os.path.join(LLVM, "llvm-objdump")) and os.path.exists(os.path.join(LLVM, "llvm-readelf"))):
         pytest.skip("llvm-objdump / llvm-readelf not in this image")
+    out = {}
     with tempfile.TemporaryDirectory() as d:
-        local = os.path.join(d, "lib.so")
-        shutil.copy(so, local)
-        subprocess.run([os.path.join(LLVM, "llvm-objdump"), "--offloading", local], check=True, capture_output=True, cwd=d)
-        objs = [f for f in os.listdir(d) if "gfx950" in f]
-        assert len(objs) == 1, os.listdir(d)
-        notes = subprocess.run([os.path.join(LLVM, "llvm-readelf"), "--notes", os.path.join(d, objs[0])], check=True,
-                               capture_output=True, text=True).stdout
-    out, name = {}, None
-    for line in notes.splitlines():
-        m = re.match(r"\s*\.name:\s+(\S+)", line)
-        if m:
-            name = m.group(1)
-            out[name] = {}
-            continue
-        m = re.match(r"\s*\.(private_segment_fixed_size|vgpr_spill_count|sgpr_spill_count|vgpr_count):\s+(\d+)", line)
-        if m and name:
-            out[name][m.group(1)] = int(m.group(2))
+        for obj in _bundles(so, d):
+            notes = subprocess.run([os.path.join(LLVM, "llvm-readelf"), "--notes", obj], check=True, capture_output=True,
+                                   text=True).stdout
+            name = None
+            for line in notes.splitlines():
+                m = re.match(r"\s*\.name:\s+(\S+)", line)
+                if m:
+                    name = m.group(1)
+                    assert name not in out, "kernel %s is emitted into two code objects" % name
+                    out[name] = {}
+                    continue
+                m = re.match(r"\s*\.(private_segment_fixed_size|vgpr_spill_count|sgpr_spill_count|vgpr_count):\s+(\d+)", line)
+                if m and name:
+                    out[name][m.group(1)] = int(m.group(2))
     return out
 
 
@@ -89,12 +97,11 @@ def test_real_block_delay_line_steps_do_not_touch_scratch():
     if not os.path.exists(so) or not os.path.exists(os.path.join(LLVM, "llvm-objdump")):
         pytest.skip("library or llvm-objdump missing")
     with tempfile.TemporaryDirectory() as d:
-        local = os.path.join(d, "lib.so")
-        shutil.copy(so, local)
-        subprocess.run([os.path.join(LLVM, "llvm-objdump"), "--offloading", local], check=True, capture_output=True, cwd=d)
-        obj = [f for f in os.listdir(d) if "gfx950" in f][0]
-        dis = subprocess.run([os.path.join(LLVM, "llvm-objdump"), "-d", "--no-show-raw-insn", os.path.join(d, obj)], check=True,
-                             capture_output=True, text=True).stdout
+        dis = ""
+        for obj in _bundles(so, d):                 # the code object that holds the kernel
+            if b"delay_line_kernel" in open(obj, "rb").read():
+                dis = subprocess.run([os.path.join(LLVM, "llvm-objdump"), "-d", "--no-show-raw-insn", obj], check=True,
+                                     capture_output=True, text=True).stdout
     for np_ in (2, 3, 4):
         m = re.search(r"<_ZN4aamd3fdr17delay_line_kernelILi%dE[^>]*>:\n(.*?)s_endpgm" % np_, dis, re.S)
         assert m, np_

@@ -1,6 +1,6 @@
 // Lab build of the real-block fftconvolve kernel (tools only): audio_amd/csrc/fftconv_fdr.h compiled alone, one shared library per
 // source variant (-D switches), so that an A/B of a kernel change builds in seconds and several variants run interleaved in
-// one process (tools/fdr_lab.py).  The launch logic is the plan-3 branch of aamd_fftconvolve_staged_f32 (csrc/c_api.hip).
+// one process (tools/fdr_lab.py).  The launch logic is the plan-3 branch of aamd_fftconvolve_staged_f32 (csrc/api_fftconv.hip).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../audio_amd/csrc/fftconv_fdr.h"

@@ -5,7 +5,7 @@
 #include <stdint.h>
 #include <stdio.h>
 #include "../../include/audio_amd.h"
-#include "../../audio_amd/csrc/melspec400.h"
+#include "../../audio_amd/csrc/mel400_tables.h"   // melspec400.h + the two table-building kernels
 
 using namespace aamd;
 

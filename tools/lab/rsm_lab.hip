@@ -1,6 +1,6 @@
 // Lab build of the binary16-split resampler (tools only): audio_amd/csrc/resample_mfma.h compiled alone, one shared library per
 // source variant (-D switches), so that an A/B of a kernel change builds in seconds and several variants run interleaved in one
-// process (tools/rsm_lab.py).  The launch logic is the f16 branch of aamd_resample_banded_f32 (csrc/c_api.hip).
+// process (tools/rsm_lab.py).  The launch logic is the f16 branch of aamd_resample_banded_f32 (csrc/api_resample.hip).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../audio_amd/csrc/resample_mfma.h"

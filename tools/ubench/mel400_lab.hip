@@ -9,7 +9,7 @@
 #include <cstdlib>
 #include <vector>
 
-#include "../../audio_amd/csrc/melspec400.h"
+#include "../../audio_amd/csrc/mel400_tables.h"   // melspec400.h + the two table-building kernels
 
 using namespace aamd;
 using namespace aamd::m400;
