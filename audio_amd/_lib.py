@@ -162,6 +162,13 @@ _SIGS = {
     "aamd_beamform_weights": (C.c_int, [C.c_int32, C.c_int32, _P, _P, _P, _P, C.c_int64, C.c_int64] + [C.c_int32] * 4 +
                               [C.c_double, C.c_double, C.c_int32, C.c_int32, _P]),
     "aamd_beamform_apply": (C.c_int, [C.c_int32, _P, _P] + [C.c_int64] * 8 + [_P, _P, _P]),
+    # RNN transducer loss (additions to ABI 7)
+    "aamd_rnnt_team_width": (C.c_int32, [C.c_int32, C.c_int64]),
+    "aamd_rnnt_lattice_threads": (C.c_int32, []),
+    "aamd_rnnt_loss_workspace": (C.c_int64, [C.c_int64] * 3),
+    "aamd_rnnt_loss_forward": (C.c_int, [C.c_int32, _P, _P, _P, _P] + [C.c_int64] * 4 + [C.c_int32, C.c_int32, _P, _P, _P]),
+    "aamd_rnnt_loss_backward": (C.c_int, [C.c_int32, _P, _P, _P, _P] + [C.c_int64] * 4 + [C.c_int32, C.c_int32, C.c_double,
+                                          _P, _P, _P, _P]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS)

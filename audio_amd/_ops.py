@@ -73,6 +73,8 @@ _DEF.define("mvdr_weights_rtf(Tensor rtf, Tensor psd_n, int? reference_channel, 
 _DEF.define("rtf_power(Tensor psd_s, Tensor psd_n, int reference_channel, Tensor? reference_vector, int n_iter, "
             "bool diagonal_loading, float diag_eps) -> Tensor")
 _DEF.define("apply_beamforming(Tensor beamform_weights, Tensor specgram) -> Tensor")
+_DEF.define("rnnt_loss(Tensor logits, Tensor targets, Tensor logit_lengths, Tensor target_lengths, int blank, float clamp, "
+            "str reduction, bool fused_log_softmax) -> Tensor")
 _DEF.define("rnnt_features(Tensor waveform, Tensor window, Tensor fb, int n_fft, int hop_length, float gain, Tensor mean, "
             "Tensor invstddev, int right_padding) -> Tensor")
 
@@ -199,6 +201,7 @@ _register("mvdr_weights_rtf", lambda rtf, psd_n, ref, vec, loading, diag_eps, ep
 _register("rtf_power", lambda psd_s, psd_n, ref, vec, n_iter, loading, diag_eps:
           F._rtf_power_eager(psd_s, psd_n, _ref_of(ref, vec), n_iter, loading, diag_eps))
 _register("apply_beamforming", F._apply_beamforming_eager)
+_register("rnnt_loss", F._rnnt_loss_eager)
 
 
 # ---- Meta implementations: shapes / strides only ---------------------------------------------
@@ -388,3 +391,15 @@ _META.impl("mvdr_weights_rtf", lambda rtf, psd_n, *rest: rtf.new_empty(tuple(rtf
 _META.impl("rtf_power", lambda psd_s, psd_n, *rest: psd_n.new_empty(tuple(psd_n.shape[:-1])))
 _META.impl("apply_beamforming", _apply_beamforming_meta)
 
+
+
+def _rnnt_loss_meta(logits, targets, logit_lengths, target_lengths, blank, clamp, reduction, fused_log_softmax):
+    if reduction not in ("none", "mean", "sum"):
+        raise ValueError("reduction should be one of 'none', 'mean', or 'sum'")
+    if logits.dim() != 4 or targets.dim() != 2 or targets.shape[0] != logits.shape[0] or targets.shape[1] + 1 != logits.shape[2]:
+        raise ValueError(f"logits must be (batch, time, target + 1, class) and targets (batch, target): got {tuple(logits.shape)} "
+                         f"and {tuple(targets.shape)}")
+    return logits.new_empty((logits.shape[0],) if reduction == "none" else ())
+
+
+_META.impl("rnnt_loss", _rnnt_loss_meta)

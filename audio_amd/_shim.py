@@ -39,7 +39,9 @@ OPS = ("spectrogram", "mel_spectrogram", "mel_spectrogram_db", "mfcc_dct", "resa
        "add_noise", "add_noise_grad", "preemphasis",
        # MVDR beamforming: F.psd (one or two masks), the per-bin solve of the weight functions, F.apply_beamforming
        # (additions to ABI 7); complex tensors cross as their real views
-       "beamform_psd", "beamform_weights", "beamform_apply")
+       "beamform_psd", "beamform_weights", "beamform_apply",
+       # the RNN transducer loss: row pass + lattice, and the gradient pass (F.rnnt_loss; additions to ABI 7)
+       "rnnt_loss_forward", "rnnt_loss_backward")
 
 _lock = threading.Lock()
 _handle = None
@@ -239,6 +241,14 @@ def _register_fakes() -> None:
     def _(weights, specgram, frame_major):
         B, F, T = specgram.shape[0], specgram.shape[2], specgram.shape[3]
         return specgram.new_empty((B, T, F, 2) if frame_major else (B, F, T, 2))
+
+    @reg("aamd::rnnt_loss_forward")
+    def _(logits, targets, logit_lengths, target_lengths, blank, fused, workspace):
+        return logits.new_empty((logits.shape[0],), dtype=torch.float64)
+
+    @reg("aamd::rnnt_loss_backward")
+    def _(logits, targets, logit_lengths, target_lengths, blank, fused, clamp, workspace, grad_costs):
+        return torch.empty_like(logits)
 
 
 def available() -> bool:

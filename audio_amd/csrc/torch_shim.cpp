@@ -1030,6 +1030,61 @@ Tensor beamform_apply(Tensor w, Tensor x, bool frame_major) {
   return out;
 }
 
+// ---- aamd::rnnt_loss_forward / rnnt_loss_backward (F.rnnt_loss, T.RNNTLoss; csrc/rnnt_loss.h) --------------------------
+// The workspace (float64, aamd_rnnt_loss_workspace bytes) is the caller's: autograd keeps it from forward to backward.
+struct RnntShape {
+  int32_t dtype;
+  int64_t B, T, U1, V;
+};
+RnntShape rnnt_check(const Tensor& logits, const Tensor& targets, const Tensor& ll, const Tensor& tl, int64_t blank,
+                     const Tensor& workspace) {
+  RnntShape s;
+  s.dtype = wave_dtype(logits, "logits");
+  STD_TORCH_CHECK(logits.dim() == 4 && logits.is_contiguous(), "audio_amd: logits must be a contiguous (batch, time, target + 1, vocab) tensor");
+  s.B = logits.size(0); s.T = logits.size(1); s.U1 = logits.size(2); s.V = logits.size(3);
+  STD_TORCH_CHECK(s.T >= 1 && s.U1 >= 1 && s.V >= 1, "audio_amd: rnnt_loss: empty time, target or vocabulary axis");
+  want_i32(targets, "targets");
+  want_i32(ll, "logit_lengths");
+  want_i32(tl, "target_lengths");
+  STD_TORCH_CHECK(targets.dim() == 2 && targets.size(0) == s.B && targets.size(1) == s.U1 - 1 && ll.dim() == 1 && ll.size(0) == s.B &&
+                  tl.dim() == 1 && tl.size(0) == s.B, "audio_amd: rnnt_loss: targets / lengths do not belong to logits");
+  STD_TORCH_CHECK(blank >= 0 && blank < s.V, "audio_amd: rnnt_loss: blank must lie in [0, vocab)");
+  STD_TORCH_CHECK(workspace.is_cuda() && workspace.scalar_type() == ScalarType::Double && workspace.is_contiguous() &&
+                  workspace.numel() * 8 >= aamd_rnnt_loss_workspace(s.B, s.T, s.U1), "audio_amd: rnnt_loss: workspace too small");
+  same_device(logits, targets);
+  same_device(logits, ll);
+  same_device(logits, tl);
+  same_device(logits, workspace);
+  return s;
+}
+const int32_t* ip(const Tensor& t) { return t.numel() ? static_cast<const int32_t*>(t.data_ptr()) : nullptr; }
+
+// costs (batch,) float64
+Tensor rnnt_loss_forward(Tensor logits, Tensor targets, Tensor logit_lengths, Tensor target_lengths, int64_t blank, bool fused,
+                         Tensor workspace) {
+  const RnntShape s = rnnt_check(logits, targets, logit_lengths, target_lengths, blank, workspace);
+  const torch::stable::accelerator::DeviceGuard guard(logits.get_device_index());
+  Tensor costs = torch::stable::new_empty(logits, {s.B}, ScalarType::Double);
+  if (s.B == 0) return costs;
+  check(aamd_rnnt_loss_forward(s.dtype, logits.data_ptr(), ip(targets), ip(logit_lengths), ip(target_lengths), s.B, s.T, s.U1, s.V,
+                               (int32_t)blank, fused ? 1 : 0, workspace.data_ptr(), dpm(costs), current_stream(logits)));
+  return costs;
+}
+Tensor rnnt_loss_backward(Tensor logits, Tensor targets, Tensor logit_lengths, Tensor target_lengths, int64_t blank, bool fused,
+                          double clamp, Tensor workspace, Tensor grad_costs) {
+  const RnntShape s = rnnt_check(logits, targets, logit_lengths, target_lengths, blank, workspace);
+  STD_TORCH_CHECK(grad_costs.is_cuda() && grad_costs.scalar_type() == ScalarType::Double && grad_costs.is_contiguous() &&
+                  grad_costs.dim() == 1 && grad_costs.size(0) == s.B, "audio_amd: rnnt_loss: grad_costs must be a float64 (batch,) device tensor");
+  same_device(logits, grad_costs);
+  const torch::stable::accelerator::DeviceGuard guard(logits.get_device_index());
+  Tensor grad = torch::stable::empty_like(logits);
+  if (s.B == 0) return grad;
+  check(aamd_rnnt_loss_backward(s.dtype, logits.data_ptr(), ip(targets), ip(logit_lengths), ip(target_lengths), s.B, s.T, s.U1, s.V,
+                                (int32_t)blank, fused ? 1 : 0, clamp, workspace.data_ptr(), dp(grad_costs), grad.data_ptr(),
+                                current_stream(logits)));
+  return grad;
+}
+
 // ---- torchaudio::_lfilter_core_loop on the CUDA key (lfilter.cpp:118-134, iir_cuda.cu:37-79) ------------------------
 //   padded_out[n][c][i + n_order - 1] = in[n][c][i] - sum_{j < n_order-1} a_flipped[c][j] * padded_out[n][c][i + j]
 // = the pure recursion y = IIR(in; a) with a = flip(a_flipped), b = (1, 0, ...), no clamp: aamd_lfilter_f32 runs it as a
@@ -1138,6 +1193,10 @@ STABLE_TORCH_LIBRARY(aamd, m) {
   m.def("beamform_weights(int mode, Tensor a, Tensor b, Tensor? reference_vector, int batch, int freq, int reference, "
         "bool loading, float diag_eps, float eps, int n_iter, bool adjoint) -> Tensor");
   m.def("beamform_apply(Tensor weights, Tensor specgram, bool frame_major) -> Tensor");
+  m.def("rnnt_loss_forward(Tensor logits, Tensor targets, Tensor logit_lengths, Tensor target_lengths, int blank, bool fused, "
+        "Tensor(a!) workspace) -> Tensor");
+  m.def("rnnt_loss_backward(Tensor logits, Tensor targets, Tensor logit_lengths, Tensor target_lengths, int blank, bool fused, "
+        "float clamp, Tensor workspace, Tensor grad_costs) -> Tensor");
 }
 
 STABLE_TORCH_LIBRARY_IMPL(aamd, CUDA, m) {
@@ -1179,6 +1238,8 @@ STABLE_TORCH_LIBRARY_IMPL(aamd, CUDA, m) {
   m.impl("beamform_psd", TORCH_BOX(&beamform_psd));
   m.impl("beamform_weights", TORCH_BOX(&beamform_weights));
   m.impl("beamform_apply", TORCH_BOX(&beamform_apply));
+  m.impl("rnnt_loss_forward", TORCH_BOX(&rnnt_loss_forward));
+  m.impl("rnnt_loss_backward", TORCH_BOX(&rnnt_loss_backward));
 }
 
 // The reference's op.  libtorchaudio (when present) has already run

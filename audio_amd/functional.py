@@ -34,6 +34,7 @@ __all__ = [
     "compute_deltas", "sliding_window_cmn", "detect_pitch_frequency", "mask_along_axis", "mask_along_axis_iid",
     "add_noise", "preemphasis", "deemphasis", "convolve",
     "psd", "mvdr_weights_souden", "mvdr_weights_rtf", "rtf_power", "rtf_evd", "apply_beamforming",
+    "rnnt_loss",
 ]
 
 # --------------------------------------------------------------------------- #
@@ -3210,6 +3211,149 @@ def rtf_evd(psd_s: Tensor) -> Tensor:
                               "package does not have yet; use rtf_power")
 
 
+# --------------------------------------------------------------------------- #
+# RNN transducer loss (csrc/rnnt_loss.h)                                      #
+# --------------------------------------------------------------------------- #
+_RNNT_DTYPES = {torch.float32: 0, torch.float64: 1, torch.float16: 2, torch.bfloat16: 3}      # AAMD_SA_*
+RNNT_MAX_U1 = 1024                   # AAMD_RNNT_MAX_U1: the longest target axis (U + 1) the lattice kernel serves
+
+
+def rnnt_tiles() -> Tuple[Tuple[int, ...], int, int]:
+    """(team widths of the row and gradient passes, threads of a lattice workgroup, largest U + 1) of csrc/rnnt_loss.h."""
+    lib = _lib.lib()
+    widths = sorted({int(lib.aamd_rnnt_team_width(0, 1 << k)) for k in range(12)})
+    return tuple(widths), int(lib.aamd_rnnt_lattice_threads()), RNNT_MAX_U1
+
+
+def rnnt_team_width(dtype: torch.dtype, vocab: int) -> int:
+    """Lanes per (b, t, u) row that the launcher picks for a vocabulary of ``vocab`` entries of ``dtype``."""
+    return int(_lib.lib().aamd_rnnt_team_width(_RNNT_DTYPES[dtype], int(vocab)))
+
+
+def _rnnt_check(logits: Tensor, targets: Tensor, logit_lengths: Tensor, target_lengths: Tensor, blank: int,
+                reduction: str) -> int:
+    """The host-side checks of F.rnnt_loss; returns the blank index counted from the front."""
+    if reduction not in ("none", "mean", "sum"):
+        raise ValueError("reduction should be one of 'none', 'mean', or 'sum'")
+    if logits.dim() != 4:
+        raise ValueError(f"logits must be 4-D (batch, time, target + 1, class), got {tuple(logits.shape)}")
+    if targets.dim() != 2:
+        raise ValueError(f"targets must be 2-D (batch, target), got {tuple(targets.shape)}")
+    if logit_lengths.dim() != 1 or target_lengths.dim() != 1:
+        raise ValueError("logit_lengths and target_lengths must be 1-D (batch,)")
+    B, T_, U1, V = logits.shape
+    if targets.shape[0] != B or logit_lengths.shape[0] != B or target_lengths.shape[0] != B:
+        raise ValueError(f"batch sizes differ: logits {B}, targets {targets.shape[0]}, logit_lengths {logit_lengths.shape[0]}, "
+                         f"target_lengths {target_lengths.shape[0]}")
+    if targets.shape[1] + 1 != U1:
+        raise ValueError(f"logits dimension 2 must be targets dimension 1 plus one (got {U1} and {targets.shape[1]})")
+    if T_ < 1 or V < 1:
+        raise ValueError(f"logits needs at least one frame and one class, got {tuple(logits.shape)}")
+    if logits.dtype not in _RNNT_DTYPES:
+        raise TypeError(f"logits must be float32, float64, float16 or bfloat16 (got {logits.dtype})")
+    for t, what in ((targets, "targets"), (logit_lengths, "logit_lengths"), (target_lengths, "target_lengths")):
+        if t.dtype != torch.int32:
+            raise TypeError(f"{what} must be int32 (got {t.dtype})")
+    for t, what in ((logits, "logits"), (targets, "targets"), (logit_lengths, "logit_lengths"),
+                    (target_lengths, "target_lengths")):
+        if not t.is_contiguous():
+            raise ValueError(f"{what} must be contiguous")
+    bl = blank + V if blank < 0 else blank
+    if not 0 <= bl < V:
+        raise ValueError(f"blank must lie in [-{V}, {V}) for {V} classes (got {blank})")
+    if U1 > RNNT_MAX_U1:
+        raise NotImplementedError(f"audio_amd: rnnt_loss serves targets up to U + 1 = {RNNT_MAX_U1} (got {U1}): the lattice of one "
+                                  "example belongs to one workgroup")
+    for t, what in ((logits, "logits"), (targets, "targets"), (logit_lengths, "logit_lengths"),
+                    (target_lengths, "target_lengths")):
+        if not t.is_cuda:
+            raise RuntimeError(f"audio_amd: {what} must be on an MI355X (ROCm) device, got {t.device}. "
+                               "The HIP kernels have no CPU fallback.")
+        if t.device != logits.device:
+            raise RuntimeError(f"audio_amd: {what} must be on the logits' device")
+    return bl
+
+
+def _rnnt_forward_launch(logits: Tensor, targets: Tensor, logit_lengths: Tensor, target_lengths: Tensor, blank: int,
+                         fused: bool) -> Tuple[Tensor, Tensor]:
+    """(costs (B,) float64, workspace): the row pass and the lattice.  Nothing is read back: lengths stay on the device."""
+    B, T_, U1, V = logits.shape
+    lib = _lib.lib()
+    ws = torch.empty((max(int(lib.aamd_rnnt_loss_workspace(B, T_, U1)) // 8, 1),), dtype=torch.float64, device=logits.device)
+    ops = _ops()
+    if ops is not None:
+        return ops.rnnt_loss_forward(logits, targets, logit_lengths, target_lengths, blank, bool(fused), ws), ws
+    costs = torch.empty((B,), dtype=torch.float64, device=logits.device)
+    if B:
+        with torch.cuda.device(logits.device):
+            _lib.check(lib.aamd_rnnt_loss_forward(_RNNT_DTYPES[logits.dtype], _lib.ptr(logits), _lib.ptr(targets) or None,
+                                                  _lib.ptr(logit_lengths), _lib.ptr(target_lengths), B, T_, U1, V, blank,
+                                                  int(bool(fused)), ws.data_ptr(), costs.data_ptr(),
+                                                  _lib.current_stream(logits.device)))
+    return costs, ws
+
+
+def _rnnt_backward_launch(logits: Tensor, targets: Tensor, logit_lengths: Tensor, target_lengths: Tensor, blank: int,
+                          fused: bool, clamp: float, ws: Tensor, grad_costs: Tensor) -> Tensor:
+    """d costs / d logits (clamped) times grad_costs (B,) float64: one read of logits, one write of the result."""
+    B, T_, U1, V = logits.shape
+    ops = _ops()
+    if ops is not None:
+        return ops.rnnt_loss_backward(logits, targets, logit_lengths, target_lengths, blank, bool(fused), float(clamp), ws,
+                                      grad_costs)
+    grad = torch.empty_like(logits)
+    if B:
+        with torch.cuda.device(logits.device):
+            _lib.check(_lib.lib().aamd_rnnt_loss_backward(_RNNT_DTYPES[logits.dtype], _lib.ptr(logits), _lib.ptr(targets) or None,
+                                                          _lib.ptr(logit_lengths), _lib.ptr(target_lengths), B, T_, U1, V, blank,
+                                                          int(bool(fused)), float(clamp), ws.data_ptr(), grad_costs.data_ptr(),
+                                                          grad.data_ptr(), _lib.current_stream(logits.device)))
+    return grad
+
+
+class _RNNTLossFunction(torch.autograd.Function):
+    """Costs (B,) in the dtype of logits.  What is kept for backward is logits itself and the float64 workspaces of
+    B * T * (U + 1) cells; the gradient is formed in backward, once: a second derivative raises."""
+
+    @staticmethod
+    def forward(ctx, logits, targets, logit_lengths, target_lengths, blank, clamp, fused):
+        costs, ws = _rnnt_forward_launch(logits, targets, logit_lengths, target_lengths, blank, fused)
+        ctx.save_for_backward(logits, targets, logit_lengths, target_lengths, ws)
+        ctx.rnnt = (blank, clamp, fused)
+        return costs.to(logits.dtype)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_costs):
+        logits, targets, logit_lengths, target_lengths, ws = ctx.saved_tensors
+        blank, clamp, fused = ctx.rnnt
+        grad = _rnnt_backward_launch(logits, targets, logit_lengths, target_lengths, blank, fused, clamp, ws,
+                                     grad_costs.to(torch.float64).contiguous())
+        return grad, None, None, None, None, None, None
+
+
+def _rnnt_loss_eager(logits: Tensor, targets: Tensor, logit_lengths: Tensor, target_lengths: Tensor, blank: int = -1,
+                     clamp: float = -1.0, reduction: str = "mean", fused_log_softmax: bool = True) -> Tensor:
+    r"""RNN transducer loss (reference: F.rnnt_loss, a compiled extension there).  ``logits`` ``(B, T, U + 1, V)``, ``targets``
+    ``(B, U)`` int32, ``logit_lengths`` / ``target_lengths`` ``(B,)`` int32.  Forward is one streaming read of ``logits`` (online
+    log-sum-exp per ``(b, t, u)`` row, the padding of ragged batches not read) and a float64 alpha / beta lattice per example;
+    backward is one read of ``logits`` and one write of the gradient, and nothing of that size is kept in between.  float16 /
+    bfloat16 are read and written directly with float32 arithmetic; float64 is the precision path.  Lengths and targets are
+    read on the device -- no synchronisation, so the call can be captured in a graph -- and an example with an impossible
+    length or label gets a NaN cost and a NaN gradient block instead of the reference's host-side error."""
+    bl = _rnnt_check(logits, targets, logit_lengths, target_lengths, blank, reduction)
+    if torch.is_grad_enabled() and logits.requires_grad:
+        costs = _RNNTLossFunction.apply(logits, targets, logit_lengths, target_lengths, bl, float(clamp), bool(fused_log_softmax))
+    else:
+        costs = _rnnt_forward_launch(logits.detach(), targets, logit_lengths, target_lengths, bl,
+                                     bool(fused_log_softmax))[0].to(logits.dtype)
+    if reduction == "mean":
+        return costs.mean()
+    if reduction == "sum":
+        return costs.sum()
+    return costs
+
+
 @_reduced_precision_io
 def _convolve_eager(x: Tensor, y: Tensor, mode: str = "full") -> Tensor:
     r"""Linear convolution along the last dim with broadcast leading dims and the reference's full / valid / same crops
@@ -3682,3 +3826,13 @@ def apply_beamforming(beamform_weights: Tensor, specgram: Tensor) -> Tensor:
         if not torch.compiler.is_compiling():
             return _apply_beamforming_eager(beamform_weights, specgram)
     return torch.ops.audio_amd.apply_beamforming(beamform_weights, specgram)
+
+
+def rnnt_loss(logits: Tensor, targets: Tensor, logit_lengths: Tensor, target_lengths: Tensor, blank: int = -1,
+              clamp: float = -1.0, reduction: str = "mean", fused_log_softmax: bool = True) -> Tensor:
+    r"""RNN transducer loss (reference: F.rnnt_loss); see ``_rnnt_loss_eager``."""
+    if not torch.jit.is_scripting():
+        if not torch.compiler.is_compiling():
+            return _rnnt_loss_eager(logits, targets, logit_lengths, target_lengths, blank, clamp, reduction, fused_log_softmax)
+    return torch.ops.audio_amd.rnnt_loss(logits, targets, logit_lengths, target_lengths, blank, clamp, reduction,
+                                         fused_log_softmax)

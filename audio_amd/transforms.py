@@ -1,6 +1,7 @@
 """Drop-in replacements for the hot-path modules of ``torchaudio.transforms``:
 Spectrogram, MelScale, MelSpectrogram, AmplitudeToDB, MFCC, Resample, FFTConvolve, ComputeDeltas, SlidingWindowCmn,
-FrequencyMasking, TimeMasking, SpecAugment, AddNoise, Preemphasis, Deemphasis, Convolve, PSD, MVDR, SoudenMVDR, RTFMVDR.
+FrequencyMasking, TimeMasking, SpecAugment, AddNoise, Preemphasis, Deemphasis, Convolve, PSD, MVDR, SoudenMVDR, RTFMVDR,
+RNNTLoss.
 
 Constructor / forward signatures, registered buffer names (``window``, ``fb``, ``dct_mat``,
 ``kernel``), shapes, strides, warnings and error messages follow
@@ -34,7 +35,7 @@ _norm_mode = F._norm_mode      # `normalized` as the op schemas' integer: 0 none
 __all__ = ["Spectrogram", "InverseSpectrogram", "GriffinLim", "TimeStretch", "PitchShift", "Speed", "SpeedPerturbation",
            "MelScale", "MelSpectrogram", "AmplitudeToDB", "MFCC", "Resample", "FFTConvolve", "ComputeDeltas",
            "SlidingWindowCmn", "FrequencyMasking", "TimeMasking", "SpecAugment", "AddNoise", "Preemphasis", "Deemphasis",
-           "Convolve", "PSD", "MVDR", "SoudenMVDR", "RTFMVDR"]
+           "Convolve", "PSD", "MVDR", "SoudenMVDR", "RTFMVDR", "RNNTLoss"]
 
 
 class Spectrogram(torch.nn.Module):
@@ -805,3 +806,20 @@ class MVDR(torch.nn.Module):
             w_mvdr = F.mvdr_weights_rtf(stv, psd_n, self.ref_channel, self.diag_loading, self.diag_eps, 1e-8)
         return F.apply_beamforming(w_mvdr, specgram).to(dtype)
 
+
+
+class RNNTLoss(torch.nn.Module):
+    r"""RNN transducer loss of ``(batch, time, target + 1, class)`` joiner outputs (reference: T.RNNTLoss): ``F.rnnt_loss``
+    with the module's ``blank``, ``clamp``, ``reduction`` and ``fused_log_softmax``; no buffers."""
+    __constants__ = ["blank", "clamp", "reduction", "fused_log_softmax"]
+
+    def __init__(self, blank: int = -1, clamp: float = -1.0, reduction: str = "mean", fused_log_softmax: bool = True) -> None:
+        super().__init__()
+        self.blank = blank
+        self.clamp = clamp
+        self.reduction = reduction
+        self.fused_log_softmax = fused_log_softmax
+
+    def forward(self, logits: Tensor, targets: Tensor, logit_lengths: Tensor, target_lengths: Tensor) -> Tensor:
+        return F.rnnt_loss(logits, targets, logit_lengths, target_lengths, self.blank, self.clamp, self.reduction,
+                           self.fused_log_softmax)

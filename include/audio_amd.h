@@ -53,6 +53,8 @@
  *   aamd_beamform_psd         F.psd / T.PSD, the weight solves and F.apply_beamforming / T.MVDR (einsum + linalg.solve
  *   aamd_beamform_weights     compositions over a (..., freq, time, ch, ch) temporary in the reference) -- additions to
  *   aamd_beamform_apply       ABI 7 as well
+ *   aamd_rnnt_loss_forward    F.rnnt_loss / T.RNNTLoss (the reference's compiled transducer loss, libtorchaudio/rnnt):
+ *   aamd_rnnt_loss_backward   one read of the logits forward, one read and one write backward -- additions to ABI 7 as well
  *   aamd_detect_pitch_f32     F.detect_pitch_frequency (_compute_nccf + _find_max_per_frame + _median_smoothing in the
  *                             reference; an addition to ABI 7 as well)
  *
@@ -657,6 +659,38 @@ int aamd_beamform_weights(int32_t dtype, int32_t mode, const void* a, const void
 int aamd_beamform_apply(int32_t dtype, const void* w, const void* x, int64_t batch, int64_t channels, int64_t freq,
                         int64_t time, int64_t stride_b, int64_t stride_c, int64_t stride_f, int64_t stride_t, void* out,
                         const int64_t* out_strides, void* stream);
+
+/* ---- RNN transducer loss (additions to ABI 7; csrc/rnnt_loss.h) -------------------------------------------------------- */
+
+#define AAMD_RNNT_MAX_U1 1024        /* the longest target axis (U + 1) the lattice kernel serves */
+
+/* Lanes per (b, t, u) row that the row and gradient passes use for a vocabulary of `vocab` entries of element type `dtype`
+ * (AAMD_SA_F32 / F64 / F16 / BF16): 8, 16, 32 or 64.  The lattice workgroup's thread count. */
+int32_t aamd_rnnt_team_width(int32_t dtype, int64_t vocab);
+int32_t aamd_rnnt_lattice_threads(void);
+
+/* Bytes of device workspace a forward call needs and a backward call reads again (8-byte aligned): denominators, the two
+ * log-probabilities per cell, alpha and beta as float64 (batch, max_t, max_u1) each, and one flag per example. */
+int64_t aamd_rnnt_loss_workspace(int64_t batch, int64_t max_t, int64_t max_u1);
+
+/* Forward.  logits dense (batch, max_t, max_u1, vocab) of `dtype` (AAMD_SA_*), targets dense (batch, max_u1 - 1) int32,
+ * logit_lengths / target_lengths (batch,) int32, all on the device and read there: no synchronisation.  blank in [0, vocab).
+ * fused_log_softmax != 0: the log-softmax over vocab is part of the loss (one streaming read of logits); 0: logits holds
+ * log-probabilities.  costs (batch,) float64 = -log P(targets | logits) per example.  An example with a logit length outside
+ * [1, max_t], a target length outside [0, max_u1 - 1] or a live target outside [0, vocab) gets a NaN cost, and nothing is
+ * indexed with those values.  max_u1 > AAMD_RNNT_MAX_U1: AAMD_EUNSUPPORTED.  Two launches (row pass, lattice). */
+int aamd_rnnt_loss_forward(int32_t dtype, const void* logits, const int32_t* targets, const int32_t* logit_lengths,
+                           const int32_t* target_lengths, int64_t batch, int64_t max_t, int64_t max_u1, int64_t vocab,
+                           int32_t blank, int32_t fused_log_softmax, void* workspace, double* costs, void* stream);
+
+/* Backward, from the workspace a forward call with the same arguments left: grad (as logits) = d costs[b] / d logits,
+ * clamped to [-clamp, clamp] when clamp > 0, times grad_costs[b] (float64, read on the device).  Exactly zero where
+ * t >= logit_lengths[b] or u > target_lengths[b]; NaN over the whole block of an example whose cost is NaN.  One launch when
+ * fused (one read of logits, one write of grad), two otherwise. */
+int aamd_rnnt_loss_backward(int32_t dtype, const void* logits, const int32_t* targets, const int32_t* logit_lengths,
+                            const int32_t* target_lengths, int64_t batch, int64_t max_t, int64_t max_u1, int64_t vocab,
+                            int32_t blank, int32_t fused_log_softmax, double clamp, const void* workspace,
+                            const double* grad_costs, void* grad, void* stream);
 
 #ifdef __cplusplus
 }
