@@ -50,12 +50,13 @@ void* current_stream(const Tensor& t) {
   return s;
 }
 
-void want_f32(const Tensor& t, const char* what, int64_t dim = -1) {
+void want_dev(const Tensor& t, ScalarType st, const char* what, int64_t dim = -1) {
   STD_TORCH_CHECK(t.is_cuda(), "audio_amd: ", what, " must be on an MI355X (ROCm) device; there is no CPU kernel");
-  STD_TORCH_CHECK(t.scalar_type() == ScalarType::Float, "audio_amd: ", what, " must be float32");
+  STD_TORCH_CHECK(t.scalar_type() == st, "audio_amd: ", what, st == ScalarType::Float ? " must be float32" : " has the wrong dtype");
   STD_TORCH_CHECK(t.is_contiguous(), "audio_amd: ", what, " must be contiguous");
   if (dim >= 0) STD_TORCH_CHECK(t.dim() == dim, "audio_amd: ", what, " must have ", dim, " dimensions");
 }
+void want_f32(const Tensor& t, const char* what, int64_t dim = -1) { want_dev(t, ScalarType::Float, what, dim); }
 
 void want_i32(const Tensor& t, const char* what) {
   STD_TORCH_CHECK(t.is_cuda() && t.scalar_type() == ScalarType::Int && t.is_contiguous(), "audio_amd: ", what,
@@ -66,21 +67,50 @@ void same_device(const Tensor& a, const Tensor& b) {
   STD_TORCH_CHECK(a.get_device_index() == b.get_device_index(), "audio_amd: tensors on different devices");
 }
 
-const float* fp(const Tensor& t) { return t.numel() ? static_cast<const float*>(t.data_ptr()) : nullptr; }
-float* fpm(Tensor& t) { return t.numel() ? static_cast<float*>(t.data_ptr()) : nullptr; }
+// the tensor's elements as T (the caller has checked the dtype); null for an empty tensor
+template <typename T>
+const T* ptr(const Tensor& t) { return t.numel() ? static_cast<const T*>(t.data_ptr()) : nullptr; }
+template <typename T>
+T* mut(Tensor& t) { return t.numel() ? static_cast<T*>(t.data_ptr()) : nullptr; }
 
-aamd_stft_desc make_desc(const Tensor& wav, int64_t n_fft, int64_t hop, int64_t pad, bool center, int64_t pad_mode,
-                         bool onesided, int64_t n_frames, double scale, double power) {
-  // rows may be a strided view of longer rows (a batch sliced in time): unit stride along time is what the kernels need
-  STD_TORCH_CHECK(wav.is_cuda(), "audio_amd: waveform must be on an MI355X (ROCm) device; there is no CPU kernel");
-  STD_TORCH_CHECK(wav.scalar_type() == ScalarType::Float, "audio_amd: waveform must be float32");
-  STD_TORCH_CHECK(wav.dim() == 2, "audio_amd: waveform must be (rows, time)");
-  STD_TORCH_CHECK(wav.size(1) <= 1 || wav.stride(1) == 1, "audio_amd: waveform rows must have unit stride");
-  STD_TORCH_CHECK(wav.size(0) <= 1 || wav.stride(0) >= wav.size(1), "audio_amd: overlapping waveform rows");
+// the float32 / float64 pairs of ops are one template over the element type T: its dtype, and its entry of the C ABI
+template <typename T>
+constexpr ScalarType scalar_of = std::is_same<T, double>::value ? ScalarType::Double : ScalarType::Float;
+template <typename T, typename F32, typename F64>
+constexpr auto pick(F32 f32, F64 f64) {
+  if constexpr (std::is_same<T, double>::value) return f64; else return f32;
+}
+
+// float16 / bfloat16 / float32 / float64 operands of the entries that take the element type as an AAMD_SA_* code
+int32_t wave_dtype(const Tensor& x, const char* what) {
+  STD_TORCH_CHECK(x.is_cuda(), "audio_amd: ", what, " must be on an MI355X (ROCm) device; there is no CPU kernel");
+  switch (x.scalar_type()) {
+    case ScalarType::Float: return AAMD_SA_F32;
+    case ScalarType::Double: return AAMD_SA_F64;
+    case ScalarType::Half: return AAMD_SA_F16;
+    case ScalarType::BFloat16: return AAMD_SA_BF16;
+    default: break;
+  }
+  STD_TORCH_CHECK(false, "audio_amd: ", what, " must be float16, bfloat16, float32 or float64");
+  return -1;
+}
+
+// the window and the twiddle table of an n_fft-point transform, of dtype st, on ref's device
+void stft_consts(const Tensor& ref, const Tensor& window, const Tensor& twiddle, int64_t n_fft, ScalarType st) {
+  want_dev(window, st, "window", 1);
+  want_dev(twiddle, st, "twiddle");
+  same_device(ref, window);
+  same_device(ref, twiddle);
+  STD_TORCH_CHECK(window.numel() == n_fft && twiddle.numel() == 2 * n_fft, "audio_amd: window / twiddle size");
+}
+
+// `rows` dense rows of `length` samples
+aamd_stft_desc dense_desc(int64_t rows, int64_t length, int64_t n_fft, int64_t hop, int64_t pad, bool center, int64_t pad_mode,
+                          bool onesided, int64_t n_frames, double scale, double power) {
   aamd_stft_desc d{};
-  d.rows = wav.size(0);
-  d.length = wav.size(1);
-  d.row_stride = d.rows > 1 ? wav.stride(0) : (d.length > 0 ? d.length : 1);
+  d.rows = rows;
+  d.length = length;
+  d.row_stride = length > 0 ? length : 1;
   d.n_fft = (int32_t)n_fft;
   d.hop = (int32_t)hop;
   d.pad = (int32_t)pad;
@@ -91,6 +121,38 @@ aamd_stft_desc make_desc(const Tensor& wav, int64_t n_fft, int64_t hop, int64_t 
   d.scale = (float)scale;
   d.power = (float)power;
   return d;
+}
+
+aamd_stft_desc make_desc(const Tensor& wav, int64_t n_fft, int64_t hop, int64_t pad, bool center, int64_t pad_mode,
+                         bool onesided, int64_t n_frames, double scale, double power) {
+  // rows may be a strided view of longer rows (a batch sliced in time): unit stride along time is what the kernels need
+  STD_TORCH_CHECK(wav.is_cuda(), "audio_amd: waveform must be on an MI355X (ROCm) device; there is no CPU kernel");
+  STD_TORCH_CHECK(wav.scalar_type() == ScalarType::Float, "audio_amd: waveform must be float32");
+  STD_TORCH_CHECK(wav.dim() == 2, "audio_amd: waveform must be (rows, time)");
+  STD_TORCH_CHECK(wav.size(1) <= 1 || wav.stride(1) == 1, "audio_amd: waveform rows must have unit stride");
+  STD_TORCH_CHECK(wav.size(0) <= 1 || wav.stride(0) >= wav.size(1), "audio_amd: overlapping waveform rows");
+  aamd_stft_desc d = dense_desc(wav.size(0), wav.size(1), n_fft, hop, pad, center, pad_mode, onesided, n_frames, scale, power);
+  if (d.rows > 1) d.row_stride = wav.stride(0);
+  return d;
+}
+
+// the running maximum of the dB cut-off groups: float32, one entry per `group` of the `count` items, updated in place
+float* group_max_of(const Tensor& ref, Tensor& group_max, int64_t group, int64_t count) {
+  want_f32(group_max, "group_max", 1);
+  same_device(ref, group_max);
+  STD_TORCH_CHECK(group > 0 && group_max.numel() * group >= count, "audio_amd: group_max too small");
+  return mut<float>(group_max);
+}
+float* group_max_of(const Tensor& ref, std::optional<Tensor>& group_max, int64_t group, int64_t count) {
+  return group_max.has_value() ? group_max_of(ref, *group_max, group, count) : nullptr;
+}
+
+// an optional map from output row to operand row (a broadcast operand of the convolutions): int64[rows] on the device
+const int64_t* row_map(const std::optional<Tensor>& m, int64_t rows, const char* what) {
+  if (!m.has_value()) return nullptr;
+  STD_TORCH_CHECK(m->is_cuda() && m->scalar_type() == ScalarType::Long && m->is_contiguous() && m->dim() == 1 && m->numel() == rows,
+                  "audio_amd: ", what, " must be int64[rows] on the device");
+  return static_cast<const int64_t*>(m->data_ptr());
 }
 
 struct Bands {
@@ -108,7 +170,7 @@ struct Bands {
     b.max_width = (int32_t)weights.size(1);
     b.lo = static_cast<const int32_t*>(lo.data_ptr());
     b.width = static_cast<const int32_t*>(width.data_ptr());
-    b.weights = fp(weights);
+    b.weights = ptr<float>(weights);
     b.lane_order = nullptr;
     if (lane_order.has_value()) {
       want_i32(*lane_order, "lane_order");
@@ -121,7 +183,7 @@ struct Bands {
       same_device(wav, *table400);
       STD_TORCH_CHECK(table400->numel() == aamd_mel400_table_dwords(b.n_mels, b.max_width),
                       "audio_amd: table400 does not belong to this band table");
-      b.table400 = fp(*table400);
+      b.table400 = ptr<float>(*table400);
     }
     b.table_sig = b.table400 ? (int32_t)table_sig : 0;     // (the kernel verifies it against the table and traps on a mismatch)
   }
@@ -131,15 +193,11 @@ struct Bands {
 Tensor spectrogram(Tensor wav, Tensor window, Tensor twiddle, int64_t n_fft, int64_t hop, int64_t pad, bool center,
                    int64_t pad_mode, bool onesided, int64_t n_frames, double scale, double power) {
   aamd_stft_desc d = make_desc(wav, n_fft, hop, pad, center, pad_mode, onesided, n_frames, scale, power);
-  want_f32(window, "window", 1);
-  want_f32(twiddle, "twiddle");
-  same_device(wav, window);
-  same_device(wav, twiddle);
-  STD_TORCH_CHECK(window.numel() == n_fft && twiddle.numel() == 2 * n_fft, "audio_amd: window / twiddle size");
+  stft_consts(wav, window, twiddle, n_fft, ScalarType::Float);
   const torch::stable::accelerator::DeviceGuard guard(wav.get_device_index());
   const int64_t n_freq = onesided ? n_fft / 2 + 1 : n_fft;
   Tensor out = torch::stable::new_empty(wav, {d.rows, n_frames, n_freq * (power > 0.0 ? 1 : 2)});
-  if (out.numel()) check(aamd_spectrogram_f32(fp(wav), fp(window), fp(twiddle), fpm(out), &d, current_stream(wav)));
+  if (out.numel()) check(aamd_spectrogram_f32(ptr<float>(wav), ptr<float>(window), ptr<float>(twiddle), mut<float>(out), &d, current_stream(wav)));
   return out;
 }
 
@@ -148,16 +206,12 @@ Tensor mel_spectrogram(Tensor wav, Tensor window, Tensor twiddle, Tensor band_lo
                        std::optional<Tensor> lane_order, std::optional<Tensor> table400, int64_t n_fft, int64_t hop, int64_t pad, bool center,
                        int64_t pad_mode, int64_t n_frames, double scale, double power, int64_t table_sig) {
   aamd_stft_desc d = make_desc(wav, n_fft, hop, pad, center, pad_mode, true, n_frames, scale, power);
-  want_f32(window, "window", 1);
-  want_f32(twiddle, "twiddle");
-  same_device(wav, window);
-  same_device(wav, twiddle);
-  STD_TORCH_CHECK(window.numel() == n_fft && twiddle.numel() == 2 * n_fft, "audio_amd: window / twiddle size");
+  stft_consts(wav, window, twiddle, n_fft, ScalarType::Float);
   Bands bands(wav, band_lo, band_width, band_weights, lane_order, table400, table_sig);
   const torch::stable::accelerator::DeviceGuard guard(wav.get_device_index());
   Tensor out = torch::stable::new_empty(wav, {d.rows, n_frames, (int64_t)bands.b.n_mels});
   if (out.numel())
-    check(aamd_melspectrogram_f32(fp(wav), fp(window), fp(twiddle), &bands.b, fpm(out), &d, current_stream(wav)));
+    check(aamd_melspectrogram_f32(ptr<float>(wav), ptr<float>(window), ptr<float>(twiddle), &bands.b, mut<float>(out), &d, current_stream(wav)));
   return out;
 }
 
@@ -168,22 +222,13 @@ Tensor mel_spectrogram_db(Tensor wav, Tensor window, Tensor twiddle, Tensor band
                           double amin, double db_multiplier, std::optional<Tensor> group_max, int64_t rows_per_group,
                           int64_t table_sig) {
   aamd_stft_desc d = make_desc(wav, n_fft, hop, pad, center, pad_mode, true, n_frames, scale, power);
-  want_f32(window, "window", 1);
-  want_f32(twiddle, "twiddle");
-  same_device(wav, window);
-  same_device(wav, twiddle);
+  stft_consts(wav, window, twiddle, n_fft, ScalarType::Float);
   Bands bands(wav, band_lo, band_width, band_weights, lane_order, table400, table_sig);
-  float* gmax = nullptr;
-  if (group_max.has_value()) {
-    want_f32(*group_max, "group_max", 1);
-    same_device(wav, *group_max);
-    STD_TORCH_CHECK(rows_per_group > 0 && group_max->numel() * rows_per_group >= d.rows, "audio_amd: group_max too small");
-    gmax = fpm(*group_max);
-  }
+  float* gmax = group_max_of(wav, group_max, rows_per_group, d.rows);
   const torch::stable::accelerator::DeviceGuard guard(wav.get_device_index());
   Tensor out = torch::stable::new_empty(wav, {d.rows, n_frames, (int64_t)bands.b.n_mels});
   if (out.numel())
-    check(aamd_melspectrogram_db_f32(fp(wav), fp(window), fp(twiddle), &bands.b, fpm(out), &d, (float)multiplier,
+    check(aamd_melspectrogram_db_f32(ptr<float>(wav), ptr<float>(window), ptr<float>(twiddle), &bands.b, mut<float>(out), &d, (float)multiplier,
                                      (float)amin, (float)db_multiplier, gmax, rows_per_group, current_stream(wav)));
   return out;
 }
@@ -195,16 +240,11 @@ Tensor mfcc_dct(Tensor mel, Tensor dct, int64_t log_mode, std::optional<Tensor> 
   want_f32(dct, "dct_mat", 2);
   same_device(mel, dct);
   STD_TORCH_CHECK(dct.size(0) == mel.size(1), "audio_amd: dct_mat rows must equal n_mels");
-  const float* gmax = nullptr;
-  if (group_max.has_value()) {
-    want_f32(*group_max, "group_max", 1);
-    same_device(mel, *group_max);
-    gmax = fp(*group_max);
-  }
+  const float* gmax = group_max_of(mel, group_max, vec_per_group, mel.size(0));
   const torch::stable::accelerator::DeviceGuard guard(mel.get_device_index());
   Tensor out = torch::stable::new_empty(mel, {mel.size(0), dct.size(1)});
   if (out.numel())
-    check(aamd_mfcc_dct_f32(fp(mel), fp(dct), fpm(out), mel.size(0), (int32_t)mel.size(1), (int32_t)dct.size(1),
+    check(aamd_mfcc_dct_f32(ptr<float>(mel), ptr<float>(dct), mut<float>(out), mel.size(0), (int32_t)mel.size(1), (int32_t)dct.size(1),
                             (int32_t)log_mode, gmax, vec_per_group > 0 ? vec_per_group : 1, (float)top_db,
                             current_stream(mel)));
   return out;
@@ -212,34 +252,48 @@ Tensor mfcc_dct(Tensor mel, Tensor dct, int64_t log_mode, std::optional<Tensor> 
 
 // ---- aamd::resample  (functional/functional.py:1421-1428) ----------------------------------------------------------
 // `frag`: the prepared tap fragments of aamd::resample_frag_build for the same kernel values and band table (ABI 7), or none
-Tensor resample(Tensor wav, Tensor kernel, int64_t orig, int64_t new_, int64_t width, int64_t out_len,
-                std::optional<std::vector<int64_t>> band_tap_lo, int64_t tap_span, std::optional<Tensor> frag) {
-  want_f32(wav, "waveform", 2);
-  want_f32(kernel, "kernel", 2);
+template <typename T>
+void resample_check(const Tensor& wav, const Tensor& kernel, int64_t orig, int64_t new_, int64_t width) {
+  want_dev(wav, scalar_of<T>, "waveform", 2);
+  want_dev(kernel, scalar_of<T>, "kernel", 2);
   same_device(wav, kernel);
-  if (frag.has_value()) same_device(wav, *frag);
   STD_TORCH_CHECK(kernel.size(0) == new_ && kernel.size(1) == 2 * width + orig,
                   "audio_amd: resample kernel shape does not match (new, 2*width+orig)");
+}
+// without a band table: aamd::resample_f64, and aamd::resample when the host has none
+template <typename T>
+Tensor resample_unbanded(Tensor wav, Tensor kernel, int64_t orig, int64_t new_, int64_t width, int64_t out_len) {
+  resample_check<T>(wav, kernel, orig, new_, width);
   const torch::stable::accelerator::DeviceGuard guard(wav.get_device_index());
   Tensor out = torch::stable::new_empty(wav, {wav.size(0), out_len});
   if (out.numel()) {
     const int64_t length = wav.size(1);
-    if (band_tap_lo.has_value()) {
-      std::vector<int32_t> lo(band_tap_lo->begin(), band_tap_lo->end());
-      aamd_resample_bands bands{(int32_t)lo.size(), (int32_t)tap_span, lo.data()};
-      const void* fr = nullptr;
-      if (frag.has_value()) {
-        STD_TORCH_CHECK(frag->is_contiguous() && (int64_t)(frag->numel() * frag->element_size()) >=
-                            aamd_resample_frag_bytes((int32_t)orig, (int32_t)new_, &bands),
-                        "audio_amd: prepared tap fragments too small for this band table");
-        fr = frag->data_ptr();
-      }
-      check(aamd_resample_prepared_f32(fp(wav), fp(kernel), fpm(out), wav.size(0), length, length > 0 ? length : 1,
-                                       (int32_t)orig, (int32_t)new_, (int32_t)width, out_len, &bands, fr, current_stream(wav)));
-    } else {
-      check(aamd_resample_f32(fp(wav), fp(kernel), fpm(out), wav.size(0), length, length > 0 ? length : 1, (int32_t)orig,
-                              (int32_t)new_, (int32_t)width, out_len, current_stream(wav)));
+    check(pick<T>(aamd_resample_f32, aamd_resample_f64)(ptr<T>(wav), ptr<T>(kernel), mut<T>(out), wav.size(0), length,
+                                                        length > 0 ? length : 1, (int32_t)orig, (int32_t)new_, (int32_t)width,
+                                                        out_len, current_stream(wav)));
+  }
+  return out;
+}
+Tensor resample(Tensor wav, Tensor kernel, int64_t orig, int64_t new_, int64_t width, int64_t out_len,
+                std::optional<std::vector<int64_t>> band_tap_lo, int64_t tap_span, std::optional<Tensor> frag) {
+  if (frag.has_value()) same_device(wav, *frag);
+  if (!band_tap_lo.has_value()) return resample_unbanded<float>(wav, kernel, orig, new_, width, out_len);
+  resample_check<float>(wav, kernel, orig, new_, width);
+  const torch::stable::accelerator::DeviceGuard guard(wav.get_device_index());
+  Tensor out = torch::stable::new_empty(wav, {wav.size(0), out_len});
+  if (out.numel()) {
+    const int64_t length = wav.size(1);
+    std::vector<int32_t> lo(band_tap_lo->begin(), band_tap_lo->end());
+    aamd_resample_bands bands{(int32_t)lo.size(), (int32_t)tap_span, lo.data()};
+    const void* fr = nullptr;
+    if (frag.has_value()) {
+      STD_TORCH_CHECK(frag->is_contiguous() && (int64_t)(frag->numel() * frag->element_size()) >=
+                          aamd_resample_frag_bytes((int32_t)orig, (int32_t)new_, &bands),
+                      "audio_amd: prepared tap fragments too small for this band table");
+      fr = frag->data_ptr();
     }
+    check(aamd_resample_prepared_f32(ptr<float>(wav), ptr<float>(kernel), mut<float>(out), wav.size(0), length, length > 0 ? length : 1,
+                                     (int32_t)orig, (int32_t)new_, (int32_t)width, out_len, &bands, fr, current_stream(wav)));
   }
   return out;
 }
@@ -255,16 +309,17 @@ Tensor resample_frag_build(Tensor kernel, int64_t orig, int64_t new_, int64_t wi
   const int64_t bytes = aamd_resample_frag_bytes((int32_t)orig, (int32_t)new_, &bands);
   STD_TORCH_CHECK(bytes > 0, "audio_amd: no matrix-core resampling kernel serves this band table (no fragments to prepare)");
   Tensor out = torch::stable::new_empty(kernel, {bytes / 4});          // float32 storage holding the packed dwords
-  check(aamd_resample_frag_build_f32(fp(kernel), (int32_t)orig, (int32_t)new_, (int32_t)width, &bands, out.data_ptr(),
+  check(aamd_resample_frag_build_f32(ptr<float>(kernel), (int32_t)orig, (int32_t)new_, (int32_t)width, &bands, out.data_ptr(),
                                      current_stream(kernel)));
   return out;
 }
 
 // ---- aamd::lfilter  (functional/filtering.py:1027-1099; cascades fused) --------------------------------------------
-Tensor lfilter(Tensor x, Tensor a, Tensor b, int64_t n_stages, int64_t clamp) {   // clamp: 0 / 1 every stage / 2 last stage
-  want_f32(x, "waveform", 3);
-  want_f32(a, "a_coeffs", 3);
-  want_f32(b, "b_coeffs", 3);
+template <typename T>
+Tensor lfilter_any(Tensor x, Tensor a, Tensor b, int64_t n_stages, int64_t clamp) {   // clamp: 0 / 1 every stage / 2 last stage
+  want_dev(x, scalar_of<T>, "waveform", 3);
+  want_dev(a, scalar_of<T>, "a_coeffs", 3);
+  want_dev(b, scalar_of<T>, "b_coeffs", 3);
   same_device(x, a);
   same_device(x, b);
   STD_TORCH_CHECK(a.size(0) == n_stages && b.size(0) == n_stages && a.size(1) == b.size(1) && a.size(2) == b.size(2),
@@ -274,9 +329,13 @@ Tensor lfilter(Tensor x, Tensor a, Tensor b, int64_t n_stages, int64_t clamp) { 
   const torch::stable::accelerator::DeviceGuard guard(x.get_device_index());
   Tensor y = torch::stable::empty_like(x);
   if (y.numel())
-    check(aamd_lfilter_f32(fp(x), fp(a), fp(b), fpm(y), x.size(0), (int32_t)x.size(1), x.size(2), (int32_t)a.size(2),
-                           (int32_t)a.size(1), (int32_t)n_stages, (int32_t)clamp, current_stream(x)));
+    check(pick<T>(aamd_lfilter_f32, aamd_lfilter_f64)(ptr<T>(x), ptr<T>(a), ptr<T>(b), mut<T>(y), x.size(0), (int32_t)x.size(1),
+                                                      x.size(2), (int32_t)a.size(2), (int32_t)a.size(1), (int32_t)n_stages,
+                                                      (int32_t)clamp, current_stream(x)));
   return y;
+}
+Tensor lfilter(Tensor x, Tensor a, Tensor b, int64_t n_stages, int64_t clamp) {
+  return lfilter_any<float>(x, a, b, n_stages, clamp);
 }
 
 // ---- aamd::fftconvolve  (functional/functional.py:2252-2258) -------------------------------------------------------
@@ -285,25 +344,15 @@ Tensor fftconvolve(Tensor x, Tensor y, std::optional<Tensor> x_row_of, std::opti
   want_f32(x, "x", 2);
   want_f32(y, "y", 2);
   same_device(x, y);
-  const int64_t* xm = nullptr;
-  const int64_t* ym = nullptr;
-  if (x_row_of.has_value()) {
-    STD_TORCH_CHECK(x_row_of->is_cuda() && x_row_of->scalar_type() == ScalarType::Long && x_row_of->numel() == rows,
-                    "audio_amd: x_row_of must be int64[rows] on the device");
-    xm = static_cast<const int64_t*>(x_row_of->data_ptr());
-  }
-  if (y_row_of.has_value()) {
-    STD_TORCH_CHECK(y_row_of->is_cuda() && y_row_of->scalar_type() == ScalarType::Long && y_row_of->numel() == rows,
-                    "audio_amd: y_row_of must be int64[rows] on the device");
-    ym = static_cast<const int64_t*>(y_row_of->data_ptr());
-  }
+  const int64_t* xm = row_map(x_row_of, rows, "x_row_of");
+  const int64_t* ym = row_map(y_row_of, rows, "y_row_of");
   const torch::stable::accelerator::DeviceGuard guard(x.get_device_index());
   Tensor out = torch::stable::new_empty(x, {rows, out_len});
   if (out.numel()) {
     const int64_t ws_bytes = aamd_fftconvolve_workspace(rows, x.size(0), y.size(0), x.size(1), y.size(1));
     STD_TORCH_CHECK(ws_bytes >= 0, aamd_last_error());
     Tensor ws = torch::stable::new_empty(x, {(ws_bytes + 3) / 4 + 2});
-    check(aamd_fftconvolve_f32(fp(x), fp(y), fpm(out), rows, x.size(0), y.size(0), x.size(1), y.size(1), xm, ym, start,
+    check(aamd_fftconvolve_f32(ptr<float>(x), ptr<float>(y), mut<float>(out), rows, x.size(0), y.size(0), x.size(1), y.size(1), xm, ym, start,
                                out_len, ws_bytes ? ws.data_ptr() : nullptr, current_stream(x)));
   }
   return out;
@@ -320,18 +369,8 @@ Tensor fftconvolve_staged(Tensor x, Tensor y, std::optional<Tensor> x_row_of, st
   want_f32(workspace, "workspace", 1);
   same_device(x, y);
   same_device(x, workspace);
-  const int64_t* xm = nullptr;
-  const int64_t* ym = nullptr;
-  if (x_row_of.has_value()) {
-    STD_TORCH_CHECK(x_row_of->is_cuda() && x_row_of->scalar_type() == ScalarType::Long && x_row_of->numel() == rows,
-                    "audio_amd: x_row_of must be int64[rows] on the device");
-    xm = static_cast<const int64_t*>(x_row_of->data_ptr());
-  }
-  if (y_row_of.has_value()) {
-    STD_TORCH_CHECK(y_row_of->is_cuda() && y_row_of->scalar_type() == ScalarType::Long && y_row_of->numel() == rows,
-                    "audio_amd: y_row_of must be int64[rows] on the device");
-    ym = static_cast<const int64_t*>(y_row_of->data_ptr());
-  }
+  const int64_t* xm = row_map(x_row_of, rows, "x_row_of");
+  const int64_t* ym = row_map(y_row_of, rows, "y_row_of");
   const torch::stable::accelerator::DeviceGuard guard(x.get_device_index());
   Tensor out = torch::stable::new_empty(x, {(stages & AAMD_FFTCONV_RUN) ? rows : 0, out_len});
   if (rows * out_len) {
@@ -339,7 +378,7 @@ Tensor fftconvolve_staged(Tensor x, Tensor y, std::optional<Tensor> x_row_of, st
     STD_TORCH_CHECK(ws_bytes >= 0, aamd_last_error());
     STD_TORCH_CHECK(workspace.numel() * 4 >= ws_bytes, "audio_amd: workspace smaller than aamd_fftconvolve_workspace()");
     STD_TORCH_CHECK(reinterpret_cast<uintptr_t>(workspace.data_ptr()) % 8 == 0, "audio_amd: workspace must be 8-byte aligned");
-    check(aamd_fftconvolve_staged_f32(fp(x), fp(y), out.numel() ? fpm(out) : nullptr, rows, x.size(0), y.size(0), x.size(1),
+    check(aamd_fftconvolve_staged_f32(ptr<float>(x), ptr<float>(y), out.numel() ? mut<float>(out) : nullptr, rows, x.size(0), y.size(0), x.size(1),
                                       y.size(1), xm, ym, start, out_len, ws_bytes ? workspace.data_ptr() : nullptr,
                                       (int32_t)stages, current_stream(x)));
   }
@@ -352,22 +391,6 @@ Tensor fftconvolve_staged(Tensor x, Tensor y, std::optional<Tensor> x_row_of, st
 // mechanism (lfilter.cpp:118-138) is one op per native entry.  Same rules as above: validate like iir_cuda.cu:41-65,
 // allocate through torch, current stream of the tensor's device, raw pointers into the C ABI.
 // =====================================================================================================================
-void want_dev(const Tensor& t, ScalarType st, const char* what, int64_t dim = -1) {
-  STD_TORCH_CHECK(t.is_cuda(), "audio_amd: ", what, " must be on an MI355X (ROCm) device; there is no CPU kernel");
-  STD_TORCH_CHECK(t.scalar_type() == st, "audio_amd: ", what, " has the wrong dtype");
-  STD_TORCH_CHECK(t.is_contiguous(), "audio_amd: ", what, " must be contiguous");
-  if (dim >= 0) STD_TORCH_CHECK(t.dim() == dim, "audio_amd: ", what, " must have ", dim, " dimensions");
-}
-const double* dp(const Tensor& t) { return t.numel() ? static_cast<const double*>(t.data_ptr()) : nullptr; }
-double* dpm(Tensor& t) { return t.numel() ? static_cast<double*>(t.data_ptr()) : nullptr; }
-
-void stft_consts(const Tensor& ref, const Tensor& window, const Tensor& twiddle, int64_t n_fft, ScalarType st) {
-  want_dev(window, st, "window", 1);
-  want_dev(twiddle, st, "twiddle");
-  same_device(ref, window);
-  same_device(ref, twiddle);
-  STD_TORCH_CHECK(window.numel() == n_fft && twiddle.numel() == 2 * n_fft, "audio_amd: window / twiddle size");
-}
 
 // ---- aamd::mel_spectrogram_lognorm / _pcm16 (pipelines/rnnt_pipeline.py:16-47, 319-326 fused; _torchcodec.py:150-152) ----
 // wav: float32 (rows, time) | int16 (rows, time) planar PCM | int16 (clips, time, channels) interleaved PCM (channels 1 / 2).
@@ -389,19 +412,15 @@ Tensor mel_spectrogram_lognorm(Tensor wav, Tensor window, Tensor twiddle, Tensor
   STD_TORCH_CHECK(mean.has_value() == invstddev.has_value(), "audio_amd: mean and invstddev come together");
   STD_TORCH_CHECK(pcm || mean.has_value(), "audio_amd: float input without statistics is aamd::mel_spectrogram");
   stft_consts(wav, window, twiddle, n_fft, ScalarType::Float);
-  aamd_stft_desc d{};
-  d.rows = channels ? wav.size(0) * channels : wav.size(0);
-  d.length = wav.size(1);
-  d.row_stride = d.length > 0 ? d.length : 1;
-  d.n_fft = (int32_t)n_fft; d.hop = (int32_t)hop; d.pad = 0; d.center = 1; d.pad_mode = AAMD_PAD_REFLECT; d.onesided = 1;
-  d.n_frames = (int32_t)n_frames; d.scale = (float)scale; d.power = 2.0f;
+  aamd_stft_desc d = dense_desc(channels ? wav.size(0) * channels : wav.size(0), wav.size(1), n_fft, hop, 0, true,
+                                AAMD_PAD_REFLECT, true, n_frames, scale, 2.0);
   Bands bands(wav, band_lo, band_width, band_weights, lane_order, table400, table_sig);
   const float *mp = nullptr, *ip = nullptr;
   if (mean.has_value()) {
     want_f32(*mean, "mean", 1); want_f32(*invstddev, "invstddev", 1);
     same_device(wav, *mean); same_device(wav, *invstddev);
     STD_TORCH_CHECK(mean->numel() == bands.b.n_mels && invstddev->numel() == bands.b.n_mels, "audio_amd: statistics must have n_mels entries");
-    mp = fp(*mean); ip = fp(*invstddev);
+    mp = ptr<float>(*mean); ip = ptr<float>(*invstddev);
   }
   const int64_t frames = mean.has_value() ? out_frames : n_frames;
   STD_TORCH_CHECK(frames >= n_frames, "audio_amd: out_frames must be >= n_frames");
@@ -414,13 +433,13 @@ Tensor mel_spectrogram_lognorm(Tensor wav, Tensor window, Tensor twiddle, Tensor
   if (out.numel() && n_frames > 0) {
     void* st = current_stream(wav);
     if (!pcm)
-      check(aamd_melspectrogram_lognorm_f32(fp(wav), fp(window), fp(twiddle), &bands.b, fpm(out), &d, (float)gain, mp, ip, frames, st));
+      check(aamd_melspectrogram_lognorm_f32(ptr<float>(wav), ptr<float>(window), ptr<float>(twiddle), &bands.b, mut<float>(out), &d, (float)gain, mp, ip, frames, st));
     else if (channels)
-      check(aamd_melspectrogram_pcm16_interleaved_f32(static_cast<const int16_t*>(wav.data_ptr()), (int32_t)channels, fp(window),
-                                                      fp(twiddle), &bands.b, fpm(out), &d, (float)gain, mp, ip, frames, st));
+      check(aamd_melspectrogram_pcm16_interleaved_f32(static_cast<const int16_t*>(wav.data_ptr()), (int32_t)channels, ptr<float>(window),
+                                                      ptr<float>(twiddle), &bands.b, mut<float>(out), &d, (float)gain, mp, ip, frames, st));
     else
-      check(aamd_melspectrogram_pcm16_f32(static_cast<const int16_t*>(wav.data_ptr()), fp(window), fp(twiddle), &bands.b,
-                                          fpm(out), &d, (float)gain, mp, ip, frames, st));
+      check(aamd_melspectrogram_pcm16_f32(static_cast<const int16_t*>(wav.data_ptr()), ptr<float>(window), ptr<float>(twiddle), &bands.b,
+                                          mut<float>(out), &d, (float)gain, mp, ip, frames, st));
   }
   return out;
 }
@@ -431,7 +450,7 @@ Tensor mfcc_frag_build(Tensor dct, int64_t n_mels, int64_t n_mfcc) {
   STD_TORCH_CHECK(dct.size(0) == n_mels && dct.size(1) == n_mfcc, "audio_amd: dct_mat must be (n_mels, n_mfcc)");
   const torch::stable::accelerator::DeviceGuard guard(dct.get_device_index());
   Tensor frag = torch::stable::new_empty(dct, {(int64_t)aamd_mfcc_frag_floats()});
-  check(aamd_mfcc_frag_build(fp(dct), (int32_t)n_mels, (int32_t)n_mfcc, fpm(frag), current_stream(dct)));
+  check(aamd_mfcc_frag_build(ptr<float>(dct), (int32_t)n_mels, (int32_t)n_mfcc, mut<float>(frag), current_stream(dct)));
   return frag;
 }
 // Single-rank form (no exchange of group_max between the passes): both passes in one op.
@@ -445,10 +464,9 @@ Tensor mfcc_fused(Tensor wav, Tensor window, Tensor twiddle, Tensor band_lo, Ten
   aamd_stft_desc d = make_desc(wav, n_fft, hop, pad, center, pad_mode, true, n_frames, scale, 2.0);
   stft_consts(wav, window, twiddle, n_fft, ScalarType::Float);
   want_f32(dct_frag, "dct_frag", 1);
-  want_f32(group_max, "group_max", 1);
-  same_device(wav, dct_frag); same_device(wav, group_max);
+  same_device(wav, dct_frag);
   STD_TORCH_CHECK(dct_frag.numel() == aamd_mfcc_frag_floats(), "audio_amd: dct_frag comes from aamd::mfcc_frag_build");
-  STD_TORCH_CHECK(rows_per_group > 0 && group_max.numel() * rows_per_group >= d.rows, "audio_amd: group_max too small");
+  float* gmax = group_max_of(wav, group_max, rows_per_group, d.rows);
   Bands bands(wav, band_lo, band_width, band_weights, lane_order, table400, table_sig);
   STD_TORCH_CHECK(aamd_mfcc_fused_supported(&d, &bands.b, (int32_t)n_mfcc), "audio_amd: shape not served by the fused MFCC "
                   "(n_fft 400, hop 100 / 160 / 200, 80 mels, n_mfcc <= 48 and a multiple of 4)");
@@ -457,17 +475,17 @@ Tensor mfcc_fused(Tensor wav, Tensor window, Tensor twiddle, Tensor band_lo, Ten
   if (!out.numel()) return out;
   const int64_t tiles = aamd_mfcc_fused_tiles(&d);
   Tensor scratch = torch::stable::new_empty(wav, {2 * tiles + 1});
-  float* sp = fpm(scratch);
+  float* sp = mut<float>(scratch);
   aamd_mfcc_fused f{};
-  f.dct_frag = fp(dct_frag); f.n_mfcc = (int32_t)n_mfcc; f.pass = 0;
+  f.dct_frag = ptr<float>(dct_frag); f.n_mfcc = (int32_t)n_mfcc; f.pass = 0;
   f.multiplier = (float)multiplier; f.amin = (float)amin; f.db_multiplier = (float)db_multiplier; f.top_db = (float)top_db;
-  f.group_max = fpm(group_max); f.rows_per_group = rows_per_group;
+  f.group_max = gmax; f.rows_per_group = rows_per_group;
   f.tile_min = sp; f.tile_list = reinterpret_cast<int32_t*>(sp + tiles);
   f.fix_count = reinterpret_cast<int32_t*>(sp + 2 * tiles);
   void* st = current_stream(wav);
-  check(aamd_mfcc_fused_f32(fp(wav), fp(window), fp(twiddle), &bands.b, fpm(out), &d, &f, st));
+  check(aamd_mfcc_fused_f32(ptr<float>(wav), ptr<float>(window), ptr<float>(twiddle), &bands.b, mut<float>(out), &d, &f, st));
   f.pass = 1;
-  check(aamd_mfcc_fused_f32(fp(wav), fp(window), fp(twiddle), &bands.b, fpm(out), &d, &f, st));
+  check(aamd_mfcc_fused_f32(ptr<float>(wav), ptr<float>(window), ptr<float>(twiddle), &bands.b, mut<float>(out), &d, &f, st));
   return out;
 }
 
@@ -475,8 +493,8 @@ Tensor mfcc_fused(Tensor wav, Tensor window, Tensor twiddle, Tensor band_lo, Ten
 template <typename T>
 Tensor istft_any(Tensor spec, Tensor window, Tensor twiddle, std::optional<Tensor> inv_envelope, int64_t n_fft, int64_t hop,
                  int64_t pad, bool center, int64_t pad_mode, int64_t length, double scale, bool adjoint) {
-  constexpr ScalarType st = std::is_same<T, double>::value ? ScalarType::Double : ScalarType::Float;
-  want_dev(spec, st, "spec", 4);                         // (rows, n_frames, n_fft / 2 + 1, 2): view_as_real of the complex frames
+  constexpr ScalarType st = scalar_of<T>;
+  want_dev(spec, st, "spec", 4);                        // (rows, n_frames, n_fft / 2 + 1, 2): view_as_real of the complex frames
   STD_TORCH_CHECK(spec.size(2) == n_fft / 2 + 1 && spec.size(3) == 2, "audio_amd: spec must be (rows, frames, n_fft / 2 + 1, 2)");
   stft_consts(spec, window, twiddle, n_fft, st);
   const T* env = nullptr;
@@ -486,18 +504,12 @@ Tensor istft_any(Tensor spec, Tensor window, Tensor twiddle, std::optional<Tenso
     STD_TORCH_CHECK(inv_envelope->numel() == length, "audio_amd: inv_envelope must have `length` entries");
     env = static_cast<const T*>(inv_envelope->data_ptr());
   }
-  aamd_stft_desc d{};
-  d.rows = spec.size(0); d.length = length; d.row_stride = length > 0 ? length : 1;
-  d.n_fft = (int32_t)n_fft; d.hop = (int32_t)hop; d.pad = (int32_t)pad; d.center = center; d.pad_mode = (int32_t)pad_mode;
-  d.onesided = 1; d.n_frames = (int32_t)spec.size(1); d.scale = (float)scale; d.power = 0.0f;
+  aamd_stft_desc d = dense_desc(spec.size(0), length, n_fft, hop, pad, center, pad_mode, true, spec.size(1), scale, 0.0);
   const torch::stable::accelerator::DeviceGuard guard(spec.get_device_index());
   Tensor out = torch::stable::new_zeros(window, {d.rows, length});     // the kernel accumulates with atomic adds
-  if (out.numel() && d.n_frames) {
-    if constexpr (std::is_same<T, double>::value)
-      check(aamd_istft_f64(dp(spec), dp(window), dp(twiddle), env, dpm(out), &d, adjoint ? 1 : 0, current_stream(spec)));
-    else
-      check(aamd_istft_f32(fp(spec), fp(window), fp(twiddle), env, fpm(out), &d, adjoint ? 1 : 0, current_stream(spec)));
-  }
+  if (out.numel() && d.n_frames)
+    check(pick<T>(aamd_istft_f32, aamd_istft_f64)(ptr<T>(spec), ptr<T>(window), ptr<T>(twiddle), env, mut<T>(out), &d,
+                                                  adjoint ? 1 : 0, current_stream(spec)));
   return out;
 }
 Tensor istft(Tensor spec, Tensor window, Tensor twiddle, std::optional<Tensor> inv_envelope, int64_t n_fft, int64_t hop,
@@ -514,13 +526,10 @@ Tensor spectrogram_f64(Tensor wav, Tensor window, Tensor twiddle, int64_t n_fft,
                        int64_t pad_mode, int64_t n_frames) {
   want_dev(wav, ScalarType::Double, "waveform", 2);
   stft_consts(wav, window, twiddle, n_fft, ScalarType::Double);
-  aamd_stft_desc d{};
-  d.rows = wav.size(0); d.length = wav.size(1); d.row_stride = d.length > 0 ? d.length : 1;
-  d.n_fft = (int32_t)n_fft; d.hop = (int32_t)hop; d.pad = (int32_t)pad; d.center = center; d.pad_mode = (int32_t)pad_mode;
-  d.onesided = 1; d.n_frames = (int32_t)n_frames; d.scale = 1.0f; d.power = 0.0f;
+  aamd_stft_desc d = dense_desc(wav.size(0), wav.size(1), n_fft, hop, pad, center, pad_mode, true, n_frames, 1.0, 0.0);
   const torch::stable::accelerator::DeviceGuard guard(wav.get_device_index());
   Tensor out = torch::stable::new_empty(wav, {d.rows, n_frames, n_fft / 2 + 1, 2});
-  if (out.numel()) check(aamd_spectrogram_f64(dp(wav), dp(window), dp(twiddle), dpm(out), &d, current_stream(wav)));
+  if (out.numel()) check(aamd_spectrogram_f64(ptr<double>(wav), ptr<double>(window), ptr<double>(twiddle), mut<double>(out), &d, current_stream(wav)));
   return out;
 }
 
@@ -548,7 +557,7 @@ Tensor phase_vocoder(Tensor spec, Tensor phase_advance, double rate, bool frame_
     v.out_stride_freq = frame_major_out ? 1 : n_out;
     v.out_stride_frame = frame_major_out ? n_freq : 1;
     v.rate = rate;
-    check(aamd_phase_vocoder_f32(static_cast<const float*>(spec.data_ptr()), fp(phase_advance), fpm(out), &v, current_stream(spec)));
+    check(aamd_phase_vocoder_f32(static_cast<const float*>(spec.data_ptr()), ptr<float>(phase_advance), mut<float>(out), &v, current_stream(spec)));
   }
   return out;
 }
@@ -561,7 +570,7 @@ Tensor griffinlim_update(Tensor rebuilt, Tensor tprev, Tensor magnitude, double 
   const torch::stable::accelerator::DeviceGuard guard(rebuilt.get_device_index());
   Tensor next = torch::stable::empty_like(rebuilt);
   if (next.numel())
-    check(aamd_griffinlim_update_f32(fp(rebuilt), fpm(tprev), fp(magnitude), fpm(next), magnitude.numel(), (float)momentum, current_stream(rebuilt)));
+    check(aamd_griffinlim_update_f32(ptr<float>(rebuilt), mut<float>(tprev), ptr<float>(magnitude), mut<float>(next), magnitude.numel(), (float)momentum, current_stream(rebuilt)));
   return next;
 }
 
@@ -572,42 +581,37 @@ Tensor mel_scale(Tensor spec, Tensor band_lo, Tensor band_width, Tensor band_wei
   const torch::stable::accelerator::DeviceGuard guard(spec.get_device_index());
   Tensor out = torch::stable::new_empty(spec, {spec.size(0), spec.size(1), (int64_t)bands.b.n_mels});
   if (out.numel())
-    check(aamd_mel_scale_f32(fp(spec), &bands.b, fpm(out), spec.size(0), (int32_t)spec.size(1), (int32_t)spec.size(2), current_stream(spec)));
+    check(aamd_mel_scale_f32(ptr<float>(spec), &bands.b, mut<float>(out), spec.size(0), (int32_t)spec.size(1), (int32_t)spec.size(2), current_stream(spec)));
   return out;
 }
 
 // ---- aamd::amplitude_to_db / _clamped / db_clamp (functional/functional.py:356-404) -----------------------------------------
 Tensor amplitude_to_db(Tensor x, double multiplier, double amin, double db_multiplier, std::optional<Tensor> group_max, int64_t group_size) {
   want_f32(x, "x");
-  float* gm = nullptr;
-  if (group_max.has_value()) {
-    want_f32(*group_max, "group_max", 1); same_device(x, *group_max);
-    STD_TORCH_CHECK(group_size > 0 && group_max->numel() * group_size >= x.numel(), "audio_amd: group_max too small");
-    gm = fpm(*group_max);
-  }
+  float* gm = group_max_of(x, group_max, group_size, x.numel());
   const torch::stable::accelerator::DeviceGuard guard(x.get_device_index());
   Tensor out = torch::stable::empty_like(x);
   if (out.numel())
-    check(aamd_amplitude_to_db_f32(fp(x), fpm(out), x.numel(), (float)multiplier, (float)amin, (float)db_multiplier, gm,
+    check(aamd_amplitude_to_db_f32(ptr<float>(x), mut<float>(out), x.numel(), (float)multiplier, (float)amin, (float)db_multiplier, gm,
                                    group_size > 0 ? group_size : 1, current_stream(x)));
   return out;
 }
 Tensor amplitude_to_db_clamped(Tensor x, double multiplier, double amin, double db_multiplier, Tensor group_max, int64_t group_size, double top_db) {
-  want_f32(x, "x"); want_f32(group_max, "group_max", 1); same_device(x, group_max);
-  STD_TORCH_CHECK(group_size > 0 && group_max.numel() * group_size >= x.numel(), "audio_amd: group_max too small");
+  want_f32(x, "x");
+  const float* gm = group_max_of(x, group_max, group_size, x.numel());
   const torch::stable::accelerator::DeviceGuard guard(x.get_device_index());
   Tensor out = torch::stable::empty_like(x);
   if (out.numel())
-    check(aamd_amplitude_to_db_clamped_f32(fp(x), fpm(out), x.numel(), (float)multiplier, (float)amin, (float)db_multiplier,
-                                           fp(group_max), group_size, (float)top_db, current_stream(x)));
+    check(aamd_amplitude_to_db_clamped_f32(ptr<float>(x), mut<float>(out), x.numel(), (float)multiplier, (float)amin, (float)db_multiplier,
+                                           gm, group_size, (float)top_db, current_stream(x)));
   return out;
 }
 Tensor db_clamp(Tensor x, Tensor group_max, int64_t group_size, double top_db) {
-  want_f32(x, "x"); want_f32(group_max, "group_max", 1); same_device(x, group_max);
-  STD_TORCH_CHECK(group_size > 0 && group_max.numel() * group_size >= x.numel(), "audio_amd: group_max too small");
+  want_f32(x, "x");
+  const float* gm = group_max_of(x, group_max, group_size, x.numel());
   const torch::stable::accelerator::DeviceGuard guard(x.get_device_index());
   Tensor out = torch::stable::empty_like(x);
-  if (out.numel()) check(aamd_db_clamp_f32(fp(x), fpm(out), x.numel(), fp(group_max), group_size, (float)top_db, current_stream(x)));
+  if (out.numel()) check(aamd_db_clamp_f32(ptr<float>(x), mut<float>(out), x.numel(), gm, group_size, (float)top_db, current_stream(x)));
   return out;
 }
 
@@ -617,7 +621,7 @@ Tensor spectrogram_grad(Tensor spec, Tensor dpower, double power) {
   STD_TORCH_CHECK(spec.numel() == 2 * dpower.numel(), "audio_amd: spec is view_as_real of dpower's shape");
   const torch::stable::accelerator::DeviceGuard guard(spec.get_device_index());
   Tensor out = torch::stable::empty_like(spec);
-  if (out.numel()) check(aamd_spectrogram_grad_f32(fp(spec), fp(dpower), fpm(out), dpower.numel(), (float)power, current_stream(spec)));
+  if (out.numel()) check(aamd_spectrogram_grad_f32(ptr<float>(spec), ptr<float>(dpower), mut<float>(out), dpower.numel(), (float)power, current_stream(spec)));
   return out;
 }
 Tensor mel_spectrogram_grad(Tensor spec, Tensor dmel, Tensor band_lo, Tensor band_width, Tensor band_weights, double power) {
@@ -628,7 +632,7 @@ Tensor mel_spectrogram_grad(Tensor spec, Tensor dmel, Tensor band_lo, Tensor ban
   STD_TORCH_CHECK(spec.size(2) == 2 && dmel.size(0) == spec.size(0) && bt.b.n_mels == spec.size(1), "audio_amd: shapes of spec / dmel / fb^T bands");
   const torch::stable::accelerator::DeviceGuard guard(spec.get_device_index());
   if (spec.numel())
-    check(aamd_melspectrogram_grad_f32(fpm(spec), fp(dmel), &bt.b, spec.size(0), (int32_t)spec.size(1), (int32_t)dmel.size(1),
+    check(aamd_melspectrogram_grad_f32(mut<float>(spec), ptr<float>(dmel), &bt.b, spec.size(0), (int32_t)spec.size(1), (int32_t)dmel.size(1),
                                        (float)power, current_stream(spec)));
   return spec;
 }
@@ -642,7 +646,7 @@ Tensor resample_sparse(Tensor wav, Tensor taps_compact, Tensor tap_lo, int64_t o
   Tensor out = torch::stable::new_empty(wav, {wav.size(0), out_len});
   if (out.numel()) {
     const int64_t length = wav.size(1);
-    check(aamd_resample_sparse_f32(fp(wav), fp(taps_compact), static_cast<const int32_t*>(tap_lo.data_ptr()), fpm(out), wav.size(0),
+    check(aamd_resample_sparse_f32(ptr<float>(wav), ptr<float>(taps_compact), static_cast<const int32_t*>(tap_lo.data_ptr()), mut<float>(out), wav.size(0),
                                    length, length > 0 ? length : 1, (int32_t)orig, (int32_t)new_, (int32_t)width,
                                    (int32_t)taps_compact.size(1), out_len, current_stream(wav)));
   }
@@ -667,7 +671,7 @@ Tensor kaldi_features(Tensor wav, Tensor window, Tensor twiddle, std::optional<T
   if (noise.has_value()) {
     want_f32(*noise, "noise"); same_device(wav, *noise);
     STD_TORCH_CHECK(noise->numel() == k.n_utt * n_frames * k.win, "audio_amd: noise must be (n_utt, n_frames, win)");
-    k.noise = fp(*noise);
+    k.noise = ptr<float>(*noise);
   }
   STD_TORCH_CHECK(k.dither == 0.0f || k.noise != nullptr, "audio_amd: dither needs the caller's Gaussian draws");
   std::optional<Bands> bands;
@@ -678,48 +682,27 @@ Tensor kaldi_features(Tensor wav, Tensor window, Tensor twiddle, std::optional<T
   const torch::stable::accelerator::DeviceGuard guard(wav.get_device_index());
   Tensor out = torch::stable::new_empty(wav, {k.n_utt, n_frames, row});
   if (out.numel())
-    check(aamd_kaldi_features_f32(fp(wav), fp(window), fp(twiddle), fbank ? &bands->b : nullptr, fpm(out), &k, current_stream(wav)));
+    check(aamd_kaldi_features_f32(ptr<float>(wav), ptr<float>(window), ptr<float>(twiddle), fbank ? &bands->b : nullptr, mut<float>(out), &k, current_stream(wav)));
   return out;
 }
 
 // ---- float64 entries: aamd::lfilter_f64 / resample_f64 / fftconvolve_f64 (the precision path, csrc/f64_paths.h) -------------
 Tensor lfilter_f64(Tensor x, Tensor a, Tensor b, int64_t n_stages, int64_t clamp) {
-  want_dev(x, ScalarType::Double, "waveform", 3); want_dev(a, ScalarType::Double, "a_coeffs", 3); want_dev(b, ScalarType::Double, "b_coeffs", 3);
-  same_device(x, a); same_device(x, b);
-  STD_TORCH_CHECK(a.size(0) == n_stages && b.size(0) == n_stages && a.size(1) == b.size(1) && a.size(2) == b.size(2),
-                  "audio_amd: a / b must be (n_stages, rows, n_order)");
-  STD_TORCH_CHECK(a.size(1) == 1 || a.size(1) == x.size(1), "audio_amd: coefficient rows must be 1 or channels");
-  const torch::stable::accelerator::DeviceGuard guard(x.get_device_index());
-  Tensor y = torch::stable::empty_like(x);
-  if (y.numel())
-    check(aamd_lfilter_f64(dp(x), dp(a), dp(b), dpm(y), x.size(0), (int32_t)x.size(1), x.size(2), (int32_t)a.size(2),
-                           (int32_t)a.size(1), (int32_t)n_stages, (int32_t)clamp, current_stream(x)));
-  return y;
+  return lfilter_any<double>(x, a, b, n_stages, clamp);
 }
 Tensor resample_f64(Tensor wav, Tensor kernel, int64_t orig, int64_t new_, int64_t width, int64_t out_len) {
-  want_dev(wav, ScalarType::Double, "waveform", 2); want_dev(kernel, ScalarType::Double, "kernel", 2);
-  same_device(wav, kernel);
-  STD_TORCH_CHECK(kernel.size(0) == new_ && kernel.size(1) == 2 * width + orig, "audio_amd: resample kernel shape does not match (new, 2*width+orig)");
-  const torch::stable::accelerator::DeviceGuard guard(wav.get_device_index());
-  Tensor out = torch::stable::new_empty(wav, {wav.size(0), out_len});
-  if (out.numel()) {
-    const int64_t length = wav.size(1);
-    check(aamd_resample_f64(dp(wav), dp(kernel), dpm(out), wav.size(0), length, length > 0 ? length : 1, (int32_t)orig,
-                            (int32_t)new_, (int32_t)width, out_len, current_stream(wav)));
-  }
-  return out;
+  return resample_unbanded<double>(wav, kernel, orig, new_, width, out_len);
 }
 Tensor fftconvolve_f64(Tensor x, Tensor y, std::optional<Tensor> x_row_of, std::optional<Tensor> y_row_of, int64_t rows,
                        int64_t start, int64_t out_len) {
   want_dev(x, ScalarType::Double, "x", 2); want_dev(y, ScalarType::Double, "y", 2);
   same_device(x, y);
-  const int64_t *xm = nullptr, *ym = nullptr;
-  if (x_row_of.has_value()) { want_dev(*x_row_of, ScalarType::Long, "x_row_of", 1); STD_TORCH_CHECK(x_row_of->numel() == rows); xm = static_cast<const int64_t*>(x_row_of->data_ptr()); }
-  if (y_row_of.has_value()) { want_dev(*y_row_of, ScalarType::Long, "y_row_of", 1); STD_TORCH_CHECK(y_row_of->numel() == rows); ym = static_cast<const int64_t*>(y_row_of->data_ptr()); }
+  const int64_t* xm = row_map(x_row_of, rows, "x_row_of");
+  const int64_t* ym = row_map(y_row_of, rows, "y_row_of");
   const torch::stable::accelerator::DeviceGuard guard(x.get_device_index());
   Tensor out = torch::stable::new_empty(x, {rows, out_len});
   if (out.numel())
-    check(aamd_fftconvolve_f64(dp(x), dp(y), dpm(out), rows, x.size(0), y.size(0), x.size(1), y.size(1), xm, ym, start, out_len,
+    check(aamd_fftconvolve_f64(ptr<double>(x), ptr<double>(y), mut<double>(out), rows, x.size(0), y.size(0), x.size(1), y.size(1), xm, ym, start, out_len,
                                current_stream(x)));
   return out;
 }
@@ -737,11 +720,10 @@ Tensor compute_deltas(Tensor x, int64_t win_length, int64_t pad_mode, bool adjoi
   const torch::stable::accelerator::DeviceGuard guard(x.get_device_index());
   Tensor out = torch::stable::new_empty(x, {x.size(0), x.size(1), x.size(2)});
   if (x.scalar_type() == ScalarType::Double)
-    check(aamd_compute_deltas_f64(x.numel() ? static_cast<const double*>(x.data_ptr()) : nullptr, dpm(out), x.size(0), x.size(1),
-                                  x.size(2), x.stride(0), x.stride(1), x.stride(2), (int32_t)win_length, (int32_t)pad_mode,
-                                  adjoint ? 1 : 0, current_stream(x)));
+    check(aamd_compute_deltas_f64(ptr<double>(x), mut<double>(out), x.size(0), x.size(1), x.size(2), x.stride(0), x.stride(1), x.stride(2),
+                                  (int32_t)win_length, (int32_t)pad_mode, adjoint ? 1 : 0, current_stream(x)));
   else
-    check(aamd_compute_deltas_f32(fp(x), fpm(out), x.size(0), x.size(1), x.size(2), x.stride(0), x.stride(1), x.stride(2),
+    check(aamd_compute_deltas_f32(ptr<float>(x), mut<float>(out), x.size(0), x.size(1), x.size(2), x.stride(0), x.stride(1), x.stride(2),
                                   (int32_t)win_length, (int32_t)pad_mode, adjoint ? 1 : 0, current_stream(x)));
   return out;
 }
@@ -752,11 +734,11 @@ Tensor sliding_window_cmn(Tensor x, int64_t cmn_window, int64_t min_cmn_window, 
   const int64_t ws_bytes = aamd_sliding_window_cmn_workspace(x.size(0), x.size(1), x.size(2), norm_vars ? 1 : 0);
   Tensor ws = torch::stable::new_empty(x, {ws_bytes / 8 > 0 ? ws_bytes / 8 : 1}, ScalarType::Double);
   if (x.scalar_type() == ScalarType::Double)
-    check(aamd_sliding_window_cmn_f64(x.numel() ? static_cast<const double*>(x.data_ptr()) : nullptr, dpm(out), ws.data_ptr(),
-                                      x.size(0), x.size(1), x.size(2), x.stride(0), x.stride(2), x.stride(1), cmn_window,
-                                      min_cmn_window, center ? 1 : 0, norm_vars ? 1 : 0, adjoint ? 1 : 0, current_stream(x)));
+    check(aamd_sliding_window_cmn_f64(ptr<double>(x), mut<double>(out), ws.data_ptr(), x.size(0), x.size(1), x.size(2), x.stride(0), x.stride(2),
+                                      x.stride(1), cmn_window, min_cmn_window, center ? 1 : 0, norm_vars ? 1 : 0,
+                                      adjoint ? 1 : 0, current_stream(x)));
   else
-    check(aamd_sliding_window_cmn_f32(fp(x), fpm(out), ws.data_ptr(), x.size(0), x.size(1), x.size(2), x.stride(0), x.stride(2),
+    check(aamd_sliding_window_cmn_f32(ptr<float>(x), mut<float>(out), ws.data_ptr(), x.size(0), x.size(1), x.size(2), x.stride(0), x.stride(2),
                                       x.stride(1), cmn_window, min_cmn_window, center ? 1 : 0, norm_vars ? 1 : 0,
                                       adjoint ? 1 : 0, current_stream(x)));
   return out;
@@ -799,17 +781,8 @@ Tensor detect_pitch(Tensor x, int64_t sample_rate, int64_t frame_size, int64_t l
 Tensor spec_augment(Tensor x, std::optional<Tensor> draws, std::vector<int64_t> axes, std::vector<int64_t> params,
                     std::vector<int64_t> starts, std::vector<int64_t> ends, bool time_inner, int64_t value_bits,
                     std::optional<Tensor> value) {
-  STD_TORCH_CHECK(x.is_cuda(), "audio_amd: specgram must be on an MI355X (ROCm) device; there is no CPU kernel");
+  const int32_t dtype = wave_dtype(x, "specgram");
   STD_TORCH_CHECK(x.dim() == 3, "audio_amd: specgram must have 3 dimensions");
-  int32_t dtype = -1;
-  switch (x.scalar_type()) {
-    case ScalarType::Float: dtype = AAMD_SA_F32; break;
-    case ScalarType::Double: dtype = AAMD_SA_F64; break;
-    case ScalarType::Half: dtype = AAMD_SA_F16; break;
-    case ScalarType::BFloat16: dtype = AAMD_SA_BF16; break;
-    default: break;
-  }
-  STD_TORCH_CHECK(dtype >= 0, "audio_amd: specgram must be float16, bfloat16, float32 or float64");
   const int64_t n = (int64_t)axes.size();
   const void* vp = nullptr;
   if (value.has_value()) {
@@ -843,18 +816,6 @@ Tensor spec_augment(Tensor x, std::optional<Tensor> draws, std::vector<int64_t> 
 // ---- aamd::add_noise / add_noise_grad / preemphasis (F.add_noise, F.preemphasis; csrc/wave_augment.h) ---------------------
 // Operands are (rows, L) with unit stride along time and any row stride (0: one row for every output row); snr is float64
 // (rows) and lengths int64 (rows), any stride, both read on the device.  workspace: float64, aamd_add_noise_workspace() bytes.
-int32_t wave_dtype(const Tensor& x, const char* what) {
-  STD_TORCH_CHECK(x.is_cuda(), "audio_amd: ", what, " must be on an MI355X (ROCm) device; there is no CPU kernel");
-  switch (x.scalar_type()) {
-    case ScalarType::Float: return AAMD_SA_F32;
-    case ScalarType::Double: return AAMD_SA_F64;
-    case ScalarType::Half: return AAMD_SA_F16;
-    case ScalarType::BFloat16: return AAMD_SA_BF16;
-    default: break;
-  }
-  STD_TORCH_CHECK(false, "audio_amd: ", what, " must be float16, bfloat16, float32 or float64");
-  return -1;
-}
 void want_rows(const Tensor& t, const char* what, const Tensor& ref) {
   STD_TORCH_CHECK(t.is_cuda() && t.dim() == 2 && t.scalar_type() == ref.scalar_type() && t.size(0) == ref.size(0) &&
                   t.size(1) == ref.size(1), "audio_amd: ", what, " must be a (rows, time) device tensor of the waveform's shape and dtype");
@@ -927,9 +888,9 @@ Tensor preemphasis(Tensor x, double coeff, bool transposed) {
   Tensor out = torch::stable::new_empty(x, {x.size(0), x.size(1)});
   if (x.numel() == 0) return out;
   if (dtype == AAMD_SA_F32)
-    check(aamd_preemphasis_f32(fp(x), fpm(out), x.size(0), x.size(1), row_stride(x), coeff, transposed ? 1 : 0, current_stream(x)));
+    check(aamd_preemphasis_f32(ptr<float>(x), mut<float>(out), x.size(0), x.size(1), row_stride(x), coeff, transposed ? 1 : 0, current_stream(x)));
   else if (dtype == AAMD_SA_F64)
-    check(aamd_preemphasis_f64(static_cast<const double*>(x.data_ptr()), dpm(out), x.size(0), x.size(1), row_stride(x), coeff,
+    check(aamd_preemphasis_f64(ptr<double>(x), mut<double>(out), x.size(0), x.size(1), row_stride(x), coeff,
                                transposed ? 1 : 0, current_stream(x)));
   else
     check(aamd_preemphasis_lp(x.data_ptr(), out.data_ptr(), x.size(0), x.size(1), row_stride(x), coeff, dtype, transposed ? 1 : 0,
@@ -1057,8 +1018,6 @@ RnntShape rnnt_check(const Tensor& logits, const Tensor& targets, const Tensor& 
   same_device(logits, workspace);
   return s;
 }
-const int32_t* ip(const Tensor& t) { return t.numel() ? static_cast<const int32_t*>(t.data_ptr()) : nullptr; }
-
 // costs (batch,) float64
 Tensor rnnt_loss_forward(Tensor logits, Tensor targets, Tensor logit_lengths, Tensor target_lengths, int64_t blank, bool fused,
                          Tensor workspace) {
@@ -1066,8 +1025,8 @@ Tensor rnnt_loss_forward(Tensor logits, Tensor targets, Tensor logit_lengths, Te
   const torch::stable::accelerator::DeviceGuard guard(logits.get_device_index());
   Tensor costs = torch::stable::new_empty(logits, {s.B}, ScalarType::Double);
   if (s.B == 0) return costs;
-  check(aamd_rnnt_loss_forward(s.dtype, logits.data_ptr(), ip(targets), ip(logit_lengths), ip(target_lengths), s.B, s.T, s.U1, s.V,
-                               (int32_t)blank, fused ? 1 : 0, workspace.data_ptr(), dpm(costs), current_stream(logits)));
+  check(aamd_rnnt_loss_forward(s.dtype, logits.data_ptr(), ptr<int32_t>(targets), ptr<int32_t>(logit_lengths), ptr<int32_t>(target_lengths), s.B, s.T, s.U1, s.V,
+                               (int32_t)blank, fused ? 1 : 0, workspace.data_ptr(), mut<double>(costs), current_stream(logits)));
   return costs;
 }
 Tensor rnnt_loss_backward(Tensor logits, Tensor targets, Tensor logit_lengths, Tensor target_lengths, int64_t blank, bool fused,
@@ -1079,8 +1038,8 @@ Tensor rnnt_loss_backward(Tensor logits, Tensor targets, Tensor logit_lengths, T
   const torch::stable::accelerator::DeviceGuard guard(logits.get_device_index());
   Tensor grad = torch::stable::empty_like(logits);
   if (s.B == 0) return grad;
-  check(aamd_rnnt_loss_backward(s.dtype, logits.data_ptr(), ip(targets), ip(logit_lengths), ip(target_lengths), s.B, s.T, s.U1, s.V,
-                                (int32_t)blank, fused ? 1 : 0, clamp, workspace.data_ptr(), dp(grad_costs), grad.data_ptr(),
+  check(aamd_rnnt_loss_backward(s.dtype, logits.data_ptr(), ptr<int32_t>(targets), ptr<int32_t>(logit_lengths), ptr<int32_t>(target_lengths), s.B, s.T, s.U1, s.V,
+                                (int32_t)blank, fused ? 1 : 0, clamp, workspace.data_ptr(), ptr<double>(grad_costs), grad.data_ptr(),
                                 current_stream(logits)));
   return grad;
 }
@@ -1124,7 +1083,7 @@ Tensor cuda_lfilter_core_loop(Tensor in, Tensor a_flipped, Tensor padded_out) {
     torch::stable::fill_(b0, 1.0);
   }
   Tensor y = torch::stable::empty_like(in);
-  check(aamd_lfilter_f32(fp(in), fp(a), fp(b), fpm(y), N, (int32_t)C, L, (int32_t)n_order, (int32_t)C, 1, 0,
+  check(aamd_lfilter_f32(ptr<float>(in), ptr<float>(a), ptr<float>(b), mut<float>(y), N, (int32_t)C, L, (int32_t)n_order, (int32_t)C, 1, 0,
                          current_stream(in)));
   Tensor dst = torch::stable::narrow(padded_out, 2, n_order - 1, L);
   torch::stable::copy_(dst, y);
@@ -1133,114 +1092,77 @@ Tensor cuda_lfilter_core_loop(Tensor in, Tensor a_flipped, Tensor padded_out) {
 
 }  // namespace
 
-STABLE_TORCH_LIBRARY(aamd, m) {
-  m.def("spectrogram(Tensor wav, Tensor window, Tensor twiddle, int n_fft, int hop, int pad, bool center, int pad_mode, "
-        "bool onesided, int n_frames, float scale, float power) -> Tensor");
-  m.def("mel_spectrogram(Tensor wav, Tensor window, Tensor twiddle, Tensor band_lo, Tensor band_width, "
-        "Tensor band_weights, Tensor? lane_order, Tensor? table400, int n_fft, int hop, int pad, bool center, int pad_mode, int n_frames, "
-        "float scale, float power, int table_sig) -> Tensor");
-  m.def("mel_spectrogram_db(Tensor wav, Tensor window, Tensor twiddle, Tensor band_lo, Tensor band_width, "
-        "Tensor band_weights, Tensor? lane_order, Tensor? table400, int n_fft, int hop, int pad, bool center, int pad_mode, int n_frames, "
-        "float scale, float power, float multiplier, float amin, float db_multiplier, Tensor(a!)? group_max, "
-        "int rows_per_group, int table_sig) -> Tensor");
-  m.def("mfcc_dct(Tensor mel, Tensor dct_mat, int log_mode, Tensor? group_max, int vec_per_group, float top_db) -> Tensor");
-  m.def("resample(Tensor wav, Tensor kernel, int orig, int new, int width, int out_len, int[]? band_tap_lo, "
-        "int tap_span, Tensor? frag) -> Tensor");
-  m.def("resample_frag_build(Tensor kernel, int orig, int new, int width, int[] band_tap_lo, int tap_span) -> Tensor");
-  m.def("lfilter(Tensor waveform, Tensor a_coeffs, Tensor b_coeffs, int n_stages, int clamp) -> Tensor");
-  m.def("fftconvolve(Tensor x, Tensor y, Tensor? x_row_of, Tensor? y_row_of, int rows, int start, int out_len) -> Tensor");
-  m.def("fftconvolve_staged(Tensor x, Tensor y, Tensor? x_row_of, Tensor? y_row_of, int rows, int start, int out_len, "
-        "Tensor(a!) workspace, int stages) -> Tensor");
-  // round 4: the rest of include/audio_amd.h
-  m.def("mel_spectrogram_lognorm(Tensor wav, Tensor window, Tensor twiddle, Tensor band_lo, Tensor band_width, "
-        "Tensor band_weights, Tensor? lane_order, Tensor? table400, int n_fft, int hop, int n_frames, float scale, float gain, "
-        "Tensor? mean, Tensor? invstddev, int out_frames, int table_sig) -> Tensor");
-  m.def("mfcc_frag_build(Tensor dct_mat, int n_mels, int n_mfcc) -> Tensor");
-  m.def("mfcc_fused(Tensor wav, Tensor window, Tensor twiddle, Tensor band_lo, Tensor band_width, Tensor band_weights, "
-        "Tensor? lane_order, Tensor? table400, Tensor dct_frag, Tensor(a!) group_max, int n_fft, int hop, int pad, bool center, "
-        "int pad_mode, int n_frames, float scale, int n_mfcc, float multiplier, float amin, float db_multiplier, float top_db, "
-        "int rows_per_group, int table_sig) -> Tensor");
-  m.def("istft(Tensor spec, Tensor window, Tensor twiddle, Tensor? inv_envelope, int n_fft, int hop, int pad, bool center, "
-        "int pad_mode, int length, float scale, bool adjoint) -> Tensor");
-  m.def("istft_f64(Tensor spec, Tensor window, Tensor twiddle, Tensor? inv_envelope, int n_fft, int hop, int pad, bool center, "
-        "int pad_mode, int length, float scale, bool adjoint) -> Tensor");
-  m.def("spectrogram_f64(Tensor wav, Tensor window, Tensor twiddle, int n_fft, int hop, int pad, bool center, int pad_mode, "
-        "int n_frames) -> Tensor");
-  m.def("phase_vocoder(Tensor spec, Tensor phase_advance, float rate, bool frame_major_out) -> Tensor");
-  m.def("griffinlim_update(Tensor rebuilt, Tensor(a!) tprev, Tensor magnitude, float momentum) -> Tensor");
-  m.def("mel_scale(Tensor spec, Tensor band_lo, Tensor band_width, Tensor band_weights) -> Tensor");
-  m.def("amplitude_to_db(Tensor x, float multiplier, float amin, float db_multiplier, Tensor(a!)? group_max, int group_size) -> Tensor");
-  m.def("amplitude_to_db_clamped(Tensor x, float multiplier, float amin, float db_multiplier, Tensor group_max, int group_size, "
-        "float top_db) -> Tensor");
-  m.def("db_clamp(Tensor x, Tensor group_max, int group_size, float top_db) -> Tensor");
-  m.def("spectrogram_grad(Tensor spec, Tensor dpower, float power) -> Tensor");
-  m.def("mel_spectrogram_grad(Tensor(a!) spec, Tensor dmel, Tensor band_lo, Tensor band_width, Tensor band_weights, float power) -> Tensor(a!)");
-  m.def("resample_sparse(Tensor wav, Tensor taps_compact, Tensor tap_lo, int orig, int new, int width, int out_len) -> Tensor");
-  m.def("kaldi_features(Tensor wav, Tensor window, Tensor twiddle, Tensor? band_lo, Tensor? band_width, Tensor? band_weights, "
-        "Tensor? noise, int n_frames, int[] opts, float[] fopts) -> Tensor");
-  m.def("lfilter_f64(Tensor waveform, Tensor a_coeffs, Tensor b_coeffs, int n_stages, int clamp) -> Tensor");
-  m.def("resample_f64(Tensor wav, Tensor kernel, int orig, int new, int width, int out_len) -> Tensor");
-  m.def("fftconvolve_f64(Tensor x, Tensor y, Tensor? x_row_of, Tensor? y_row_of, int rows, int start, int out_len) -> Tensor");
-  m.def("compute_deltas(Tensor specgram, int win_length, int pad_mode, bool adjoint) -> Tensor");
-  m.def("sliding_window_cmn(Tensor specgram, int cmn_window, int min_cmn_window, bool center, bool norm_vars, bool adjoint) -> Tensor");
-  m.def("detect_pitch(Tensor x, int sample_rate, int frame_size, int lags, int lag_min, int win_length, int mode) -> Tensor");
-  m.def("spec_augment(Tensor x, Tensor? draws, int[] axes, int[] params, int[] starts, int[] ends, bool time_inner, "
-        "int value_bits, Tensor? value) -> Tensor");
-  m.def("add_noise(Tensor waveform, Tensor noise, Tensor snr, Tensor? lengths, Tensor workspace) -> Tensor");
-  m.def("add_noise_grad(Tensor cotangent, Tensor waveform, Tensor noise, Tensor snr, Tensor? lengths, Tensor workspace) -> Tensor");
-  m.def("preemphasis(Tensor waveform, float coeff, bool transposed) -> Tensor");
-  m.def("beamform_psd(Tensor specgram, Tensor? mask1, Tensor? mask2, bool normalize, float eps) -> Tensor");
-  m.def("beamform_weights(int mode, Tensor a, Tensor b, Tensor? reference_vector, int batch, int freq, int reference, "
-        "bool loading, float diag_eps, float eps, int n_iter, bool adjoint) -> Tensor");
-  m.def("beamform_apply(Tensor weights, Tensor specgram, bool frame_major) -> Tensor");
-  m.def("rnnt_loss_forward(Tensor logits, Tensor targets, Tensor logit_lengths, Tensor target_lengths, int blank, bool fused, "
-        "Tensor(a!) workspace) -> Tensor");
-  m.def("rnnt_loss_backward(Tensor logits, Tensor targets, Tensor logit_lengths, Tensor target_lengths, int blank, bool fused, "
-        "float clamp, Tensor workspace, Tensor grad_costs) -> Tensor");
-}
+// Every op of namespace aamd, once: X(the kernel above = the op's name, the rest of its schema).  Both registration blocks
+// below are produced from this list, so a new op is its function plus one entry here (and its fake in audio_amd/_shim.py).
+#define AAMD_OPS(X)                                                                                                            \
+  X(spectrogram, "(Tensor wav, Tensor window, Tensor twiddle, int n_fft, int hop, int pad, bool center, int pad_mode, "        \
+    "bool onesided, int n_frames, float scale, float power) -> Tensor")                                                        \
+  X(mel_spectrogram, "(Tensor wav, Tensor window, Tensor twiddle, Tensor band_lo, Tensor band_width, "                         \
+    "Tensor band_weights, Tensor? lane_order, Tensor? table400, int n_fft, int hop, int pad, bool center, int pad_mode, int n_frames, " \
+    "float scale, float power, int table_sig) -> Tensor")                                                                      \
+  X(mel_spectrogram_db, "(Tensor wav, Tensor window, Tensor twiddle, Tensor band_lo, Tensor band_width, "                      \
+    "Tensor band_weights, Tensor? lane_order, Tensor? table400, int n_fft, int hop, int pad, bool center, int pad_mode, int n_frames, " \
+    "float scale, float power, float multiplier, float amin, float db_multiplier, Tensor(a!)? group_max, "                     \
+    "int rows_per_group, int table_sig) -> Tensor")                                                                            \
+  X(mfcc_dct, "(Tensor mel, Tensor dct_mat, int log_mode, Tensor? group_max, int vec_per_group, float top_db) -> Tensor")      \
+  X(resample, "(Tensor wav, Tensor kernel, int orig, int new, int width, int out_len, int[]? band_tap_lo, "                    \
+    "int tap_span, Tensor? frag) -> Tensor")                                                                                   \
+  X(resample_frag_build, "(Tensor kernel, int orig, int new, int width, int[] band_tap_lo, int tap_span) -> Tensor")           \
+  X(lfilter, "(Tensor waveform, Tensor a_coeffs, Tensor b_coeffs, int n_stages, int clamp) -> Tensor")                         \
+  X(fftconvolve, "(Tensor x, Tensor y, Tensor? x_row_of, Tensor? y_row_of, int rows, int start, int out_len) -> Tensor")       \
+  X(fftconvolve_staged, "(Tensor x, Tensor y, Tensor? x_row_of, Tensor? y_row_of, int rows, int start, int out_len, "          \
+    "Tensor(a!) workspace, int stages) -> Tensor")                                                                             \
+  /* round 4: the rest of include/audio_amd.h */                                                                               \
+  X(mel_spectrogram_lognorm, "(Tensor wav, Tensor window, Tensor twiddle, Tensor band_lo, Tensor band_width, "                 \
+    "Tensor band_weights, Tensor? lane_order, Tensor? table400, int n_fft, int hop, int n_frames, float scale, float gain, "   \
+    "Tensor? mean, Tensor? invstddev, int out_frames, int table_sig) -> Tensor")                                               \
+  X(mfcc_frag_build, "(Tensor dct_mat, int n_mels, int n_mfcc) -> Tensor")                                                     \
+  X(mfcc_fused, "(Tensor wav, Tensor window, Tensor twiddle, Tensor band_lo, Tensor band_width, Tensor band_weights, "         \
+    "Tensor? lane_order, Tensor? table400, Tensor dct_frag, Tensor(a!) group_max, int n_fft, int hop, int pad, bool center, "  \
+    "int pad_mode, int n_frames, float scale, int n_mfcc, float multiplier, float amin, float db_multiplier, float top_db, "   \
+    "int rows_per_group, int table_sig) -> Tensor")                                                                            \
+  X(istft, "(Tensor spec, Tensor window, Tensor twiddle, Tensor? inv_envelope, int n_fft, int hop, int pad, bool center, "     \
+    "int pad_mode, int length, float scale, bool adjoint) -> Tensor")                                                          \
+  X(istft_f64, "(Tensor spec, Tensor window, Tensor twiddle, Tensor? inv_envelope, int n_fft, int hop, int pad, bool center, " \
+    "int pad_mode, int length, float scale, bool adjoint) -> Tensor")                                                          \
+  X(spectrogram_f64, "(Tensor wav, Tensor window, Tensor twiddle, int n_fft, int hop, int pad, bool center, int pad_mode, "    \
+    "int n_frames) -> Tensor")                                                                                                 \
+  X(phase_vocoder, "(Tensor spec, Tensor phase_advance, float rate, bool frame_major_out) -> Tensor")                          \
+  X(griffinlim_update, "(Tensor rebuilt, Tensor(a!) tprev, Tensor magnitude, float momentum) -> Tensor")                       \
+  X(mel_scale, "(Tensor spec, Tensor band_lo, Tensor band_width, Tensor band_weights) -> Tensor")                              \
+  X(amplitude_to_db, "(Tensor x, float multiplier, float amin, float db_multiplier, Tensor(a!)? group_max, int group_size) -> Tensor") \
+  X(amplitude_to_db_clamped, "(Tensor x, float multiplier, float amin, float db_multiplier, Tensor group_max, int group_size, " \
+    "float top_db) -> Tensor")                                                                                                 \
+  X(db_clamp, "(Tensor x, Tensor group_max, int group_size, float top_db) -> Tensor")                                          \
+  X(spectrogram_grad, "(Tensor spec, Tensor dpower, float power) -> Tensor")                                                   \
+  X(mel_spectrogram_grad, "(Tensor(a!) spec, Tensor dmel, Tensor band_lo, Tensor band_width, Tensor band_weights, float power) -> Tensor(a!)") \
+  X(resample_sparse, "(Tensor wav, Tensor taps_compact, Tensor tap_lo, int orig, int new, int width, int out_len) -> Tensor")  \
+  X(kaldi_features, "(Tensor wav, Tensor window, Tensor twiddle, Tensor? band_lo, Tensor? band_width, Tensor? band_weights, "  \
+    "Tensor? noise, int n_frames, int[] opts, float[] fopts) -> Tensor")                                                       \
+  X(lfilter_f64, "(Tensor waveform, Tensor a_coeffs, Tensor b_coeffs, int n_stages, int clamp) -> Tensor")                     \
+  X(resample_f64, "(Tensor wav, Tensor kernel, int orig, int new, int width, int out_len) -> Tensor")                          \
+  X(fftconvolve_f64, "(Tensor x, Tensor y, Tensor? x_row_of, Tensor? y_row_of, int rows, int start, int out_len) -> Tensor")   \
+  X(compute_deltas, "(Tensor specgram, int win_length, int pad_mode, bool adjoint) -> Tensor")                                 \
+  X(sliding_window_cmn, "(Tensor specgram, int cmn_window, int min_cmn_window, bool center, bool norm_vars, bool adjoint) -> Tensor") \
+  X(detect_pitch, "(Tensor x, int sample_rate, int frame_size, int lags, int lag_min, int win_length, int mode) -> Tensor")    \
+  X(spec_augment, "(Tensor x, Tensor? draws, int[] axes, int[] params, int[] starts, int[] ends, bool time_inner, "            \
+    "int value_bits, Tensor? value) -> Tensor")                                                                                \
+  X(add_noise, "(Tensor waveform, Tensor noise, Tensor snr, Tensor? lengths, Tensor workspace) -> Tensor")                     \
+  X(add_noise_grad, "(Tensor cotangent, Tensor waveform, Tensor noise, Tensor snr, Tensor? lengths, Tensor workspace) -> Tensor") \
+  X(preemphasis, "(Tensor waveform, float coeff, bool transposed) -> Tensor")                                                  \
+  X(beamform_psd, "(Tensor specgram, Tensor? mask1, Tensor? mask2, bool normalize, float eps) -> Tensor")                      \
+  X(beamform_weights, "(int mode, Tensor a, Tensor b, Tensor? reference_vector, int batch, int freq, int reference, "          \
+    "bool loading, float diag_eps, float eps, int n_iter, bool adjoint) -> Tensor")                                            \
+  X(beamform_apply, "(Tensor weights, Tensor specgram, bool frame_major) -> Tensor")                                           \
+  X(rnnt_loss_forward, "(Tensor logits, Tensor targets, Tensor logit_lengths, Tensor target_lengths, int blank, bool fused, "  \
+    "Tensor(a!) workspace) -> Tensor")                                                                                         \
+  X(rnnt_loss_backward, "(Tensor logits, Tensor targets, Tensor logit_lengths, Tensor target_lengths, int blank, bool fused, " \
+    "float clamp, Tensor workspace, Tensor grad_costs) -> Tensor")
 
-STABLE_TORCH_LIBRARY_IMPL(aamd, CUDA, m) {
-  m.impl("spectrogram", TORCH_BOX(&spectrogram));
-  m.impl("mel_spectrogram", TORCH_BOX(&mel_spectrogram));
-  m.impl("mel_spectrogram_db", TORCH_BOX(&mel_spectrogram_db));
-  m.impl("mfcc_dct", TORCH_BOX(&mfcc_dct));
-  m.impl("resample", TORCH_BOX(&resample));
-  m.impl("resample_frag_build", TORCH_BOX(&resample_frag_build));
-  m.impl("lfilter", TORCH_BOX(&lfilter));
-  m.impl("fftconvolve", TORCH_BOX(&fftconvolve));
-  m.impl("fftconvolve_staged", TORCH_BOX(&fftconvolve_staged));
-  m.impl("mel_spectrogram_lognorm", TORCH_BOX(&mel_spectrogram_lognorm));
-  m.impl("mfcc_frag_build", TORCH_BOX(&mfcc_frag_build));
-  m.impl("mfcc_fused", TORCH_BOX(&mfcc_fused));
-  m.impl("istft", TORCH_BOX(&istft));
-  m.impl("istft_f64", TORCH_BOX(&istft_f64));
-  m.impl("spectrogram_f64", TORCH_BOX(&spectrogram_f64));
-  m.impl("phase_vocoder", TORCH_BOX(&phase_vocoder));
-  m.impl("griffinlim_update", TORCH_BOX(&griffinlim_update));
-  m.impl("mel_scale", TORCH_BOX(&mel_scale));
-  m.impl("amplitude_to_db", TORCH_BOX(&amplitude_to_db));
-  m.impl("amplitude_to_db_clamped", TORCH_BOX(&amplitude_to_db_clamped));
-  m.impl("db_clamp", TORCH_BOX(&db_clamp));
-  m.impl("spectrogram_grad", TORCH_BOX(&spectrogram_grad));
-  m.impl("mel_spectrogram_grad", TORCH_BOX(&mel_spectrogram_grad));
-  m.impl("resample_sparse", TORCH_BOX(&resample_sparse));
-  m.impl("kaldi_features", TORCH_BOX(&kaldi_features));
-  m.impl("lfilter_f64", TORCH_BOX(&lfilter_f64));
-  m.impl("resample_f64", TORCH_BOX(&resample_f64));
-  m.impl("fftconvolve_f64", TORCH_BOX(&fftconvolve_f64));
-  m.impl("compute_deltas", TORCH_BOX(&compute_deltas));
-  m.impl("sliding_window_cmn", TORCH_BOX(&sliding_window_cmn));
-  m.impl("detect_pitch", TORCH_BOX(&detect_pitch));
-  m.impl("spec_augment", TORCH_BOX(&spec_augment));
-  m.impl("add_noise", TORCH_BOX(&add_noise));
-  m.impl("add_noise_grad", TORCH_BOX(&add_noise_grad));
-  m.impl("preemphasis", TORCH_BOX(&preemphasis));
-  m.impl("beamform_psd", TORCH_BOX(&beamform_psd));
-  m.impl("beamform_weights", TORCH_BOX(&beamform_weights));
-  m.impl("beamform_apply", TORCH_BOX(&beamform_apply));
-  m.impl("rnnt_loss_forward", TORCH_BOX(&rnnt_loss_forward));
-  m.impl("rnnt_loss_backward", TORCH_BOX(&rnnt_loss_backward));
-}
+#define AAMD_DEF(name, schema) m.def(#name schema);
+#define AAMD_IMPL(name, schema) m.impl(#name, TORCH_BOX(&name));
+STABLE_TORCH_LIBRARY(aamd, m) { AAMD_OPS(AAMD_DEF) }
+STABLE_TORCH_LIBRARY_IMPL(aamd, CUDA, m) { AAMD_OPS(AAMD_IMPL) }
 
 // The reference's op.  libtorchaudio (when present) has already run
 //   STABLE_TORCH_LIBRARY_FRAGMENT(torchaudio, m) { m.def("_lfilter_core_loop(...)"); }

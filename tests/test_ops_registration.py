@@ -15,6 +15,29 @@ def test_ops_are_registered():
         assert "Tensor" in str(getattr(torch.ops.audio_amd, name).default._schema)
 
 
+def _registered(namespace):
+    return {n.split("::", 1)[1] for n in torch._C._dispatch_get_all_op_names() if n.startswith(namespace + "::")}
+
+
+def test_every_op_is_declared_once_and_its_three_parts_agree():
+    """audio_amd/_ops.py declares an op by ONE `_register(schema, kernel, meta)` call; `_ops.OPS` records the triple.  The dispatcher
+    holds exactly those ops with exactly those schemas, the kernel and the Meta function take the schema's number of arguments,
+    and every op has the CUDA, Meta and AutogradCUDA kernels and no CPU kernel."""
+    import inspect
+    from audio_amd import _ops
+    assert _registered("audio_amd") == set(_ops.OPS)
+    assert len(_ops.OPS) == 36
+    for name, (schema, kernel, meta) in _ops.OPS.items():
+        registered = torch._C._get_schema(f"audio_amd::{name}", "")
+        assert str(registered) == "audio_amd::" + schema, name
+        n = len(registered.arguments)
+        for fn in (kernel, meta):
+            inspect.signature(fn).bind(*range(n))              # raises TypeError when the arity disagrees
+        keys = [k for k in ("CUDA", "Meta", "AutogradCUDA", "CPU")
+                if torch._C._dispatch_has_kernel_for_dispatch_key(f"audio_amd::{name}", k)]
+        assert keys == ["CUDA", "Meta", "AutogradCUDA"], (name, keys)
+
+
 def test_meta_shapes_and_strides_match_reference_layout():
     x = torch.empty(3, 2, 16000, device="meta")
     w = torch.empty(400, device="meta")

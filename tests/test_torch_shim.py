@@ -41,6 +41,21 @@ def test_shim_loads_and_registers_documented_schemas():
     assert "Tensor(a!)? group_max" in s          # the running group maximum is declared as mutated
 
 
+def test_compiled_ops_fakes_and_op_list_name_the_same_ops_with_the_same_arity():
+    """csrc/torch_shim.cpp registers the ops from one list; audio_amd/_shim.py records one fake per op and derives `OPS` from
+    that record.  The three agree by name, and each fake takes exactly the arguments of the compiled schema."""
+    import inspect
+    from audio_amd import _shim
+    _shim.load()
+    compiled = {n.split("::", 1)[1] for n in torch._C._dispatch_get_all_op_names() if n.startswith("aamd::")}
+    assert compiled == set(_shim.OPS) == set(_shim.FAKES)
+    assert len(_shim.OPS) == len(compiled) == 40
+    for name, fake in _shim.FAKES.items():
+        n = len(torch._C._get_schema(f"aamd::{name}", "").arguments)
+        inspect.signature(fake).bind(*range(n))                # raises TypeError when the arity disagrees
+        assert len(inspect.signature(fake).parameters) == n, name
+
+
 def test_reference_op_gets_reference_schema_and_cuda_kernel():
     from audio_amd import _shim
     _shim.ensure_torchaudio_op()
@@ -290,6 +305,35 @@ def test_round4_ops_reach_every_remaining_entry_point():
         G = ops.spectrogram_grad(Xc, dP, 2.0)
         want = 2.0 * dP.unsqueeze(-1) * Xc
         assert float((G - want).abs().max()) <= 1e-5 * float(want.abs().max())
+
+
+@pytest.mark.gpu
+def test_mel_spectrogram_db_checks_the_window_size_like_the_other_stft_ops():
+    """The input has zero rows: the output is empty and no kernel is launched whether or not the check is there."""
+    from audio_amd import _shim
+    _shim.load()
+    ops, dev = torch.ops.aamd, torch.device("cuda")
+    i32 = dict(dtype=torch.int32, device=dev)
+    bands = (torch.zeros(80, **i32), torch.ones(80, **i32), torch.zeros(80, 30, device=dev))
+    wav, twiddle = torch.zeros(0, 1600, device=dev), torch.zeros(400, 2, device=dev)
+    with pytest.raises(RuntimeError, match="window"):
+        ops.mel_spectrogram_db(wav, torch.ones(399, device=dev), twiddle, *bands, None, None, 400, 160, 0, True, 0, 11, 1.0, 2.0,
+                               10.0, 1e-10, 0.0, None, 1, 0)
+    assert ops.mel_spectrogram_db(wav, torch.ones(400, device=dev), twiddle, *bands, None, None, 400, 160, 0, True, 0, 11, 1.0,
+                                  2.0, 10.0, 1e-10, 0.0, None, 1, 0).shape == (0, 11, 80)
+
+
+@pytest.mark.gpu
+def test_lfilter_f64_checks_the_clamp_range_like_lfilter():
+    """The input has zero rows: the output is empty and no kernel is launched whether or not the check is there."""
+    from audio_amd import _shim
+    _shim.load()
+    ops, dev = torch.ops.aamd, torch.device("cuda")
+    x64 = torch.zeros(0, 1, 8, dtype=torch.float64, device=dev)
+    coeffs = torch.ones(1, 1, 3, dtype=torch.float64, device=dev)
+    with pytest.raises(RuntimeError, match="clamp"):
+        ops.lfilter_f64(x64, coeffs, coeffs, 1, 3)
+    assert ops.lfilter_f64(x64, coeffs, coeffs, 1, 2).shape == (0, 1, 8)
 
 
 # ------------------------------------------------------------------ round 5: prepared tap spectra (aamd_fftconvolve_staged_f32)
