@@ -27,7 +27,8 @@ CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "lib", "libaudio_amd.so")
 LAB_OUT = os.path.join(HERE, "lib", "libaudio_amd_lab.so")
 SOURCES = ["api_common.hip", "api_stft.hip", "api_mel400_lowp.hip", "api_istft.hip", "api_kaldi.hip", "api_f64.hip",
-           "api_specdomain.hip", "api_resample.hip", "api_lfilter.hip", "api_fftconv.hip", "api_post.hip", "api_rnnt.hip"]
+           "api_specdomain.hip", "api_resample.hip", "api_lfilter.hip", "api_fftconv.hip", "api_post.hip", "api_rnnt.hip",
+           "api_align.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=fast",
          # packed fp32 VALU ops run at half rate on gfx950 (no gain) and cost v_mov shuffles
          "-fno-slp-vectorize"]

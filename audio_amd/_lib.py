@@ -169,6 +169,14 @@ _SIGS = {
     "aamd_rnnt_loss_forward": (C.c_int, [C.c_int32, _P, _P, _P, _P] + [C.c_int64] * 4 + [C.c_int32, C.c_int32, _P, _P, _P]),
     "aamd_rnnt_loss_backward": (C.c_int, [C.c_int32, _P, _P, _P, _P] + [C.c_int64] * 4 + [C.c_int32, C.c_int32, C.c_double,
                                           _P, _P, _P, _P]),
+    # CTC forced alignment (additions to ABI 7)
+    "aamd_forced_align_states_per_lane": (C.c_int32, [C.c_int64]),
+    "aamd_forced_align_threads": (C.c_int32, [C.c_int64]),
+    "aamd_forced_align_prefetch": (C.c_int32, []),
+    "aamd_forced_align_backtrack_block": (C.c_int32, []),
+    "aamd_forced_align_workspace": (C.c_int64, [C.c_int64] * 3),
+    "aamd_forced_align": (C.c_int, [C.c_int32, _P, _P, C.c_int32, _P, _P, C.c_int32] + [C.c_int64] * 4 + [C.c_int32, _P, _P, _P,
+                                    _P]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS)

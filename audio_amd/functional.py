@@ -9,6 +9,7 @@ from __future__ import annotations
 
 import collections
 import ctypes as C
+import dataclasses
 import math
 import os
 import threading
@@ -34,7 +35,7 @@ __all__ = [
     "compute_deltas", "sliding_window_cmn", "detect_pitch_frequency", "mask_along_axis", "mask_along_axis_iid",
     "add_noise", "preemphasis", "deemphasis", "convolve",
     "psd", "mvdr_weights_souden", "mvdr_weights_rtf", "rtf_power", "rtf_evd", "apply_beamforming",
-    "rnnt_loss",
+    "rnnt_loss", "forced_align", "merge_tokens", "TokenSpan",
 ]
 
 # --------------------------------------------------------------------------- #
@@ -3352,6 +3353,142 @@ def _rnnt_loss_eager(logits: Tensor, targets: Tensor, logit_lengths: Tensor, tar
     if reduction == "sum":
         return costs.sum()
     return costs
+
+
+# --------------------------------------------------------------------------- #
+# CTC forced alignment (csrc/forced_align.h)                                  #
+# --------------------------------------------------------------------------- #
+FORCED_ALIGN_MAX_L = 2047            # AAMD_FORCED_ALIGN_MAX_L: the longest transcript axis the forward kernel serves
+_ALIGN_INTS = (torch.int32, torch.int64)
+
+
+def forced_align_tiles() -> Tuple[Tuple[Tuple[int, int, int], ...], int, int, int]:
+    """(((largest L, states per lane, lanes per workgroup) of every forward configuration, by L), steps the forward's
+    gathers run ahead, frames per backtrack block, largest L) of csrc/forced_align.h."""
+    lib = _lib.lib()
+    configs, prev = [], None
+    for L in range(FORCED_ALIGN_MAX_L + 1):
+        cur = (int(lib.aamd_forced_align_states_per_lane(L)), int(lib.aamd_forced_align_threads(L)))
+        if cur != prev and prev is not None:
+            configs.append((L - 1,) + prev)
+        prev = cur
+    configs.append((FORCED_ALIGN_MAX_L,) + prev)
+    return tuple(configs), int(lib.aamd_forced_align_prefetch()), int(lib.aamd_forced_align_backtrack_block()), FORCED_ALIGN_MAX_L
+
+
+def _forced_align_check(log_probs: Tensor, targets: Tensor, input_lengths: Optional[Tensor], target_lengths: Optional[Tensor],
+                        blank: int) -> None:
+    """The host-side checks of F.forced_align, with the reference's exception types.  Nothing is read from the device."""
+    if log_probs.dim() != 3:
+        raise ValueError(f"log_probs must be 3-D (batch, frame, class), got {tuple(log_probs.shape)}")
+    if targets.dim() != 2:
+        raise ValueError(f"targets must be 2-D (batch, label), got {tuple(targets.shape)}")
+    B, T_, C_ = log_probs.shape
+    if targets.shape[0] != B:
+        raise ValueError(f"batch sizes differ: log_probs {B}, targets {targets.shape[0]}")
+    for t, what in ((input_lengths, "input_lengths"), (target_lengths, "target_lengths")):
+        if t is not None and (t.dim() != 1 or t.shape[0] != B):
+            raise ValueError(f"{what} must be 1-D of the batch size {B}, got {tuple(t.shape)}")
+    if T_ < 1 or C_ < 1:
+        raise ValueError(f"log_probs needs at least one frame and one class, got {tuple(log_probs.shape)}")
+    if log_probs.dtype not in _RNNT_DTYPES:
+        raise TypeError(f"log_probs must be float32, float64, float16 or bfloat16 (got {log_probs.dtype})")
+    if targets.dtype not in _ALIGN_INTS:
+        raise TypeError(f"targets must be int32 or int64 (got {targets.dtype})")
+    lengths = [(t, what) for t, what in ((input_lengths, "input_lengths"), (target_lengths, "target_lengths")) if t is not None]
+    for t, what in lengths:
+        if t.dtype not in _ALIGN_INTS:
+            raise TypeError(f"{what} must be int32 or int64 (got {t.dtype})")
+    if len(lengths) == 2 and input_lengths.dtype != target_lengths.dtype:
+        raise TypeError(f"input_lengths and target_lengths must have one dtype (got {input_lengths.dtype} and "
+                        f"{target_lengths.dtype})")
+    tensors = [(log_probs, "log_probs"), (targets, "targets")] + lengths
+    for t, what in tensors:
+        if not t.is_contiguous():
+            raise ValueError(f"{what} must be contiguous")
+    if blank >= C_ or blank < 0:
+        raise ValueError("blank must be within [0, log_probs.shape[-1])")
+    if targets.shape[1] > FORCED_ALIGN_MAX_L:
+        raise NotImplementedError(f"audio_amd: forced_align serves transcripts up to L = {FORCED_ALIGN_MAX_L} labels (got "
+                                  f"{targets.shape[1]}): the lattice of one example belongs to one workgroup")
+    for t, what in tensors:
+        if not t.is_cuda:
+            raise RuntimeError(f"audio_amd: {what} must be on an MI355X (ROCm) device, got {t.device}. "
+                               "The HIP kernels have no CPU fallback.")
+        if t.device != log_probs.device:
+            raise RuntimeError(f"audio_amd: {what} must be on the log_probs' device")
+
+
+def _forced_align_launch(log_probs: Tensor, targets: Tensor, input_lengths: Tensor, target_lengths: Tensor,
+                         blank: int) -> Tuple[Tensor, Tensor]:
+    """(paths, scores): the forward and the backtrack through the C ABI.  The workspace is written and read on the device only."""
+    B, T_, C_ = log_probs.shape
+    L = targets.shape[1]
+    lib = _lib.lib()
+    paths = torch.empty((B, T_), dtype=targets.dtype, device=log_probs.device)
+    scores = torch.empty((B, T_), dtype=log_probs.dtype, device=log_probs.device)
+    if B:
+        ws = torch.empty((max(int(lib.aamd_forced_align_workspace(B, T_, L)), 16),), dtype=torch.uint8, device=log_probs.device)
+        with torch.cuda.device(log_probs.device):
+            _lib.check(lib.aamd_forced_align(_RNNT_DTYPES[log_probs.dtype], _lib.ptr(log_probs), _lib.ptr(targets) or None,
+                                             int(targets.dtype == torch.int64), _lib.ptr(input_lengths), _lib.ptr(target_lengths),
+                                             int(input_lengths.dtype == torch.int64), B, T_, C_, L, blank, ws.data_ptr(),
+                                             paths.data_ptr(), scores.data_ptr(), _lib.current_stream(log_probs.device)))
+    return paths, scores
+
+
+def forced_align(log_probs: Tensor, targets: Tensor, input_lengths: Optional[Tensor] = None,
+                 target_lengths: Optional[Tensor] = None, blank: int = 0) -> Tuple[Tensor, Tensor]:
+    r"""CTC forced alignment (reference: F.forced_align): the most likely frame-level labelling of ``log_probs`` ``(B, T, C)``
+    that collapses to ``targets`` ``(B, L)``.  Returns ``paths`` ``(B, T)`` in the dtype of ``targets`` and ``scores`` ``(B, T)``,
+    the elements ``log_probs[b, t, paths[b, t]]`` copied bit for bit.  The Viterbi recurrence accumulates in float64 for every
+    input dtype; ties keep the smaller move.  The whole time loop and the backtrack run on the device in two launches, the
+    lengths and labels are read there -- no synchronisation, so the call can be captured in a graph -- and a ragged batch is
+    served (the reference refuses ``B > 1``).  Frames from ``input_lengths[b]`` on get ``blank`` / 0; an example that cannot be
+    aligned (a length out of range, fewer frames than labels plus adjacent equal labels, a live label outside ``[0, C)`` or
+    equal to ``blank``) gets ``-1`` / NaN over its whole row instead of the reference's host-side error.  A plain Python entry
+    point through the C ABI: not registered as a dispatcher op."""
+    _forced_align_check(log_probs, targets, input_lengths, target_lengths, blank)
+    B, T_, _ = log_probs.shape
+    ldt = (input_lengths if input_lengths is not None else target_lengths if target_lengths is not None else targets).dtype
+    if input_lengths is None:
+        input_lengths = torch.full((B,), T_, dtype=ldt, device=log_probs.device)
+    if target_lengths is None:
+        target_lengths = torch.full((B,), targets.shape[1], dtype=ldt, device=log_probs.device)
+    return _forced_align_launch(log_probs.detach(), targets, input_lengths, target_lengths, int(blank))
+
+
+@dataclasses.dataclass
+class TokenSpan:
+    """A run of one token in an alignment (reference: F.TokenSpan): frames ``[start, end)`` and their mean score."""
+    token: int
+    start: int
+    end: int
+    score: float
+
+    def __len__(self) -> int:
+        return self.end - self.start
+
+
+def merge_tokens(tokens: Tensor, scores: Tensor, blank: int = 0) -> List[TokenSpan]:
+    r"""Runs of equal tokens of a frame-level alignment as ``TokenSpan``s, blank runs dropped (reference: F.merge_tokens).
+    ``score`` is the mean of the run's scores in float64.  The result is a Python list, so the two tensors are copied to the
+    host once, from any device, and the rest is host bookkeeping."""
+    if tokens.ndim != 1 or scores.ndim != 1:
+        raise ValueError("`tokens` and `scores` must be 1D Tensor.")
+    if len(tokens) != len(scores):
+        raise ValueError("`tokens` and `scores` must be the same length.")
+    n = len(tokens)
+    if n == 0:
+        return []
+    if tokens.device.type != "cpu":                            # one device-to-host copy of both
+        packed = torch.stack((tokens.to(torch.float64), scores.detach().to(torch.float64))).cpu().numpy()
+        tok, sc = packed[0].astype(np.int64), packed[1]
+    else:
+        tok, sc = tokens.numpy().astype(np.int64), scores.detach().to(torch.float64).numpy()
+    edges = [0] + (np.flatnonzero(tok[1:] != tok[:-1]) + 1).tolist() + [n]
+    return [TokenSpan(token=int(tok[s]), start=s, end=e, score=float(sc[s:e].mean()))
+            for s, e in zip(edges[:-1], edges[1:]) if tok[s] != blank]
 
 
 @_reduced_precision_io

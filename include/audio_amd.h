@@ -55,6 +55,8 @@
  *   aamd_beamform_apply       ABI 7 as well
  *   aamd_rnnt_loss_forward    F.rnnt_loss / T.RNNTLoss (the reference's compiled transducer loss, libtorchaudio/rnnt):
  *   aamd_rnnt_loss_backward   one read of the logits forward, one read and one write backward -- additions to ABI 7 as well
+ *   aamd_forced_align         F.forced_align (the reference's libtorchaudio/forced_align: one launch per frame and a host
+ *                             backtrack there; two launches here) -- an addition to ABI 7 as well
  *   aamd_detect_pitch_f32     F.detect_pitch_frequency (_compute_nccf + _find_max_per_frame + _median_smoothing in the
  *                             reference; an addition to ABI 7 as well)
  *
@@ -691,6 +693,34 @@ int aamd_rnnt_loss_backward(int32_t dtype, const void* logits, const int32_t* ta
                             const int32_t* target_lengths, int64_t batch, int64_t max_t, int64_t max_u1, int64_t vocab,
                             int32_t blank, int32_t fused_log_softmax, double clamp, const void* workspace,
                             const double* grad_costs, void* grad, void* stream);
+
+/* ---- CTC forced alignment (additions to ABI 7; csrc/forced_align.h) -------------------------------------------------- */
+
+#define AAMD_FORCED_ALIGN_MAX_L 2047 /* the longest transcript axis the forward kernel serves (2 L + 1 states) */
+
+/* What the launcher picks for a transcript axis of max_l labels: consecutive states per lane (4 or 16) and lanes per
+ * workgroup (64 or 256); the steps the forward's gathers run ahead; the frames per block of the backtrack. */
+int32_t aamd_forced_align_states_per_lane(int64_t max_l);
+int32_t aamd_forced_align_threads(int64_t max_l);
+int32_t aamd_forced_align_prefetch(void);
+int32_t aamd_forced_align_backtrack_block(void);
+
+/* Bytes of device workspace a call needs (16-byte aligned; written and read on the device only): one int32 per example and
+ * 2 bits per (example, frame, state).  0 for max_l > AAMD_FORCED_ALIGN_MAX_L. */
+int64_t aamd_forced_align_workspace(int64_t batch, int64_t max_t, int64_t max_l);
+
+/* F.forced_align.  log_probs dense (batch, max_t, classes) of `dtype` (AAMD_SA_*), targets dense (batch, max_l) int32 or
+ * int64 (targets_int64), input_lengths / target_lengths (batch,) int32 or int64 (lengths_int64), all on the device and read
+ * there: no synchronisation.  blank in [0, classes).  paths (batch, max_t) of the targets' type: the label of the Viterbi
+ * state of every frame (float64 accumulation; ties keep the smaller move); scores (batch, max_t) of `dtype`:
+ * log_probs[b][t][paths[b][t]] copied bit for bit.  Frames from input_lengths[b] on: blank / 0.  An example with an input
+ * length outside [1, max_t], a target length outside [0, max_l], fewer frames than labels plus adjacent equal labels, or a
+ * live label outside [0, classes) or equal to blank gets -1 / NaN over its whole row, and nothing is indexed with those
+ * values.  max_l > AAMD_FORCED_ALIGN_MAX_L: AAMD_EUNSUPPORTED.  Two launches (forward, backtrack). */
+int aamd_forced_align(int32_t dtype, const void* log_probs, const void* targets, int32_t targets_int64,
+                      const void* input_lengths, const void* target_lengths, int32_t lengths_int64, int64_t batch,
+                      int64_t max_t, int64_t classes, int64_t max_l, int32_t blank, void* workspace, void* paths, void* scores,
+                      void* stream);
 
 #ifdef __cplusplus
 }
