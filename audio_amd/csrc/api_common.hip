@@ -40,6 +40,7 @@ int policy() {
     if (std::getenv("AAMD_FFTCONV_FDL") != nullptr) p |= AAMD_POLICY_FFTCONV_FDL;
     if (std::getenv("AAMD_RESAMPLE_B32") != nullptr) p |= AAMD_POLICY_RESAMPLE_B32;
     if (std::getenv("AAMD_MEL400_NO_POOL") != nullptr) p |= AAMD_POLICY_MEL400_NO_POOL;
+    if (std::getenv("AAMD_MEL400_SCALAR") != nullptr) p |= AAMD_POLICY_MEL400_SCALAR;
     int expected = -1;
     g_policy.compare_exchange_strong(expected, p);
     p = g_policy.load(std::memory_order_relaxed);
@@ -133,7 +134,8 @@ int aamd_set_kernel_policy(int flags) {
   const int prev = policy();
   if (flags >= 0) g_policy.store(flags & (AAMD_POLICY_FORCE_GENERIC | AAMD_POLICY_MEL400_WIDE | AAMD_POLICY_ISTFT_ATOMIC |
                                           AAMD_POLICY_RESAMPLE_FP32 | AAMD_POLICY_FFTCONV_NO_FDL | AAMD_POLICY_FFTCONV_FDL |
-                                          AAMD_POLICY_FFTCONV_COMPLEX | AAMD_POLICY_RESAMPLE_B32 | AAMD_POLICY_MEL400_NO_POOL));
+                                          AAMD_POLICY_FFTCONV_COMPLEX | AAMD_POLICY_RESAMPLE_B32 | AAMD_POLICY_MEL400_NO_POOL |
+                                          AAMD_POLICY_MEL400_SCALAR));
   return prev;
 }
 

@@ -50,7 +50,7 @@ int mel_prologue(const aamd_stft_desc* desc, const aamd_mel_bands* bands, bool b
 unsigned* mel400_pool_block(hipStream_t s);
 #endif
 
-template <int EPI, int H, typename TIn, int NR, int SIG = 0>
+template <int EPI, int H, typename TIn, int NR, int SIG = 0, int AR = m400::AR_LEGACY>
 int launch_fft400_nr(const StftGeom& g, const MelBandsDev& mb, const TIn* wav, const float* window,
                      const float* twiddle, float* out, const m400::Epi400& epi_in, hipStream_t s) {
   if (g.rows == 0) return AAMD_OK;
@@ -69,7 +69,7 @@ int launch_fft400_nr(const StftGeom& g, const MelBandsDev& mb, const TIn* wav, c
   }
   if (lds > dev_props().lds_per_block_optin)
     return fail(AAMD_EUNSUPPORTED, "audio_amd: mel filterbank too large for the LDS of this device");
-  auto kern = m400::melspec400_kernel<0, EPI, H, TIn, NR, SIG>;
+  auto kern = m400::melspec400_kernel<0, EPI, H, TIn, NR, SIG, AR>;
 #ifdef AAMD_LAB    // tools-only instantiations are compiled into the lab library only (python -m audio_amd._build --lab)
   if (EPI == m400::EPI400_MFCC && epi.lab != 0) kern = m400::melspec400_kernel<(EPI == m400::EPI400_MFCC ? 524288 : 0), EPI, H, TIn, NR, SIG>;
 #endif
@@ -123,8 +123,16 @@ int launch_fft400_h(const StftGeom& g, const MelBandsDev& mb, const TIn* wav, co
     // the 80-mel HTK / Slaney banks of the 16 kHz front-ends (headline hop, float input): band reduction compiled for them
     if constexpr (H == 8 && sizeof(TIn) == 4 && std::is_same<TIn, float>::value &&
                   (EPI == m400::EPI400_MEL || EPI == m400::EPI400_MFCC)) {   // (MEL_DB: the straight-line form spills 4 registers)
-      if (mb.table_sig == m400::kSigHtk80 && mb.n_mels == 80)
+      if (mb.table_sig == m400::kSigHtk80 && mb.n_mels == 80) {
+        // the headline shape: roundings pinned in the source, paired operations as packed fp32 -- or, by policy, the same
+        // arithmetic one scalar instruction per operation (bit-identical; tests and A/B runs)
+        if constexpr (EPI == m400::EPI400_MEL) {
+          if (policy() & AAMD_POLICY_MEL400_SCALAR)
+            return launch_fft400_nr<EPI, H, TIn, 4, m400::kSigHtk80, m400::kArScalar>(g, mb, wav, window, twiddle, out, epi, s);
+          return launch_fft400_nr<EPI, H, TIn, 4, m400::kSigHtk80, m400::kArPacked>(g, mb, wav, window, twiddle, out, epi, s);
+        }
         return launch_fft400_nr<EPI, H, TIn, 4, m400::kSigHtk80>(g, mb, wav, window, twiddle, out, epi, s);
+      }
       if (mb.table_sig == m400::kSigSlaney80 && mb.n_mels == 80)
         return launch_fft400_nr<EPI, H, TIn, 4, m400::kSigSlaney80>(g, mb, wav, window, twiddle, out, epi, s);
     }

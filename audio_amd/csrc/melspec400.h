@@ -426,7 +426,142 @@ AAMD_HD void dft5(const float* xr, const float* xi, float* o_r, float* o_i) {
   o_r[3] = m2r - u2i; o_i[3] = m2i + u2r;
 }
 
+// ---- arithmetic of the signature instantiation: roundings pinned in the source, pairs issued as packed fp32 ----------------
+// -ffp-contract=fast lets the compiler choose which product of a b + c d is fused, and it chooses per SITE (moving one twiddle
+// batch from LDS to registers flipped two of them: profiles/r07_b_mel400_lab_trim_ab.txt).  With AR_PIN the ambiguous
+// expressions are written as fmaf + plain products under `fp contract(off)`, in exactly the shapes the 80-mel HTK
+// instantiation compiled to before (read from its ISA, site by site):
+//   dft5      u1 = fma(S2, t4, S1 t3), u2 = fma(S2, t3, -(S1 t4)), m = fma(C', t2, fma(C, t1, x0));
+//             only the imaginary u1 of the butterflies k1 = 1 and 3 of the SECOND transform is fma(S1, t3, S2 t4)
+//   twiddle   wr = fma(yr, tr, -(yi ti)), wi = fma(yi, tr, yr ti); columns 16 and 18: wi = fma(yr, ti, yi tr)
+//   power     fma(ar, ar, ai ai), fma(br, br, bi bi)
+// so the result no longer depends on where the operands live.  Every other instantiation (and istft400.h) compiles the
+// unpinned source, unchanged.  The AR_PK_* bits issue the paired operations of a phase as v_pk_*_f32: each half of a packed
+// instruction is the IEEE operation of its scalar twin (same operands, same order), so the output is bit for bit the same.
+enum { AR_LEGACY = 0, AR_PIN = 1, AR_PK_BAND = 2, AR_PK_TW = 4, AR_PK_POW = 8 };
+// One compile-time switch per packed phase.  All three are OFF: each is bit-identical on finite data but none beat the pinned
+// scalar build in the lab (band + 1.3 us, twiddle + 0.9 us, power + 0.6 us, all three + 4.5 us per launch of 66 us,
+// profiles/r08_a_mel400_packed_ab.txt), and with them on the NaN bit patterns of rows holding inf / NaN differ
+// from the scalar twin's (tests/test_melspec400_packed.py, special values).  The two DFT-20 are not packed.
+#ifndef AAMD_M400_PK_BAND
+#define AAMD_M400_PK_BAND 0
+#endif
+#ifndef AAMD_M400_PK_TW
+#define AAMD_M400_PK_TW 0
+#endif
+#ifndef AAMD_M400_PK_POW
+#define AAMD_M400_PK_POW 0
+#endif
+constexpr int kArScalar = AR_PIN;      // AAMD_POLICY_MEL400_SCALAR: the same roundings, one scalar instruction per operation
+constexpr int kArPacked = AR_PIN | (AAMD_M400_PK_BAND ? AR_PK_BAND : 0) | (AAMD_M400_PK_TW ? AR_PK_TW : 0) |
+                          (AAMD_M400_PK_POW ? AR_PK_POW : 0);
+constexpr int kDft2U1iMask = 0xA;          // second transform: butterflies k1 whose imaginary u1 fuses the S1 product
+AAMD_HD constexpr bool tw_wi_swapped(int s) { return s == 16 || s == 18; }
+
+struct Pk2 { float lo, hi; };              // two floats that go through the same operation
+#if defined(__HIP_DEVICE_COMPILE__)
+typedef float pkf2 __attribute__((ext_vector_type(2)));
+typedef float pkf4 __attribute__((ext_vector_type(4)));
+// Operand halves are picked per instruction (op_sel = source of the low half, op_sel_hi = of the high half; 0 = the pair's
+// low register), a half is negated with neg_lo / neg_hi: no v_mov, no v_xor.  (The compiler emits the packed instructions
+// for 2-element vectors by itself and folds broadcasts, but not the negation of one half.)
+#define AAMD_PK3(NAME, MODS)                                                                   \
+  __device__ __forceinline__ pkf2 NAME(pkf2 a, pkf2 b, pkf2 c) {                               \
+    pkf2 d;                                                                                    \
+    asm("v_pk_fma_f32 %0, %1, %2, %3 " MODS : "=v"(d) : "v"(a), "v"(b), "v"(c));               \
+    return d;                                                                                  \
+  }
+#define AAMD_PK2(NAME, OP, MODS)                                                               \
+  __device__ __forceinline__ pkf2 NAME(pkf2 a, pkf2 b) {                                       \
+    pkf2 d;                                                                                    \
+    asm(OP " %0, %1, %2 " MODS : "=v"(d) : "v"(a), "v"(b));                                    \
+    return d;                                                                                  \
+  }
+AAMD_PK3(pk_fma, "")                                                             // (a.lo b.lo + c.lo, a.hi b.hi + c.hi)
+AAMD_PK3(pk_fma_alo, "op_sel:[0,0,0] op_sel_hi:[0,1,1]")                         // a.lo broadcast
+AAMD_PK3(pk_fma_ahi, "op_sel:[1,0,0] op_sel_hi:[1,1,1]")                         // a.hi broadcast
+AAMD_PK3(pk_fma_blo_nclo, "op_sel:[0,0,0] op_sel_hi:[1,0,1] neg_lo:[0,0,1]")     // b.lo broadcast, - c.lo
+AAMD_PK3(pk_fma_alo_nclo, "op_sel:[0,0,0] op_sel_hi:[0,1,1] neg_lo:[0,0,1]")     // a.lo broadcast, - c.lo
+AAMD_PK2(pk_fma_alo_z, "v_pk_fma_f32", ", 0 op_sel:[0,0,0] op_sel_hi:[0,1,0]")   // a.lo broadcast, + 0
+AAMD_PK2(pk_fma_ahi_z, "v_pk_fma_f32", ", 0 op_sel:[1,0,0] op_sel_hi:[1,1,0]")   // a.hi broadcast, + 0
+AAMD_PK2(pk_mul, "v_pk_mul_f32", "")
+AAMD_PK2(pk_mul_aswap_bhi, "v_pk_mul_f32", "op_sel:[1,1] op_sel_hi:[0,1]")       // (a.hi b.hi, a.lo b.hi)
+AAMD_PK2(pk_mul_ahi_bswap, "v_pk_mul_f32", "op_sel:[1,1] op_sel_hi:[1,0]")       // (a.hi b.hi, a.hi b.lo)
+AAMD_PK2(pk_add_lolo_nbhi, "v_pk_add_f32", "op_sel:[0,0] op_sel_hi:[0,0] neg_hi:[0,1]")   // (a.lo + b.lo, a.lo - b.lo)
+AAMD_PK2(pk_add_hihi_nblo, "v_pk_add_f32", "op_sel:[1,1] op_sel_hi:[1,1] neg_lo:[0,1]")   // (a.hi - b.hi, a.hi + b.hi)
+#undef AAMD_PK3
+#undef AAMD_PK2
+#endif
+
+// twiddle product (yr + i yi)(tr + i ti), pinned; SW = the column is one of tw_wi_swapped()
+template <bool SW, bool PK>
+AAMD_HD Pk2 tw_mul_pin(float yr, float yi, float tr, float ti) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  if (PK) {
+    const pkf2 y = {yr, yi}, t = {tr, ti};
+    const pkf2 w = SW ? pk_fma_alo_nclo(y, t, pk_mul_ahi_bswap(y, t)) : pk_fma_blo_nclo(y, t, pk_mul_aswap_bhi(y, t));
+    return Pk2{w.x, w.y};
+  }
+#endif
+  {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+    const float p = yi * ti;
+    const float q = SW ? yi * tr : yr * ti;
+    return Pk2{__builtin_fmaf(yr, tr, -p), SW ? __builtin_fmaf(yr, ti, q) : __builtin_fmaf(yi, tr, q)};
+  }
+}
+
+// (|Z + conj C|^2, |Z - conj C|^2) of Z = zr + i zi, C = cr + i ci, pinned
+template <bool PK>
+AAMD_HD Pk2 sep_pow_pin(float zr, float zi, float cr, float ci) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  if (PK) {
+    const pkf2 z = {zr, zi}, c = {cr, ci};
+    const pkf2 u = pk_add_lolo_nbhi(z, c), v = pk_add_hihi_nblo(z, c);      // (ar, br), (ai, bi)
+    const pkf2 P = pk_fma(u, u, pk_mul(v, v));
+    return Pk2{P.x, P.y};
+  }
+#endif
+  {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+    const float ar = zr + cr, ai = zi - ci;
+    const float br = zr - cr, bi = zi + ci;
+    const float pa = ai * ai, pb = bi * bi;
+    return Pk2{__builtin_fmaf(ar, ar, pa), __builtin_fmaf(br, br, pb)};
+  }
+}
+
+template <bool U1I_S1>      // the imaginary u1 fuses the S1 product (see above)
+AAMD_HD void dft5_pin(const float* xr, const float* xi, float* o_r, float* o_i) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  constexpr float C1 = 0.30901699437494742f, C2 = -0.80901699437494742f;
+  constexpr float S1 = 0.95105651629515357f, S2 = 0.58778525229247313f;
+  const float t1r = xr[1] + xr[4], t1i = xi[1] + xi[4];
+  const float t2r = xr[2] + xr[3], t2i = xi[2] + xi[3];
+  const float t3r = xr[1] - xr[4], t3i = xi[1] - xi[4];
+  const float t4r = xr[2] - xr[3], t4i = xi[2] - xi[3];
+  const float m1r = __builtin_fmaf(C2, t2r, __builtin_fmaf(C1, t1r, xr[0])), m1i = __builtin_fmaf(C2, t2i, __builtin_fmaf(C1, t1i, xi[0]));
+  const float m2r = __builtin_fmaf(C1, t2r, __builtin_fmaf(C2, t1r, xr[0])), m2i = __builtin_fmaf(C1, t2i, __builtin_fmaf(C2, t1i, xi[0]));
+  const float p1r = S1 * t3r, p1i = U1I_S1 ? S2 * t4i : S1 * t3i;
+  const float u1r = __builtin_fmaf(S2, t4r, p1r), u1i = U1I_S1 ? __builtin_fmaf(S1, t3i, p1i) : __builtin_fmaf(S2, t4i, p1i);
+  const float p2r = S1 * t4r, p2i = S1 * t4i;
+  const float u2r = __builtin_fmaf(S2, t3r, -p2r), u2i = __builtin_fmaf(S2, t3i, -p2i);
+  o_r[0] = xr[0] + t1r + t2r; o_i[0] = xi[0] + t1i + t2i;
+  o_r[1] = m1r + u1i; o_i[1] = m1i - u1r;   // m1 - i*u1
+  o_r[4] = m1r - u1i; o_i[4] = m1i + u1r;
+  o_r[2] = m2r + u2i; o_i[2] = m2i - u2r;   // m2 - i*u2
+  o_r[3] = m2r - u2i; o_i[3] = m2i + u2r;
+}
+
 // Good-Thomas: n = (5 n1 + 4 n2) mod 20, k = (5 k1 + 16 k2) mod 20.
+// PIN: dft5_pin, bit k1 of U1I_MASK = its U1I_S1
+template <bool PIN = false, int U1I_MASK = 0>
 AAMD_HD void dft20(const float (&xr)[20], const float (&xi)[20], float (&yr)[20], float (&yi)[20]) {
   float tr[4][5], ti[4][5];
 #pragma unroll
@@ -441,7 +576,9 @@ AAMD_HD void dft20(const float (&xr)[20], const float (&xi)[20], float (&yr)[20]
 #pragma unroll
   for (int k1 = 0; k1 < 4; ++k1) {
     float o_r[5], o_i[5];
-    dft5(tr[k1], ti[k1], o_r, o_i);
+    if (!PIN) dft5(tr[k1], ti[k1], o_r, o_i);
+    else if ((U1I_MASK >> k1) & 1) dft5_pin<true>(tr[k1], ti[k1], o_r, o_i);      // (k1 is a constant once unrolled)
+    else dft5_pin<false>(tr[k1], ti[k1], o_r, o_i);
 #pragma unroll
     for (int k2 = 0; k2 < 5; ++k2) {
       const int k = (5 * k1 + 16 * k2) % 20;
@@ -531,7 +668,7 @@ __device__ __forceinline__ void tr_store5(unsigned lds_base, const float (&wr)[5
 
 // DFT-20 over q of the lane's 20 complex inputs, twiddle by W400^(b s), transposed write (shared by the forward
 // kernel and the inverse / adjoint kernel of istft400.h, whose inputs are spectrum bins instead of windowed samples)
-template <int TREG = 0>      // leading batches of five columns whose twiddles are in registers (`twr`); the rest comes from the LDS table
+template <int TREG = 0, int AR = AR_LEGACY>      // leading batches of five columns whose twiddles are in registers (`twr`); the rest comes from the LDS table
 AAMD_HD void phase_a_core(const LaneConst& c, const float (&xr)[20], const float (&xi)[20], float* __restrict__ lds,
                           const float* twr = nullptr) {
   // The twiddle table and the transposition rows live in the same LDS array but never overlap.  The reads of batch
@@ -551,7 +688,7 @@ AAMD_HD void phase_a_core(const LaneConst& c, const float (&xr)[20], const float
   };
   if (TREG < 4) tw_load(TREG);
   float yr[20], yi[20];
-  dft20(xr, xi, yr, yi);
+  dft20<(AR & AR_PIN) != 0, 0>(xr, xi, yr, yi);
 #if defined(__HIP_DEVICE_COMPILE__)
   const unsigned lds_base = (unsigned)(uintptr_t)lds;      // wave-uniform LDS byte address
 #endif
@@ -573,6 +710,11 @@ AAMD_HD void phase_a_core(const LaneConst& c, const float (&xr)[20], const float
       if (s == 0) {
         wr[j] = yr[0];
         wi[j] = yi[0];
+      } else if (AR & AR_PIN) {
+        const Pk2 w = tw_wi_swapped(s) ? tw_mul_pin<true, (AR & AR_PK_TW) != 0>(yr[s], yi[s], tw[2 * j], tw[2 * j + 1])
+                                       : tw_mul_pin<false, (AR & AR_PK_TW) != 0>(yr[s], yi[s], tw[2 * j], tw[2 * j + 1]);
+        wr[j] = w.lo;
+        wi[j] = w.hi;
       } else {
         wr[j] = yr[s] * tw[2 * j] - yi[s] * tw[2 * j + 1];
         wi[j] = yr[s] * tw[2 * j + 1] + yi[s] * tw[2 * j];
@@ -597,7 +739,7 @@ AAMD_HD void phase_a_core(const LaneConst& c, const float (&xr)[20], const float
 //   A frame b beyond the end of the clip is NOT zeroed here (that cost 20 selects per tile): its
 //   spectrum is garbage that no store path writes (store_direct / store_wide / store_spec mask by
 //   frame) and that the dB epilogue excludes from the running maximum.
-template <int H, bool WREG = false, int TREG = 0>
+template <int H, bool WREG = false, int TREG = 0, int AR = AR_LEGACY>
 AAMD_HD void phase_a(const LaneConst& c, const float (&X)[Hop<H>::nx], float* lds, const float* winr = nullptr,
                      const float* twr = nullptr) {
   float xr[20], xi[20];
@@ -617,7 +759,7 @@ AAMD_HD void phase_a(const LaneConst& c, const float (&X)[Hop<H>::nx], float* ld
       }
     }
   }
-  phase_a_core<TREG>(c, xr, xi, lds, twr);
+  phase_a_core<TREG, AR>(c, xr, xi, lds, twr);
 }
 
 // ---- phase B1: read own row (then DFT-20 over b  ->  Z[col + 20 d] in registers) ----------
@@ -651,6 +793,7 @@ AAMD_HD void phase_b2_send(const LaneConst& c, const float (&zr)[20], const floa
 // ---- phase B2b: separate the two real spectra, |.|^2, write interleaved P rows ------------
 //   x = the exchanged values: q of lane ^ 1 (DPP swap), except on the self-paired columns 0 and 10,
 //   which keep their own q (exchange_partner below).  conj(Z[400-k]) for k = col + 20u is x[9 - u].
+template <int AR = AR_LEGACY>
 AAMD_HD void phase_b2(const LaneConst& c, const float (&zr)[20], const float (&zi)[20],
                       const float (&xr)[10], const float (&xi)[10], float* lds) {
   if (!c.active) return;
@@ -658,6 +801,11 @@ AAMD_HD void phase_b2(const LaneConst& c, const float (&zr)[20], const float (&z
 #pragma unroll
   for (int u = 0; u < 10; ++u) {
     const float cr = xr[9 - u], ci = xi[9 - u];
+    if (AR & AR_PIN) {
+      const Pk2 pw = sep_pow_pin<(AR & AR_PK_POW) != 0>(zr[u], zi[u], cr, ci);
+      *reinterpret_cast<F2*>(P + 40 * u) = F2{pw.lo, pw.hi};
+      continue;
+    }
     const float ar = zr[u] + cr, ai = zi[u] - ci;   // 2*A = Z[k] + conj(Z[N-k])
     const float br = zr[u] - cr, bi = zi[u] + ci;   // |2*B|: Z[k] - conj(Z[N-k])
     *reinterpret_cast<F2*>(P + 40 * u) = F2{ar * ar + ai * ai, br * br + bi * bi};
@@ -820,8 +968,32 @@ AAMD_HD void phase_b2_pad(int lane, float* lds) {
 // ---- phase C: banded mel reduction from the LDS power rows --------------------------------
 //   lane (p, slot) computes mel m = slot + 20 r of frames 2p and 2p + 1 in round r; the chunk
 //   count rc[r] is wave-uniform.  All LDS reads of a round are issued before its FMAs.
-template <int NC>
+template <int NC, bool PK = false, bool Z = false>      // Z: sa = sb = 0 on entry (the first packed tap adds the constant)
 AAMD_HD void mel_chunks(const float* wt, const float* P, float& sa, float& sb) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  if (PK) {      // (sa, sb) is one register pair, the b128 reads deliver (Pa, Pb) side by side: one v_pk_fma_f32 per tap, the weight broadcast
+    pkf4 w[NC], q0[NC], q1[NC];
+#pragma unroll
+    for (int k = 0; k < NC; ++k) {
+      w[k] = *reinterpret_cast<const pkf4*>(wt + 4 * k);
+      q0[k] = *reinterpret_cast<const pkf4*>(P + 8 * k);
+      q1[k] = *reinterpret_cast<const pkf4*>(P + 8 * k + 4);
+    }
+    pkf2 acc = {sa, sb};
+#pragma unroll
+    for (int k = 0; k < NC; ++k) {
+      const pkf2 w01 = __builtin_shufflevector(w[k], w[k], 0, 1), w23 = __builtin_shufflevector(w[k], w[k], 2, 3);
+      if (Z && k == 0) acc = pk_fma_alo_z(w01, __builtin_shufflevector(q0[k], q0[k], 0, 1));
+      else acc = pk_fma_alo(w01, __builtin_shufflevector(q0[k], q0[k], 0, 1), acc);
+      acc = pk_fma_ahi(w01, __builtin_shufflevector(q0[k], q0[k], 2, 3), acc);
+      acc = pk_fma_alo(w23, __builtin_shufflevector(q1[k], q1[k], 0, 1), acc);
+      acc = pk_fma_ahi(w23, __builtin_shufflevector(q1[k], q1[k], 2, 3), acc);
+    }
+    sa = acc.x;
+    sb = acc.y;
+    return;
+  }
+#endif
   F4 w[NC], q0[NC], q1[NC];
 #pragma unroll
   for (int k = 0; k < NC; ++k) {
@@ -878,7 +1050,7 @@ AAMD_HD void mel_regs_load(const LaneConst& c, const MelTab& mt, MelRegs<NR>& h)
 AAMD_HD constexpr int sig_chunks(int sig, int r) { return (sig >> (4 * r)) & 15; }
 constexpr int kSigHtk80 = 0x4221, kSigSlaney80 = 0x4211;      // melscale_fbanks(201, 0, 8000, 80, 16000): htk / slaney
 
-template <int NR = kMelMaxRounds, int SIG = 0, bool FENCED = false>
+template <int NR = kMelMaxRounds, int SIG = 0, bool FENCED = false, bool PK = false>
 AAMD_HD void phase_c(const LaneConst& c, const MelTab& mt, const float* lds,
                      float (&acc_a)[NR], float (&acc_b)[NR], const MelRegs<NR>* h = nullptr) {
   const float* Pp = lds + kPPair * c.p;
@@ -896,12 +1068,12 @@ AAMD_HD void phase_c(const LaneConst& c, const MelTab& mt, const float* lds,
       const float* P = Pp + (h ? h->poff(r) : 2 * mt.lo2[r * kMelSlots + c.pi]);
       const int nc = SIG != 0 ? sig_chunks(SIG, r) : (h ? h->nc[r] : mt.rc[r]);
       switch (nc) {
-        case 1: mel_chunks<1>(wt, P, sa, sb); break;
-        case 2: mel_chunks<2>(wt, P, sa, sb); break;
-        case 3: mel_chunks<3>(wt, P, sa, sb); break;
-        case 4: mel_chunks<4>(wt, P, sa, sb); break;
+        case 1: mel_chunks<1, PK, true>(wt, P, sa, sb); break;
+        case 2: mel_chunks<2, PK, true>(wt, P, sa, sb); break;
+        case 3: mel_chunks<3, PK, true>(wt, P, sa, sb); break;
+        case 4: mel_chunks<4, PK, true>(wt, P, sa, sb); break;
         default:
-          for (int k = 0; k < nc; ++k) mel_chunks<1>(wt + 4 * k, P + 8 * k, sa, sb);
+          for (int k = 0; k < nc; ++k) mel_chunks<1, PK>(wt + 4 * k, P + 8 * k, sa, sb);
       }
     }
     acc_a[r] = sa;
@@ -1115,7 +1287,8 @@ __device__ __forceinline__ void atomic_max_f32(float* addr, float v) {
 
 // NR = rounds of 20 mels the per-lane arrays are sized for: 4 (n_mels <= 80, the common front-ends: the control words of
 // the band table then live in registers, MelRegs) or kMelMaxRounds (up to 160 mels, control words re-read from LDS).
-template <int LAB, int EPI, int H = 8, typename TIn = float, int NR = kMelMaxRounds, int SIG = 0>
+// AR = arithmetic of the tile loop (AR_* above): AR_LEGACY for every instantiation but the 80-mel HTK one of the headline config.
+template <int LAB, int EPI, int H = 8, typename TIn = float, int NR = kMelMaxRounds, int SIG = 0, int AR = AR_LEGACY>
 __global__ void __launch_bounds__(64 * kWavesPerBlock, AAMD_M400_MINWAVES)
 melspec400_kernel(const TIn* __restrict__ wav, const float* __restrict__ window,
                   const float* __restrict__ tw400, MelBandsDev mb, float* __restrict__ out,
@@ -1260,12 +1433,16 @@ melspec400_kernel(const TIn* __restrict__ wav, const float* __restrict__ window,
 #ifndef AAMD_M400_TWREG
 #define AAMD_M400_TWREG 3
 #endif
+#ifndef AAMD_M400_TWREG_PIN
+#define AAMD_M400_TWREG_PIN 4
+#endif
   // Twiddle batches (of five columns) held in registers instead of re-read from the LDS table every tile: all four under lab
   // bit 14 (spills).  The signature instantiation runs at 136 registers, so three batches fit its 168 (164; - 3.0 % on the
   // headline batch, 67.3 -> 65.3 us, profiles/r03_i_mel400_lab_twiddle_regs.txt): 15 of the 20 ds_read_b64 per tile gone.
   // (Since the row stores take a scalar base the signature instantiation runs at 150 registers and a fourth batch fits, 159; it is
   // 0.6 us faster but NOT bit-identical -- the compiler contracts that batch's complex multiplies into other fma pairs, 9e-8 of the
-  // peak -- so it stays at three: profiles/r07_b_mel400_lab_trim_ab.txt.)
+  // peak -- so the unpinned source stays at three: profiles/r07_b_mel400_lab_trim_ab.txt.  With the roundings pinned in the source
+  // (AR_PIN) where the twiddles live no longer matters: AAMD_M400_TWREG_PIN = 4.)
   // The other float-input hop-160 instantiations get what their register count leaves (tests/test_no_spills.py keeps every
   // one of them out of scratch): Spectrogram 144 -> 2 batches, generic mel 149 / 135 (NR 4 / 8) -> 1 / 3, mel + dB 154 -> 1.
 #ifndef AAMD_M400_TWREG_DB
@@ -1276,7 +1453,7 @@ melspec400_kernel(const TIn* __restrict__ wav, const float* __restrict__ window,
 #endif
   constexpr bool kPlain = H == 8 && std::is_same<TIn, float>::value && LAB == 0;
   constexpr int kTwRegBatches = (LAB & 16384) ? 4
-                                : (SIG != 0 && EPI == EPI400_MEL) ? AAMD_M400_TWREG
+                                : (SIG != 0 && EPI == EPI400_MEL) ? ((AR & AR_PIN) ? AAMD_M400_TWREG_PIN : AAMD_M400_TWREG)
                                 : !kPlain ? 0
                                 : EPI == EPI400_SPEC ? 2
                                 : (EPI == EPI400_MEL && SIG == 0) ? (NR <= 4 ? 1 : 3)
@@ -1635,7 +1812,7 @@ melspec400_kernel(const TIn* __restrict__ wav, const float* __restrict__ window,
     // (behind stage_wait's vmcnt(0): the atomic flies during phase A and the column reads and is read in front of the next DMA)
     if (nxt_idx == kPendIdx) pool_request();
 #endif
-    phase_a<H, kWinRegs, kTwRegBatches>(c, X, lds, winr, twr);
+    phase_a<H, kWinRegs, kTwRegBatches, AR>(c, X, lds, winr, twr);
     if ((LAB & 32768) && nxt.staged) gload(nxt);        // X is dead: the next tile's samples fly during phases B and C
     wave_lds_fence();
     AAMD_M400_STAMP(0)   // claim, gather, window, first DFT-20, twiddles, transposed writes
@@ -1654,7 +1831,7 @@ melspec400_kernel(const TIn* __restrict__ wav, const float* __restrict__ window,
       if (nxt.staged && !(LAB & 8) && !fix) stage_issue(nxt);
     }
     if (LAB & 16) { wave_lds_fence(); cur = nxt; cur_idx = nxt_idx; continue; }
-    dft20(vr, vi, zr, zi);
+    dft20<(AR & AR_PIN) != 0, kDft2U1iMask>(vr, vi, zr, zi);
     phase_b2_send(c, zr, zi, qr, qi);
     exchange_partner(qr, qi, self_mask);
     wave_lds_fence();
@@ -1686,13 +1863,13 @@ melspec400_kernel(const TIn* __restrict__ wav, const float* __restrict__ window,
       cur_idx = nxt_idx;
       continue;
     }
-    phase_b2(c, zr, zi, qr, qi, lds);
+    phase_b2<AR>(c, zr, zi, qr, qi, lds);
     phase_b2_pad(lane, lds);
     wave_lds_fence();
     AAMD_M400_STAMP(3)     // power, P rows
     float acc_a[NR], acc_b[NR];
     if (LAB & 4) { wave_lds_fence(); cur = nxt; cur_idx = nxt_idx; continue; }
-    phase_c<NR, SIG, EPI == EPI400_MFCC>(c, mt, lds, acc_a, acc_b, mh);
+    phase_c<NR, SIG, EPI == EPI400_MFCC, (AR & AR_PK_BAND) != 0>(c, mt, lds, acc_a, acc_b, mh);
     if (LAB & 8388608) { asm volatile("" : "+v"(acc_a[0]), "+v"(acc_b[NR - 1])); }
     AAMD_M400_STAMP(4)     // band reduction
     if (kDb) {

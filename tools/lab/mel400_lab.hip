@@ -27,7 +27,10 @@ static int launch(const float* wav, const float* window, const float* tw, const 
 #ifndef LAB_SIG
 #define LAB_SIG 0
 #endif
-  auto kern = m400::melspec400_kernel<LAB, m400::EPI400_MEL, 8, float, 4, LAB_SIG>;
+#ifndef LAB_AR
+#define LAB_AR 0      /* arithmetic of the tile loop: m400::AR_* bits (1 pinned roundings, 2 / 4 / 8 packed band / twiddle / power) */
+#endif
+  auto kern = m400::melspec400_kernel<LAB, m400::EPI400_MEL, 8, float, 4, LAB_SIG, LAB_AR>;
   if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return -2;
   hipDeviceProp_t dp;
   int dev = 0;

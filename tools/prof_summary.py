@@ -83,7 +83,7 @@ def code_object_notes():
 
 
 def config_of(name: str, cluster: str) -> str:
-    m = re.match(r"aamd::m400::melspec400_kernel<(\d+),(\d+),(\d+),([^,]+),(\d+),(\d+)>", name)
+    m = re.match(r"aamd::m400::melspec400_kernel<(\d+),(\d+),(\d+),([^,]+),(\d+),(\d+)(?:,\d+)?>", name)
     if m:
         epi = int(m.group(2))
         tag = EPI.get(epi, "EPI?")
