@@ -386,20 +386,13 @@ AAMD_HD void mid_mac(int tid, const C32 (&h)[8], const C32 (&z)[8], C32 (&acc)[8
     }
   }
 }
-// tap spectra in the thread-owned layout.  AAMD_FDR_H16 = 0: complex index ((p * 8 + i) * 1024 + tid) of a y row's table -- eight
-// coalesced 8-byte loads per partition and thread; 1 (round 6): bins i and i + 1 of a thread lie side by side,
-// ((p * 4 + i / 2) * 1024 + tid) * 2 + (i & 1) -- four 16-byte loads: the 192 KB of tap spectra a step reads are a throughput cost
-// of the vector-memory path (the kernel without them ran 13 % faster, profiles/r05_c_fdr_lab_barriers_hloads.txt), and an 8-byte
+// tap spectra in the thread-owned layout: bins i and i + 1 of a thread lie side by side, complex index
+// ((p * 4 + i / 2) * 1024 + tid) * 2 + (i & 1) of a y row's table -- four 16-byte loads per partition and thread (rounds 3-5:
+// ((p * 8 + i) * 1024 + tid), eight 8-byte loads).  The 192 KB of tap spectra a step reads are a throughput cost of the
+// vector-memory path (the kernel without them ran 13 % faster, profiles/r05_c_fdr_lab_barriers_hloads.txt), and an 8-byte
 // access moves bytes at 0.54-0.70 of the 16-byte rate (MI355X_MICROARCH.md)
-#ifndef AAMD_FDR_H16
-#define AAMD_FDR_H16 1
-#endif
 AAMD_HD int64_t h_index(int p, int i, int tid) {
-#if AAMD_FDR_H16
   return (((int64_t)p * 4 + (i >> 1)) * kThreads + tid) * 2 + (i & 1);
-#else
-  return ((int64_t)p * 8 + i) * kThreads + tid;
-#endif
 }
 constexpr int64_t kHPerPart = 8 * kThreads;            // complex numbers per partition (= 8192)
 
@@ -499,17 +492,11 @@ constexpr float kSpectrumScale = 1.0f / (8.0f * (float)kM);      // un-halved sp
 #define AAMD_FDR_LAB_NOBAR 0
 #endif
 // The length-1024 pass runs on the 1024 elements of TWO neighbouring waves (w, w ^ 1) and the passes on either side of it are
-// wave-local: the two workgroup barriers around it are replaced by a rendezvous of the pair (AAMD_FDR_PAIRSYNC, default on) --
+// wave-local: the two workgroup barriers around it are replaced by a rendezvous of the pair (round 5) --
 // a wave waits for its neighbour only, not for the slowest of sixteen (the lab build without those two barriers: - 6.5 %).
 // gfx950 has no named barriers: each wave publishes an arrival counter in LDS and polls its neighbour's.  LDS executes a
 // wave's instructions in order, and the s_waitcnt in front of the flag write has every data write of the pass performed
 // before the counter moves; the reads behind the poll are issued after the neighbour's counter has been seen.
-#ifndef AAMD_FDR_PAIRSYNC
-#define AAMD_FDR_PAIRSYNC 1
-#endif
-#ifndef AAMD_FDR_WAR_BARRIER
-#define AAMD_FDR_WAR_BARRIER 0
-#endif
 __device__ __forceinline__ void pair_sync(unsigned* flags, unsigned gen) {
   // (release / acquire spelled out instead of relying on `volatile` and in-order LDS.  The fences name the LDS address
   // space only -- "local" -- so they lower to s_waitcnt lgkmcnt(0): a plain workgroup-scope release would also wait for the
@@ -529,8 +516,7 @@ __device__ __forceinline__ void pair_sync(unsigned* flags, unsigned gen) {
 #define AAMD_FDR_PAIR(BIT)                                                                \
   do {                                                                                    \
     if (AAMD_FDR_LAB_NOBAR & (BIT)) fco::wave_sync();                                      \
-    else if (AAMD_FDR_PAIRSYNC) pair_sync(pair_flags, ++pair_gen);                         \
-    else __syncthreads();                                                                 \
+    else pair_sync(pair_flags, ++pair_gen);                                               \
   } while (0)
 #define AAMD_FDR_BARRIER(BIT) do { if (AAMD_FDR_LAB_NOBAR & (BIT)) fco::wave_sync(); else __syncthreads(); } while (0)
 // the radix-2 between neighbouring lanes (lane ^ 1: DPP quad_perm [1, 0, 3, 2]) on all 16 floats of a thread, in place:
@@ -554,17 +540,9 @@ __device__ __forceinline__ void radix2_dpp(C32 (&u)[8], float s) {
 }
 // forward transform of the block in v (registers) to the digit-reversed spectrum in LDS; ends with a workgroup barrier
 // how many of the 7 twiddles of the length-128 pass live in registers, by partition count (the 3-partition kernel holds two
-// delayed spectra and has fewer registers to spare: tools/fdr_lab.py reports registers and scratch per setting)
-#ifndef AAMD_FDR_TW3_N12
-#define AAMD_FDR_TW3_N12 7
-#endif
-#ifndef AAMD_FDR_TW3_N3
-#define AAMD_FDR_TW3_N3 5
-#endif
-#ifndef AAMD_FDR_TW3_N4
-#define AAMD_FDR_TW3_N4 0
-#endif
-template <int NP> struct Tw3Regs { static constexpr int n = NP >= 4 ? AAMD_FDR_TW3_N4 : NP == 3 ? AAMD_FDR_TW3_N3 : AAMD_FDR_TW3_N12; };
+// delayed spectra and has fewer registers to spare: `tools/fdr_lab.py build` prints each kernel's registers and scratch)
+constexpr int kTw3N12 = 7, kTw3N3 = 5, kTw3N4 = 0;     // 1 or 2 partitions, 3, 4
+template <int NP> struct Tw3Regs { static constexpr int n = NP >= 4 ? kTw3N4 : NP == 3 ? kTw3N3 : kTw3N12; };
 template <int NR>
 __device__ __forceinline__ void forward_block(int tid, C32 (&v)[8], C32* lds, const C32* tl, const C32 (&tw3)[7]) {
   first_pass_from_regs(tid, v, lds, tl);
@@ -638,22 +616,6 @@ delay_line_kernel(Geom g, const float* __restrict__ x, const C32* __restrict__ t
   C32 tw3[7];
   load_tw3<kTw3>(tid, tl, tw3);
   const float r2s = radix2_sign(tid);
-#ifdef AAMD_FDR_PRIO
-  // lab (tools/fdr_lab.py): static issue priority per wave -- the four waves of a SIMD (w, w + 4, w + 8, w + 12) get distinct
-  // priorities so that they leave a pass one after the other instead of together
-  {
-#if AAMD_FDR_PRIO == 1
-    const int pr = __builtin_amdgcn_readfirstlane((threadIdx.x >> 8) & 3);
-#elif AAMD_FDR_PRIO == 2
-    const int pr = __builtin_amdgcn_readfirstlane(3 - ((threadIdx.x >> 8) & 3));
-#else
-    const int pr = __builtin_amdgcn_readfirstlane((threadIdx.x >> 9) & 1);
-#endif
-    if (pr == 1) __builtin_amdgcn_s_setprio(1);
-    else if (pr == 2) __builtin_amdgcn_s_setprio(2);
-    else if (pr == 3) __builtin_amdgcn_s_setprio(3);
-  }
-#endif
   const unsigned n_items = (unsigned)(g.rows * g.segs);          // < 2^31 (checked by the launcher): 32-bit item arithmetic
 #pragma unroll 1
   for (unsigned item = blockIdx.x; item < n_items; item += gridDim.x) {
@@ -683,11 +645,10 @@ delay_line_kernel(Geom g, const float* __restrict__ x, const C32* __restrict__ t
 #pragma unroll
       for (int i = 0; i < 8; ++i) acc[i] = C32{0.0f, 0.0f};
       C32 h0[8];                           // tap spectra of this thread's bins, one partition at a time
-      auto h_load = [&](int p) {           // partition p: 8 coalesced 8-byte loads from L2 (the thread-owned layout)
-        // ONE scalar base (the row's table) + a 32-bit vector byte offset per load: global_load_dwordx2 v, v_off, s[base].
-        // Left to itself the compiler forms eight 64-bit vector addresses per partition (16 registers and 16 carry chains)
-        // or, with per-load scalar bases, hoists 24 base pairs out of the step loop and spills scalar registers.
-#if AAMD_FDR_H16
+      auto h_load = [&](int p) {           // partition p: 4 coalesced 16-byte loads from L2 (the thread-owned layout)
+        // ONE scalar base (the row's table) + a 32-bit vector byte offset per load: global_load_dwordx4 v, v_off, s[base].
+        // Left to itself the compiler forms 64-bit vector addresses per load (registers and carry chains)
+        // or, with per-load scalar bases, hoists the base pairs out of the step loop and spills scalar registers.
         const unsigned off = (unsigned)fco::opaque(tid) * 16u;
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
@@ -697,15 +658,6 @@ delay_line_kernel(Geom g, const float* __restrict__ x, const C32* __restrict__ t
           h0[2 * i] = C32{q.x, q.y};
           h0[2 * i + 1] = C32{q.z, q.w};
         }
-#else
-        const unsigned off = (unsigned)fco::opaque(tid) * (unsigned)sizeof(C32);
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-          unsigned o = off + (unsigned)((p * 8 + i) * kThreads * (int)sizeof(C32));
-          asm volatile("" : "+v"(o));
-          h0[i] = *reinterpret_cast<const C32*>(reinterpret_cast<const char*>(Hr) + o);
-        }
-#endif
 #ifdef AAMD_FDR_LAB_NOH
 #pragma unroll
         for (int i = 0; i < 8; ++i) h0[i] = C32{1.0f + (float)i, 0.5f};
@@ -768,10 +720,7 @@ delay_line_kernel(Geom g, const float* __restrict__ x, const C32* __restrict__ t
         // No barrier here (round 5; rounds 3-4 had one: "the next first pass overwrites what the last pass has just read"):
         // the last pass READS the cells pad(tid) + 1088 r and the next first pass WRITES exactly those cells from the same
         // thread -- program order of one thread is all the hazard needs, and every other access to them lies behind the
-        // barrier that follows the first pass.  AAMD_FDR_WAR_BARRIER=1 restores it for A/B runs.
-#if AAMD_FDR_WAR_BARRIER
-        AAMD_FDR_BARRIER(4);
-#endif
+        // barrier that follows the first pass.
       }
     }
   }

@@ -42,12 +42,9 @@ namespace m400 {
 constexpr int kN = 400;
 constexpr int kPad = 200;
 constexpr int kFramesPerWave = 6;
-#ifndef AAMD_M400_WAVES
-#define AAMD_M400_WAVES 12
-#define AAMD_M400_MINWAVES 3
-#endif
-constexpr int kWavesPerBlock = AAMD_M400_WAVES;              // 768 threads = 3 waves per SIMD: ONE block per CU (a second block of a
+constexpr int kWavesPerBlock = 12;             // 768 threads = 3 waves per SIMD: ONE block per CU (a second block of a
                                                // smaller size is not admitted: its waves land on the same SIMDs)
+constexpr int kMinWavesPerSimd = 3;            // (the launch bounds' second argument)
 // LDS strides picked with tools/lds_conflicts.py (bank model of MI355X_MICROARCH.md):
 // Transposition buffer, round-2 layout: one ROW per transposed value and one COLUMN per writer lane.
 //   row (s, re) at dword kTOff[s], row (s, im) at kTOff[s] + 64; element of writer lane l at row + l.
@@ -892,9 +889,6 @@ AAMD_HD void store_spec(int lane, const float* lds, float* out, int64_t a0, int 
 // and their two lanes finish with single floats out of the registers they already hold.  (The loop above reads, waits and
 // stores piece by piece and walks four guarded single-float blocks, each with an LDS read of its own, in its first and last
 // iteration.)
-#ifndef AAMD_M400_SPEC_FULL
-#define AAMD_M400_SPEC_FULL 1
-#endif
 AAMD_HD void store_spec_full(int lane, const float* lds, float* out, int64_t a0) {
   constexpr int kN = kFramesPerWave * kSpecBins;          // 1206
   const int phase = (int)(a0 & 3);
@@ -1252,9 +1246,6 @@ __device__ __forceinline__ void glds16(const void* gsrc, unsigned lds_dst) {
 }
 
 // the same with the source as wave-uniform base (SGPR pair) + 32-bit lane offset in bytes: no per-lane 64-bit address
-#ifndef AAMD_M400_DMA_SADDR
-#define AAMD_M400_DMA_SADDR 1
-#endif
 __device__ __forceinline__ void glds16s(const void* sbase, unsigned voff_bytes, unsigned lds_dst) {
   asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" : : "v"(voff_bytes), "s"(sbase), "s"(lds_dst) : "memory", "m0");
 }
@@ -1289,7 +1280,7 @@ __device__ __forceinline__ void atomic_max_f32(float* addr, float v) {
 // the band table then live in registers, MelRegs) or kMelMaxRounds (up to 160 mels, control words re-read from LDS).
 // AR = arithmetic of the tile loop (AR_* above): AR_LEGACY for every instantiation but the 80-mel HTK one of the headline config.
 template <int LAB, int EPI, int H = 8, typename TIn = float, int NR = kMelMaxRounds, int SIG = 0, int AR = AR_LEGACY>
-__global__ void __launch_bounds__(64 * kWavesPerBlock, AAMD_M400_MINWAVES)
+__global__ void __launch_bounds__(64 * kWavesPerBlock, kMinWavesPerSimd)
 melspec400_kernel(const TIn* __restrict__ wav, const float* __restrict__ window,
                   const float* __restrict__ tw400, MelBandsDev mb, float* __restrict__ out,
                   int64_t rows, int64_t length, int64_t row_stride, int n_frames, float scale,
@@ -1351,14 +1342,6 @@ melspec400_kernel(const TIn* __restrict__ wav, const float* __restrict__ window,
   const int elab = (LAB & 524288) ? epi.lab : 0;
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-#ifdef AAMD_M400_PRIO
-  // lab (tools/mel400_lab.py): a static issue priority per wave; the waves w, w + 4, w + 8 of a SIMD get distinct ones
-  {
-    const int pr = AAMD_M400_PRIO == 1 ? (wave >> 2) : AAMD_M400_PRIO == 2 ? 2 - (wave >> 2) : (wave >> 2) == 0 ? 1 : 0;
-    if (pr == 1) __builtin_amdgcn_s_setprio(1);
-    else if (pr == 2) __builtin_amdgcn_s_setprio(2);
-  }
-#endif
   long long lab_t0 = 0;
   if (LAB & 1024) lab_t0 = wall_clock64();
   if ((LAB & 1048576) && lane == 0) {  // lab: ... and at its entry (shader clock of the launch = cycles / wall time)
@@ -1430,35 +1413,24 @@ melspec400_kernel(const TIn* __restrict__ wav, const float* __restrict__ window,
 #pragma unroll
     for (int q = 0; q < 20; ++q) winr[q] = c.win[q];
   }
-#ifndef AAMD_M400_TWREG
-#define AAMD_M400_TWREG 3
-#endif
-#ifndef AAMD_M400_TWREG_PIN
-#define AAMD_M400_TWREG_PIN 4
-#endif
   // Twiddle batches (of five columns) held in registers instead of re-read from the LDS table every tile: all four under lab
   // bit 14 (spills).  The signature instantiation runs at 136 registers, so three batches fit its 168 (164; - 3.0 % on the
   // headline batch, 67.3 -> 65.3 us, profiles/r03_i_mel400_lab_twiddle_regs.txt): 15 of the 20 ds_read_b64 per tile gone.
   // (Since the row stores take a scalar base the signature instantiation runs at 150 registers and a fourth batch fits, 159; it is
   // 0.6 us faster but NOT bit-identical -- the compiler contracts that batch's complex multiplies into other fma pairs, 9e-8 of the
   // peak -- so the unpinned source stays at three: profiles/r07_b_mel400_lab_trim_ab.txt.  With the roundings pinned in the source
-  // (AR_PIN) where the twiddles live no longer matters: AAMD_M400_TWREG_PIN = 4.)
+  // (AR_PIN) where the twiddles live no longer matters: kTwRegPin = 4.)
   // The other float-input hop-160 instantiations get what their register count leaves (tests/test_no_spills.py keeps every
   // one of them out of scratch): Spectrogram 144 -> 2 batches, generic mel 149 / 135 (NR 4 / 8) -> 1 / 3, mel + dB 154 -> 1.
-#ifndef AAMD_M400_TWREG_DB
-#define AAMD_M400_TWREG_DB 1
-#endif
-#ifndef AAMD_M400_TWREG_MFCC
-#define AAMD_M400_TWREG_MFCC 2
-#endif
+  constexpr int kTwReg = 3, kTwRegPin = 4, kTwRegDb = 1, kTwRegMfcc = 2;
   constexpr bool kPlain = H == 8 && std::is_same<TIn, float>::value && LAB == 0;
   constexpr int kTwRegBatches = (LAB & 16384) ? 4
-                                : (SIG != 0 && EPI == EPI400_MEL) ? ((AR & AR_PIN) ? AAMD_M400_TWREG_PIN : AAMD_M400_TWREG)
+                                : (SIG != 0 && EPI == EPI400_MEL) ? ((AR & AR_PIN) ? kTwRegPin : kTwReg)
                                 : !kPlain ? 0
                                 : EPI == EPI400_SPEC ? 2
                                 : (EPI == EPI400_MEL && SIG == 0) ? (NR <= 4 ? 1 : 3)
-                                : (EPI == EPI400_MFCC && NR <= 4) ? AAMD_M400_TWREG_MFCC
-                                : (EPI == EPI400_MEL_DB && NR <= 4) ? AAMD_M400_TWREG_DB : 0;
+                                : (EPI == EPI400_MFCC && NR <= 4) ? kTwRegMfcc
+                                : (EPI == EPI400_MEL_DB && NR <= 4) ? kTwRegDb : 0;
   if (kTwRegBatches > 0) {
 #pragma unroll
     for (int q = 0; q < 10 * kTwRegBatches; ++q) twr[q] = c.tw[q];
@@ -1644,13 +1616,8 @@ melspec400_kernel(const TIn* __restrict__ wav, const float* __restrict__ window,
     if (LAB & 32) src = wav + 6 * kHop;                 // lab: always the same (cache-resident) tile
 #pragma unroll
     for (int k = 0; k < SG::ndma; ++k)
-      if (!(LAB & 64) || k == 0) {                      // lab bit 6: one piece only
-#if AAMD_M400_DMA_SADDR
+      if (!(LAB & 64) || k == 0)                        // lab bit 6: one piece only
         glds16s(src, (unsigned)spiece[k] * (unsigned)sizeof(TIn), s_addr + 1024 * k);
-#else
-        glds16(src + spiece[k], s_addr + 1024 * k);
-#endif
-      }
   };
 
   // MEL_DB: running maximum of this wave's dB values, flushed whenever the cut-off group changes
@@ -1844,7 +1811,7 @@ melspec400_kernel(const TIn* __restrict__ wav, const float* __restrict__ window,
         phase_b2_spec(c, zr, zi, qr, qi, epi.power, (int)(a0 & 3), lds);
         wave_lds_fence();
         if (!(LAB & 2)) {
-          if (AAMD_M400_SPEC_FULL && n_valid == kFramesPerWave) store_spec_full(lane, lds, out, a0);
+          if (n_valid == kFramesPerWave) store_spec_full(lane, lds, out, a0);
           else store_spec(lane, lds, out, a0, n_valid * kSpecBins);
         }
         wave_lds_fence();

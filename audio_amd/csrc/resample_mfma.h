@@ -427,19 +427,10 @@ resample_f16_kernel(Geom g, const float* __restrict__ wav, const float* __restri
   using u32x4 = __attribute__((ext_vector_type(4))) uint32_t;
   constexpr int NS = KS / 8;                       // MFMA steps: 8 taps per lane group and step
   extern __shared__ __attribute__((aligned(16))) float smem_rsm[];
-#ifndef AAMD_RSM_FLAGS
-#define AAMD_RSM_FLAGS 0
-#endif
-  // AAMD_RSM_FLAGS = 1 (round 6): no workgroup barrier in the chunk loop.  The two LDS buffers are handed over by counters -- `fullc[b]`:
-  // loader waves that have written their packed pieces of a chunk into buffer b; `donec[b]`: compute waves that have finished reading
-  // it -- so a wave that is done with chunk k goes on to chunk k + 1 as soon as the loaders have it, instead of idling at the barrier
-  // until the slowest wave of the workgroup arrives (the oldest wave of a SIMD finishes its matrix loop 2 us before the youngest of a
-  // 5.3 us period, profiles/r06_zi).  Every wave of the workgroup is resident: the waits are bounded.  Four maximum slots instead of
-  // three; a slot is zeroed by the first loader wave one chunk before its next use (see publish).
-  constexpr int kSlots = AAMD_RSM_FLAGS ? 4 : 3;
-#if AAMD_RSM_FLAGS && defined(AAMD_RSM_SHARED_CONV)
-#error "the flag hand-over needs the loader-side conversion (the batch counters of AAMD_RSM_SHARED_CONV share its LDS words)"
-#endif
+  // The two LDS buffers change hands at ONE workgroup barrier per chunk.  (Round 6 also built a hand-over by LDS counters, so that
+  // a wave done with chunk k goes on as soon as the loaders have chunk k + 1 -- the oldest wave of a SIMD finishes its matrix loop
+  // 2 us before the youngest of a 5.3 us period, profiles/r06_zi: bit-identical, it measured 0.7 %, profiles/r06_zs_rsm_lab_flag_handover.txt, and was removed.)
+  constexpr int kSlots = 3;
   unsigned* mx = reinterpret_cast<unsigned*>(smem_rsm + 2 * g.buf_floats);     // [kSlots]: largest |sample| bits, chunk k -> slot k % kSlots
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -456,7 +447,7 @@ resample_f16_kernel(Geom g, const float* __restrict__ wav, const float* __restri
   const int64_t first = (int64_t)blockIdx.x * g.chunks_per_block;
   int64_t end = first + g.chunks_per_block;
   if (end > g.n_chunks) end = g.n_chunks;
-  if (threadIdx.x < 12) mx[threadIdx.x] = 0u;         // maxima + arrival counters + (3 batch counters | 2 + 2 hand-over counters): 48 bytes
+  if (threadIdx.x < 12) mx[threadIdx.x] = 0u;         // maxima + arrival counters + six words nothing reads (`spare` below): the launcher's 48 bytes
   __syncthreads();
 
   // Timeline (one barrier per chunk; round 6):
@@ -466,57 +457,18 @@ resample_f16_kernel(Geom g, const float* __restrict__ wav, const float* __restri
   // (two chunks in LDS + one in the loaders' registers = the HBM latency of a 60 KB burst per CU is off the critical path);
   // stage = wait for the data, publish the wave's largest |sample| (max3 chain + DPP reduction + one LDS atomic max), count the
   // wave in, wait for the other loader wave(s), then split the pieces IN THE REGISTERS with the chunk's scale and write the
-  // packed (lo << 16 | hi) dwords to the free buffer.  (Rounds 2-5, kept as -DAAMD_RSM_SHARED_CONV for A/Bs: the loaders staged
-  // the raw floats and every wave that found itself free converted batches of them in place -- `convert` below; with the
-  // 6-operation split and the staged path of round 2 the two loader waves were the critical path, profiles/r02_v.  With the
-  // 4-operation split, buffer loads and immediate offsets a loader wave's chunk is ~650 instructions, profiles/r06_zi.)
+  // packed (lo << 16 | hi) dwords to the free buffer.  (Rounds 2-5: the loaders staged the raw floats and every wave that found
+  // itself free converted batches of them in place; with the 6-operation split and the staged path of round 2 the two loader
+  // waves were the critical path, profiles/r02_v.  With the 4-operation split, buffer loads and immediate offsets a loader
+  // wave's chunk is ~650 instructions, profiles/r06_zi.)
   unsigned* cnt = mx + kSlots;                         // [kSlots]: loader waves whose maximum is in LDS, monotonic
-  unsigned* fullc = mx + 8;                            // [2] (AAMD_RSM_FLAGS): loader waves that have filled buffer b, monotonic
-  unsigned* donec = mx + 10;                           // [2] (AAMD_RSM_FLAGS): compute waves that have consumed buffer b, monotonic
-  (void)fullc; (void)donec;
-  auto pack4 = [](const F4& t, float scale) {
+  // [3] behind cnt, written and never read: the batch counters of the rounds 2-5 conversion.  Their reset at the end of a chunk is
+  // kept with them, because taking a store out changes the kernel's code object; both go with the next change that may.
+  unsigned* spare = cnt + 3;
+  auto pack4 = [](const F4& t, float scale) {          // the truncating split (4 operations a sample; the taps take the round-to-nearest one)
     u32x4 o;
-#if defined(AAMD_RSM_RNE_SAMPLES)    /* lab: the round-to-nearest split of the samples (6 operations each; the taps always use it) */
-    o.x = pack_hl(t.x * scale); o.y = pack_hl(t.y * scale); o.z = pack_hl(t.z * scale); o.w = pack_hl(t.w * scale);
-#else
     o.x = pack_hl_cut(t.x * scale); o.y = pack_hl_cut(t.y * scale); o.z = pack_hl_cut(t.z * scale); o.w = pack_hl_cut(t.w * scale);
-#endif
     return o;
-  };
-  // convert(k): raw image of chunk k -> packed dwords, in batches of kGrab x 64 pieces handed out by an LDS counter to whichever
-  // wave is free (the early finishers of the MFMA loop and the loaders behind their fetches take most of them; the last
-  // compute waves of a period find nothing left), once all loader waves have counted themselves in (slot k % 3 is used for
-  // the (k / 3 + 1)-th time; every wave of the workgroup is resident, so the wait is bounded)
-  unsigned* grab = cnt + 3;                            // [3]: batches handed out (AAMD_RSM_SHARED_CONV builds only)
-  constexpr int kGrab = 3;
-  auto convert = [&](int k) {
-    const unsigned want = (unsigned)nld * (unsigned)(k / kSlots + 1);
-    while (__atomic_load_n(&cnt[k % kSlots], __ATOMIC_RELAXED) < want) __builtin_amdgcn_s_sleep(1);
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-    if (!loader) { AAMD_RSM_STAMP(k - 1, 3) }
-    if (lab & 1) return;
-#if defined(AAMD_RSM_PRIO_CONV)
-    __builtin_amdgcn_s_setprio(AAMD_RSM_PRIO_CONV);     // lab: the conversion yields its issue slots to the MFMA loops still running
-#endif
-    float scale, inv;
-    chunk_scale(__atomic_load_n(&mx[k % kSlots], __ATOMIC_RELAXED), scale, inv);
-    float* buf = smem_rsm + (k & 1) * g.buf_floats;
-    for (;;) {
-      unsigned b = 0u;
-      if (lane == 0) b = atomicAdd(&grab[k % 3], 1u);
-      const int j0 = (int)__builtin_amdgcn_readfirstlane(b) * (64 * kGrab) + lane;
-      if (j0 - lane >= pieces) break;
-      F4 t[kGrab];
-#pragma unroll
-      for (int i = 0; i < kGrab; ++i)
-        if (j0 + 64 * i < pieces) t[i] = *reinterpret_cast<const F4*>(buf + 4 * (j0 + 64 * i));
-#pragma unroll
-      for (int i = 0; i < kGrab; ++i)
-        if (j0 + 64 * i < pieces) *reinterpret_cast<u32x4*>(buf + 4 * (j0 + 64 * i)) = pack4(t[i], scale);
-    }
-#if defined(AAMD_RSM_PRIO_CONV)
-    if (loader) __builtin_amdgcn_s_setprio(3);
-#endif
   };
   if (loader) {
     __builtin_amdgcn_s_setprio(3);                  // the producers: first pick of the issue slots of their SIMDs
@@ -543,14 +495,8 @@ resample_f16_kernel(Geom g, const float* __restrict__ wav, const float* __restri
     // modifiers per piece (rounds 2-6: four v_and_b32 + three integer maxima).  A NaN sample no longer forces the unit scale -- the
     // maximum skips it; the outputs it reaches are NaN either way
     auto absmax = [](unsigned m, const F4& t) {
-#if defined(AAMD_RSM_INT_ABSMAX)
-      const unsigned a = __float_as_uint(t.x) & 0x7fffffffu, bb = __float_as_uint(t.y) & 0x7fffffffu;
-      const unsigned cc = __float_as_uint(t.z) & 0x7fffffffu, d = __float_as_uint(t.w) & 0x7fffffffu;
-      return max(max(m, max(a, bb)), max(cc, d));
-#else
       asm("v_max3_f32 %0, |%1|, |%2|, %0\n\tv_max3_f32 %0, |%3|, |%4|, %0" : "+v"(m) : "v"(t.x), "v"(t.y), "v"(t.z), "v"(t.w));   // (one statement: hipcc pads between two)
       return m;
-#endif
     };
     // five pieces per statement (hipcc pads an s_nop between two asm statements; U = 20 / 30)
     auto absmax5 = [](unsigned m, const F4& a, const F4& b, const F4& c, const F4& d, const F4& e) {
@@ -574,10 +520,6 @@ resample_f16_kernel(Geom g, const float* __restrict__ wav, const float* __restri
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
       if (lane == 63) {
         atomicMax(&mx[k % kSlots], m);
-        // (flags: the slot of chunk k + 1 was last used by chunk k - 3, whose readers -- the compute waves' headers -- ran before
-        // their loops of chunk k - 3, and this wave has waited for the end of those loops in its stage of chunk k - 1; the other
-        // loader waves publish into it only behind this chunk's rendezvous, i.e. behind the atomicAdd below)
-        if (AAMD_RSM_FLAGS && wave == ncw) __atomic_store_n(&mx[(k + 1) % kSlots], 0u, __ATOMIC_RELAXED);
         atomicAdd(&cnt[k % kSlots], 1u);
       }
     };
@@ -605,40 +547,12 @@ resample_f16_kernel(Geom g, const float* __restrict__ wav, const float* __restri
         }                                                                                                          \
       }                                                                                                            \
     }
-#if defined(AAMD_RSM_SHARED_CONV)   /* lab: rounds 2-6 -- raw floats staged, every free wave converts them in place (convert()) */
-#define AAMD_RSM_STAGE(CID)                                                                                        \
-    {                                                                                                              \
-      const int k_ = (int)((CID) - first);                                                                         \
-      float* buf_ = smem_rsm + (k_ & 1) * g.buf_floats;                                                            \
-      unsigned m_ = 0u;                                                                                            \
-      AAMD_RSM_STAMP(k_, 0)                                                                                        \
-      if (interior) {   /* from the registers; a lane past the end holds a copy of the last piece and rewrites it */ \
-        int lt_ = lt;                                                                                              \
-        asm volatile("" : "+v"(lt_));   /* as in FETCH: nothing of this hoisted out of the chunk loop */            \
-        F4* dst_ = reinterpret_cast<F4*>(buf_);                                                                    \
-        _Pragma("unroll") for (int u = 0; u < U; ++u) {                                                            \
-          const int j = lt_ + 64 * nld * u;                                                               \
-          dst_[j < pieces ? j : pieces - 1] = v[u];                                                                \
-          m_ = absmax(m_, v[u]);                                                                                   \
-        }                                                                                                          \
-      } else if (!(lab & 8)) {   /* edge chunks, very long chunks */                                               \
-        _Pragma("unroll 4") for (int j = lt; j < pieces; j += 64 * nld) {                                 \
-          const F4 t = load_piece(g, wrow, a0, j);                                                                 \
-          *reinterpret_cast<F4*>(buf_ + 4 * j) = t;                                                                \
-          m_ = absmax(m_, t);                                                                                      \
-        }                                                                                                          \
-      }                                                                                                            \
-      AAMD_RSM_STAMP(k_, 1)                                                                                        \
-      publish(k_, m_);                                                                                             \
-      AAMD_RSM_STAMP(k_, 2)                                                                                        \
-    }
-#else
-    // Round 6: the loader waves convert THEIR pieces from the registers the fetch left them in -- largest |sample| of the wave
+    // The loader waves convert THEIR pieces from the registers the fetch left them in -- largest |sample| of the wave
     // (DPP) -> LDS atomic max + arrival count -> wait for the other loader wave(s) -> the chunk's power-of-two scale -> split
-    // and pack in the registers -> ONE 16-byte LDS write per piece.  (Rounds 2-6 staged the raw floats, and every wave of the
+    // and pack in the registers -> ONE 16-byte LDS write per piece.  (Rounds 2-5 staged the raw floats, and every wave of the
     // workgroup that found itself free converted batches of them in place: a write, a read and a write per piece, a batch
-    // counter, and the compute waves' matrix loops could not start before the last batch.)  Same maximum, same scale, same
-    // arithmetic per sample: bit-identical results.  Edge chunks (zero padding by index) and chunks longer than the loaders'
+    // counter, and the compute waves' matrix loops could not start before the last batch; same maximum, same scale, same
+    // arithmetic per sample, bit-identical results -- removed.)  Edge chunks (zero padding by index) and chunks longer than the loaders'
     // registers go through LDS: raw pieces written, then -- behind the same rendezvous -- converted in place by the lane that
     // wrote them (the LDS executes one wave's accesses in order).
 #define AAMD_RSM_STAGE(CID)                                                                                        \
@@ -666,11 +580,6 @@ resample_f16_kernel(Geom g, const float* __restrict__ wav, const float* __restri
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");                                                     \
       }                                                                                                            \
       AAMD_RSM_STAMP(k_, 2)                                                                                        \
-      if (AAMD_RSM_FLAGS) {   /* the buffer's previous chunk (k - 2) consumed by every compute wave */              \
-        const unsigned wd_ = (unsigned)ncw * (unsigned)(k_ / 2);                                                   \
-        while (__atomic_load_n(&donec[k_ & 1], __ATOMIC_RELAXED) < wd_) __builtin_amdgcn_s_sleep(1);               \
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");                                                     \
-      }                                                                                                            \
       if (!(lab & 1)) {                                                                                            \
         float scale_, inv_;                                                                                        \
         chunk_scale(__atomic_load_n(&mx[k_ % kSlots], __ATOMIC_RELAXED), scale_, inv_);                                 \
@@ -694,30 +603,19 @@ resample_f16_kernel(Geom g, const float* __restrict__ wav, const float* __restri
           }                                                                                                        \
         }                                                                                                          \
       }                                                                                                            \
-      if (AAMD_RSM_FLAGS) {   /* behind the wave's own LDS writes (the LDS executes a wave's accesses in order) */   \
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");                                                     \
-        if (lane == 63) atomicAdd(&fullc[k_ & 1], 1u);                                                             \
-      }                                                                                                            \
     }
-#endif
     if (first < end) {
       AAMD_RSM_FETCH(first)
       AAMD_RSM_STAGE(first)
     }
     if (first + 1 < end) AAMD_RSM_FETCH(first + 1)
-#if defined(AAMD_RSM_SHARED_CONV)
-    if (first < end) convert(0);
-#endif
-    if (!AAMD_RSM_FLAGS) __syncthreads();                // A0
+    __syncthreads();                                     // A0
     for (int64_t cid = first; cid < end; ++cid) {
       if (cid + 1 < end) AAMD_RSM_STAGE(cid + 1)          // fetched a whole chunk period ago; its buffer is free since A(cid - 1)
       AAMD_RSM_STAMP((int)(cid + 1 - first), 3)
       if (cid + 2 < end) AAMD_RSM_FETCH(cid + 2)          // stays in registers until the next round
-#if defined(AAMD_RSM_SHARED_CONV)
-      if (cid + 1 < end) convert((int)(cid + 1 - first));
-#endif
       AAMD_RSM_STAMP((int)(cid + 1 - first), 4)
-      if (!AAMD_RSM_FLAGS) __syncthreads();              // A(cid)
+      __syncthreads();                                   // A(cid)
       AAMD_RSM_STAMP((int)(cid + 1 - first), 5)
     }
 #undef AAMD_RSM_FETCH
@@ -739,15 +637,13 @@ resample_f16_kernel(Geom g, const float* __restrict__ wav, const float* __restri
     }
   } else if constexpr (RD == 1) {
     // odd lane groups hold the steps rotated (b64_step): one per-lane tap offset, the wrap a compile-time choice per step.
-    // The per-lane base goes through an opaque move every AAMD_RSM_PRO_BATCH steps: left alone, the 224 tap indices are all
+    // The per-lane base goes through an opaque move every kProBatch steps: left alone, the 224 tap indices are all
     // formed up front, and with the 8-byte loop's registers on top the fragment loads were spilled one by one behind vmcnt(0)
-#ifndef AAMD_RSM_PRO_BATCH
-#define AAMD_RSM_PRO_BATCH 2
-#endif
+    constexpr int kProBatch = 2;
     int tap_base = tap_lo + KS * (lane >> 4);
 #pragma unroll
     for (int s_ = 0; s_ < NS; ++s_) {
-      if (s_ % AAMD_RSM_PRO_BATCH == 0) asm volatile("" : "+v"(tap_base));
+      if (s_ % kProBatch == 0) asm volatile("" : "+v"(tap_base));
       if (b64_jump(KS, s_) != 0) tap_base += ((lane >> 4) & 1) * b64_jump(KS, s_);
 #pragma unroll
       for (int d = 0; d < 4; ++d) {
@@ -755,8 +651,8 @@ resample_f16_kernel(Geom g, const float* __restrict__ wav, const float* __restri
         ah[i] = 0x3c003c00u; al[i] = 0x1c001c00u + i;
         if (!(lab & 16)) a_pack16_at(g, kern, pt, tap_base + 8 * s_ + 2 * d, lane, ah[i], al[i]);
       }
-      // the packed fragments of the step exist HERE: the split arithmetic was otherwise sunk behind convert(0)'s wait loop and
-      // the barrier, with all 224 raw taps alive across both
+      // the packed fragments of the step exist HERE: the split arithmetic was otherwise sunk behind the barrier, with all 224 raw
+      // taps alive across it
       asm volatile("" : "+v"(ah[4 * s_]), "+v"(ah[4 * s_ + 1]), "+v"(ah[4 * s_ + 2]), "+v"(ah[4 * s_ + 3]),
                         "+v"(al[4 * s_]), "+v"(al[4 * s_ + 1]), "+v"(al[4 * s_ + 2]), "+v"(al[4 * s_ + 3]));
     }
@@ -767,10 +663,7 @@ resample_f16_kernel(Geom g, const float* __restrict__ wav, const float* __restri
       if (!(lab & 16)) a_pack16(g, kern, pt, tap_lo, KS, i >> 2, i & 3, lane, ah[i], al[i]);
     }
   }
-#if defined(AAMD_RSM_SHARED_CONV)
-  if (first < end) convert(0);
-#endif
-  if (!AAMD_RSM_FLAGS) __syncthreads();                  // A0
+  __syncthreads();                                       // A0
   // The scalars of a chunk -- its row, first output group, 16-byte phase, output row, and the scale that undoes the chunk's
   // power-of-two (from the loaders' maximum) -- are ~75 dependent scalar instructions and an LDS round trip.  Round 6: they are
   // worked out for chunk k + 1 IN FRONT of barrier A(k), where eleven of the twelve waves wait anyway; behind the barrier every wave
@@ -796,24 +689,8 @@ resample_f16_kernel(Geom g, const float* __restrict__ wav, const float* __restri
   for (int64_t cid = first; cid < end; ++cid) {
     const int k = (int)(cid - first);
     AAMD_RSM_STAMP(k, 0)
-#if defined(AAMD_RSM_PRIO_LOOP)
-#if AAMD_RSM_PRIO_LOOP == 9                              /* lab: the younger wave of a SIMD first */
-    if ((wave >> 2) == 0) __builtin_amdgcn_s_setprio(1); else if ((wave >> 2) == 1) __builtin_amdgcn_s_setprio(2); else __builtin_amdgcn_s_setprio(3);
-#else
-    __builtin_amdgcn_s_setprio(AAMD_RSM_PRIO_LOOP);
-#endif
-#endif
     const uint32_t* buf = reinterpret_cast<const uint32_t*>(smem_rsm + (k & 1) * g.buf_floats);
-#if defined(AAMD_RSM_HEADER_BEHIND_BARRIER)   /* lab: rounds 2-6 -- every wave works out the chunk's scalars right behind the barrier */
-    if (true) hdr = chunk_header(cid);
-#else
     if (k == 0) hdr = chunk_header(cid);
-#endif
-    if (AAMD_RSM_FLAGS) {   // the chunk is in its buffer: every loader wave has written its pieces
-      const unsigned wf = (unsigned)nld * (unsigned)(k / 2 + 1);
-      while (__atomic_load_n(&fullc[k & 1], __ATOMIC_RELAXED) < wf) __builtin_amdgcn_s_sleep(1);
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-    }
     const float inv = hdr.inv;
     const int64_t qc0 = hdr.qc0;
     const int shift = hdr.shift;
@@ -866,12 +743,9 @@ resample_f16_kernel(Geom g, const float* __restrict__ wav, const float* __restri
 #ifndef AAMD_RSM_LAB_T1MASK      /* lab, timing only (wrong results): steps that issue hi x hi alone */
 #define AAMD_RSM_LAB_T1MASK 0
 #endif
-#ifndef AAMD_RSM_ONE_WAIT
-#define AAMD_RSM_ONE_WAIT 1
-#endif
       // the eight regrouping instructions of a tile in front of its three matrix instructions (the scheduler put two of them behind
       // the first MFMA and paid an s_nop for the hazard in front of the second)
-#if defined(AAMD_RSM_NO_ORDER) || defined(AAMD_RSM_LAB_NOPERM) || defined(AAMD_RSM_LAB_NOMFMA)
+#if defined(AAMD_RSM_LAB_NOPERM) || defined(AAMD_RSM_LAB_NOMFMA)
 #define AAMD_RSM_ORDER_PERM_MFMA
 #else
 #define AAMD_RSM_ORDER_PERM_MFMA if (!((AAMD_RSM_LAB_T1MASK >> s) & 1)) { __builtin_amdgcn_sched_group_barrier(0x002, 8, 0); __builtin_amdgcn_sched_group_barrier(0x008, 3, 0); }
@@ -884,59 +758,15 @@ resample_f16_kernel(Geom g, const float* __restrict__ wav, const float* __restri
       // operand tiles one after the other as in the 4-byte loop (A(s), B(s), A(s + 1), ...), the reads of the tile after the
       // next in flight: 3 x 8 registers + the carry
       uint32_t ra[2][8], rb[2][8], cf = 0u;
-#if defined(AAMD_RSM_DEEP_A)
-      uint32_t ra3[3][8];
-#define AAMD_RSM_RA_CUR ra3[s % 3]
-      AAMD_RSM_READ_A(0, ra3[0])
-#else
-#define AAMD_RSM_RA_CUR ra[cur]
       AAMD_RSM_READ_A(0, ra[0])
-#endif
       AAMD_RSM_READ_B(0, rb[0])
       __builtin_amdgcn_sched_barrier(0);
-#if defined(AAMD_RSM_B64_INTERLEAVE)
-      // lab: both tiles of a step regrouped first, their six MFMAs interleaved (no MFMA waits for its predecessor's accumulator)
-#pragma unroll
-      for (int s = 0; s < NS; ++s) {
-        const h8 ahv = __builtin_bit_cast(h8, u32x4{ah[4 * s], ah[4 * s + 1], ah[4 * s + 2], ah[4 * s + 3]});
-        const h8 alv = __builtin_bit_cast(h8, u32x4{al[4 * s], al[4 * s + 1], al[4 * s + 2], al[4 * s + 3]});
-        const uint32_t d0 = b64_run_start(KS, s) ? cf : rb[(s + 1) & 1][7];
-        u32x4 hv, lv, hw, lw;
-#pragma unroll
-        for (int d = 0; d < 4; ++d) {
-          hv[d] = __builtin_amdgcn_perm(ra[s & 1][2 * d + 1], ra[s & 1][2 * d], 0x05040100u);
-          lv[d] = __builtin_amdgcn_perm(ra[s & 1][2 * d + 1], ra[s & 1][2 * d], 0x07060302u);
-        }
-        hw[0] = __builtin_amdgcn_perm(rb[s & 1][0], d0, 0x05040100u);
-        lw[0] = __builtin_amdgcn_perm(rb[s & 1][0], d0, 0x07060302u);
-#pragma unroll
-        for (int d = 1; d < 4; ++d) {
-          hw[d] = __builtin_amdgcn_perm(rb[s & 1][2 * d], rb[s & 1][2 * d - 1], 0x05040100u);
-          lw[d] = __builtin_amdgcn_perm(rb[s & 1][2 * d], rb[s & 1][2 * d - 1], 0x07060302u);
-        }
-        __builtin_amdgcn_sched_barrier(0);
-        if (s + 1 < NS) { AAMD_RSM_READ_A(s + 1, ra[(s + 1) & 1]) AAMD_RSM_READ_B(s + 1, rb[(s + 1) & 1]) }
-        __builtin_amdgcn_sched_barrier(0);
-        accA = __builtin_amdgcn_mfma_f32_16x16x32_f16(alv, __builtin_bit_cast(h8, hv), accA, 0, 0, 0);
-        accB = __builtin_amdgcn_mfma_f32_16x16x32_f16(alv, __builtin_bit_cast(h8, hw), accB, 0, 0, 0);
-        accA = __builtin_amdgcn_mfma_f32_16x16x32_f16(ahv, __builtin_bit_cast(h8, lv), accA, 0, 0, 0);
-        accB = __builtin_amdgcn_mfma_f32_16x16x32_f16(ahv, __builtin_bit_cast(h8, lw), accB, 0, 0, 0);
-        accA = __builtin_amdgcn_mfma_f32_16x16x32_f16(ahv, __builtin_bit_cast(h8, hv), accA, 0, 0, 0);
-        accB = __builtin_amdgcn_mfma_f32_16x16x32_f16(ahv, __builtin_bit_cast(h8, hw), accB, 0, 0, 0);
-        __builtin_amdgcn_sched_barrier(0);
-      }
-#else
 #pragma unroll
       for (int s = 0; s < NS; ++s) {
         const int cur = kNoRead ? 0 : (s & 1);
         const h8 ahv = __builtin_bit_cast(h8, u32x4{ah[4 * s], ah[4 * s + 1], ah[4 * s + 2], ah[4 * s + 3]});
         const h8 alv = __builtin_bit_cast(h8, u32x4{al[4 * s], al[4 * s + 1], al[4 * s + 2], al[4 * s + 3]});
-#if defined(AAMD_RSM_DEEP_A)   /* lab: tile A's pairs requested two steps ahead (three register sets) */
-        if (s == 0 && NS > 1) AAMD_RSM_READ_A(1, ra3[1])
-        if (s + 2 < NS) AAMD_RSM_READ_A(s + 2, ra3[(s + 2) % 3])
-#else
         if (s + 1 < NS && !kNoRead) AAMD_RSM_READ_A(s + 1, ra[(s + 1) & 1])
-#endif
         if (kNoRead) {
 #pragma unroll
           for (int j = 0; j < 8; ++j) { asm volatile("" : "+v"(ra[0][j])); asm volatile("" : "+v"(rb[0][j])); }
@@ -946,19 +776,19 @@ resample_f16_kernel(Geom g, const float* __restrict__ wav, const float* __restri
         // (10), (9), (8) -- four issue slots of a loop that is bound by its issue slots: 19.5 instructions around 3 MFMAs of 4 slots
         // each, profiles/r06_zd); where the carried dword's read is among the outstanding ones the compiler's own waits stand
         // (outstanding behind tile A(s): B(s) -- with its carried dword where a run starts -- and A(s + 1))
-        if (AAMD_RSM_ONE_WAIT && s + 1 < NS) {
+        if (s + 1 < NS) {
           if (b64_run_start(KS, s)) __builtin_amdgcn_s_waitcnt(0xC07F | (9 << 8)); else __builtin_amdgcn_s_waitcnt(0xC07F | (8 << 8));
           __builtin_amdgcn_sched_barrier(0);
         }
         u32x4 hv, lv;
 #if defined(AAMD_RSM_LAB_NOPERM)   /* lab, timing only (wrong results): what the 16 v_perm_b32 per step cost */
 #pragma unroll
-        for (int d = 0; d < 4; ++d) { hv[d] = AAMD_RSM_RA_CUR[2 * d]; lv[d] = AAMD_RSM_RA_CUR[2 * d + 1]; }
+        for (int d = 0; d < 4; ++d) { hv[d] = ra[cur][2 * d]; lv[d] = ra[cur][2 * d + 1]; }
 #else
 #pragma unroll
         for (int d = 0; d < 4; ++d) {
-          hv[d] = __builtin_amdgcn_perm(AAMD_RSM_RA_CUR[2 * d + 1], AAMD_RSM_RA_CUR[2 * d], 0x05040100u);
-          lv[d] = __builtin_amdgcn_perm(AAMD_RSM_RA_CUR[2 * d + 1], AAMD_RSM_RA_CUR[2 * d], 0x07060302u);
+          hv[d] = __builtin_amdgcn_perm(ra[cur][2 * d + 1], ra[cur][2 * d], 0x05040100u);
+          lv[d] = __builtin_amdgcn_perm(ra[cur][2 * d + 1], ra[cur][2 * d], 0x07060302u);
         }
 #endif
         AAMD_RSM_MFMA3(accA, hv, lv)
@@ -968,7 +798,7 @@ resample_f16_kernel(Geom g, const float* __restrict__ wav, const float* __restri
         if (s + 1 < NS && !kNoRead) AAMD_RSM_READ_B(s + 1, rb[(s + 1) & 1])
         __builtin_amdgcn_sched_barrier(0);
         // (behind tile B(s): A(s + 1) and B(s + 1))
-        if (AAMD_RSM_ONE_WAIT && s + 1 < NS) {
+        if (s + 1 < NS) {
           if (b64_run_start(KS, s + 1)) __builtin_amdgcn_s_waitcnt(0xC07F | (9 << 8)); else __builtin_amdgcn_s_waitcnt(0xC07F | (8 << 8));
           __builtin_amdgcn_sched_barrier(0);
         }
@@ -989,9 +819,7 @@ resample_f16_kernel(Geom g, const float* __restrict__ wav, const float* __restri
         AAMD_RSM_ORDER_PERM_MFMA
         __builtin_amdgcn_sched_barrier(0);
       }
-#endif
 #undef AAMD_RSM_MFMA3
-#undef AAMD_RSM_RA_CUR
 #undef AAMD_RSM_ORDER_PERM_MFMA
 #undef AAMD_RSM_READ_A
 #undef AAMD_RSM_READ_B
@@ -1054,28 +882,14 @@ resample_f16_kernel(Geom g, const float* __restrict__ wav, const float* __restri
       store_c(g, out_row, qc0, qt1, pt, lane, acc1[0] * inv, acc1[1] * inv, acc1[2] * inv, acc1[3] * inv);
     }
     }
-    if (AAMD_RSM_FLAGS) {   // this wave's operand reads of the chunk have all returned (the matrix instructions used them)
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-      if (lane == 0) atomicAdd(&donec[k & 1], 1u);
-    }
     AAMD_RSM_STAMP(k, 1)                                 // (the MFMA loops and the stores of all rounds)
     AAMD_RSM_STAMP(k, 2)
-#if defined(AAMD_RSM_SHARED_CONV)
-#if defined(AAMD_RSM_CONV_SIMD23)                         /* lab: the waves of SIMDs 0 / 1 (three MFMA loops each) leave the conversion to the others */
-    if (cid + 1 < end && (wave & 3) >= 2) convert(k + 1);
-#else
-    if (cid + 1 < end) convert(k + 1);                   // (stamp 3 inside: both loaders have arrived)
-#endif
-#else
     AAMD_RSM_STAMP(k, 3)
-#endif
     AAMD_RSM_STAMP(k, 4)
-#if !defined(AAMD_RSM_HEADER_BEHIND_BARRIER)
     if (cid + 1 < end) hdr = chunk_header(cid + 1);
-#endif
-    if (!AAMD_RSM_FLAGS) __syncthreads();                // A(cid): chunk cid is consumed, chunk cid + 1 is in LDS
+    __syncthreads();                                     // A(cid): chunk cid is consumed, chunk cid + 1 is in LDS
     AAMD_RSM_STAMP(k, 5)
-    if (!AAMD_RSM_FLAGS && threadIdx.x == 0) { mx[k % kSlots] = 0u; grab[k % 3] = 0u; }   // read by everybody before A(cid); next written behind A(cid + 1)
+    if (threadIdx.x == 0) { mx[k % kSlots] = 0u; spare[k % 3] = 0u; }   // read by everybody before A(cid); next written behind A(cid + 1)
   }
 }
 // the prepared tap fragments of the phase tiles [g.pt0, g.pt0 + g.n_pt) of one filter: one thread per (tile, step, lane)

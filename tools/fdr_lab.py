@@ -7,7 +7,10 @@
 Every variant is tools/lab/fdr_lab.hip (= csrc/fftconv_fdr.h alone) compiled into tools/lab/_build/libfdr_NAME.so with its -D
 switches.  `run` convolves the BASELINE config-5 shard (256 rows x 480 000 samples, one 24 000-tap response) with the tap
 spectra prepared once, variants interleaved round by round, checks every variant against the first one and the first one
-against the product (F.fftconvolve), and prints the average time per launch."""
+against the product (F.fftconvolve), and prints the average time per launch.
+
+Timing-only switches of the header (wrong results): -DAAMD_FDR_LAB_NOBAR=BITS turns workgroup barriers into wave-local fences
+(1 around the length-1024 pass, 2 around the middle step, 4 first / last pass); -DAAMD_FDR_LAB_NOH reads no tap spectra."""
 import ctypes as C
 import json
 import os

@@ -8,7 +8,10 @@
 Every variant is tools/lab/mel400_lab.hip (= csrc/melspec400.h alone) compiled into tools/lab/_build/libm400_NAME.so with
 its -D switches.  `run` launches the cfg2 batch (256 x 160 000) with buffers rotating over > 256 MiB, variants interleaved
 round by round, checks every variant's output against the first one (max |diff| relative to the peak) and prints the
-average launch time per variant and round."""
+average launch time per variant and round.
+
+Switches of the header: -DAAMD_M400_PK_BAND=1, -DAAMD_M400_PK_TW=1, -DAAMD_M400_PK_POW=1 issue that phase of the headline
+instantiation as packed fp32 (tests/test_melspec400_packed.py is the bar for switching one on)."""
 import ctypes as C
 import json
 import os

@@ -1,7 +1,9 @@
 #!/usr/bin/env python
 """What the fix-up launch of the one-kernel MFCC costs on the cfg4 noise batch (no tile is flagged there): the module with
 `fused = True` as it ships (pass 0 + fix-up launch) against the same module with the second C-ABI call suppressed (tools only:
-the result is only right because nothing is flagged).  us per call, un-profiled, interleaved rounds."""
+the result is only right because nothing is flagged).  us per call, un-profiled, interleaved rounds.
+Run against a lab library built with AAMD_EXTRA_HIPCC_FLAGS=-DAAMD_MFCC_FIXUP_RETURNS=1 (AAMD_USE_LAB_LIB=1), whose fix-up
+kernel returns at its first instruction, the difference is the bare launch (profiles/r06_n_mfcc_fixup_floor.txt)."""
 import json, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch

@@ -8,7 +8,11 @@ Every variant is tools/lab/rsm_lab.hip (= csrc/resample_mfma.h alone) compiled i
 switches (-DLAB_RSM_RD=1: the 8-byte operand-read layout).  `run` resamples the BASELINE config-3 shard (128 x stereo x 30 s,
 44.1 kHz -> 16 kHz, kaiser_best) with the variants interleaved round by round on three rotating input / output buffers, checks
 every variant against the product under AAMD_POLICY_RESAMPLE_FP32 (exact-fp32 MFMA, same taps) and against the first variant,
-and prints the average time per launch."""
+and prints the average time per launch.
+
+Timing-only switches of the 8-byte loop (wrong results; profiles/r06_zd_rsm_lab_loop_decomposition.txt): -DAAMD_RSM_LAB_NOMFMA
+no matrix instructions, -DAAMD_RSM_LAB_NOPERM no regrouping, -DAAMD_RSM_LAB_NOREAD operand tiles read once per round,
+-DAAMD_RSM_LAB_T1MASK=BITS the steps that issue hi x hi alone."""
 import ctypes as C
 import json
 import os
