@@ -1277,6 +1277,26 @@ int sim_rsm_b64_conflicted_steps(int ks, int orig, int tap_lo, int shift) {
   return bad_steps;
 }
 
+// The launch geometry of the FFT convolution plans by the headers' own plan functions, for the host mirror of
+// tests/test_gpu_fuzz_fftconv.py.  sim_fdr_plan: out = {n_part, hop, skip, segs, n_blocks, seg_blocks} of fdr::plan, returns 1
+// when plan 3 serves the shape.  sim_fco_plan: out = {n_part, part_taps, v, n_blocks, n_pairs} of fco::plan followed by
+// {n_part, segs, n_blocks, seg_blocks} of fco::plan_fdl, returns 1 when the cost model picks the delay line.
+int sim_fdr_plan(int64_t rows, int64_t ny, int64_t out_len, int cu_count, int64_t* out) {
+  fdr::Geom g{};
+  const bool ok = fdr::plan(rows, ny, out_len, cu_count, g);
+  out[0] = g.n_part; out[1] = g.hop; out[2] = g.skip; out[3] = g.segs; out[4] = g.n_blocks; out[5] = g.seg_blocks;
+  return ok ? 1 : 0;
+}
+int sim_fco_plan(int64_t rows, int64_t ny, int64_t out_len, int cu_count, int64_t* out) {
+  fco::Geom g{};
+  fco::plan(ny, out_len, g);
+  out[0] = g.n_part; out[1] = g.part_taps; out[2] = g.v; out[3] = g.n_blocks; out[4] = g.n_pairs;
+  fco::FdlGeom f{};
+  const bool cheaper = fco::plan_fdl(rows, ny, out_len, cu_count, f);
+  out[5] = f.n_part; out[6] = f.segs; out[7] = f.n_blocks; out[8] = f.seg_blocks;
+  return cheaper ? 1 : 0;
+}
+
 // Replay of the overlap-save path (fco::spectrum_kernel + fco::overlap_save_kernel): the same
 // launcher logic as aamd_fftconvolve_f32, 1024 "threads" per phase, phases separated where the
 // kernel has barriers.  Twiddles as the device twiddle_kernel computes them (fp64 -> fp32).

@@ -316,6 +316,26 @@ def sim_fftconv_fdr(x, y, start, out_len, xmap=None, ymap=None, rows=None, cu_co
     return out if rc == 1 else None
 
 
+def sim_fdr_plan(rows, ny, out_len, cu_count):
+    """fdr::plan itself: (served, dict(n_part, hop, skip, segs, n_blocks, seg_blocks))."""
+    out = np.zeros(6, dtype=np.int64)
+    f = sim().sim_fdr_plan
+    f.argtypes = [C.c_int64] * 3 + [C.c_int, C.c_void_p]
+    rc = f(rows, ny, out_len, cu_count, fptr(out))
+    return bool(rc), dict(zip(("n_part", "hop", "skip", "segs", "n_blocks", "seg_blocks"), (int(v) for v in out)))
+
+
+def sim_fco_plan(rows, ny, out_len, cu_count):
+    """fco::plan and fco::plan_fdl themselves: (the cost model picks the delay line, Geom fields, FdlGeom fields)."""
+    out = np.zeros(9, dtype=np.int64)
+    f = sim().sim_fco_plan
+    f.argtypes = [C.c_int64] * 3 + [C.c_int, C.c_void_p]
+    rc = f(rows, ny, out_len, cu_count, fptr(out))
+    v = [int(a) for a in out]
+    return (bool(rc), dict(zip(("n_part", "part_taps", "v", "n_blocks", "n_pairs"), v[:5])),
+            dict(zip(("n_part", "segs", "n_blocks", "seg_blocks"), v[5:])))
+
+
 def sim_istft(spec_fm, window_padded, length, n_fft, hop, center=True, pad_mode="constant", pad=0, scale=1.0,
               adjoint=False, inv_env=None, pow2=False, runs=0, fast400=False, trace=None):
     """trace: optional dict; filled with 'stores' / 'adds' int32 arrays (rows, length): plain stores / atomic adds per sample."""
