@@ -121,6 +121,7 @@ _SIGS = {
                                            C.c_int32, C.c_int64, _P]),
     "aamd_lfilter_f32": (C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_int32, C.c_int64, C.c_int32, C.c_int32,
                                    C.c_int32, C.c_int32, _P]),
+    "aamd_lfilter_plan": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.POINTER(C.c_int32)]),
     "aamd_spectrogram_f64": (C.c_int, [_P, _P, _P, _P, C.POINTER(StftDesc), _P]),
     "aamd_istft_f64": (C.c_int, [_P, _P, _P, _P, _P, C.POINTER(StftDesc), C.c_int32, _P]),
     "aamd_lfilter_f64": (C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_int32, C.c_int64, C.c_int32, C.c_int32,

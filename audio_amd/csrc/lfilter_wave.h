@@ -908,5 +908,47 @@ lfilter_wave_mover_kernel(const float* __restrict__ x, const float* __restrict__
 }
 #endif  // __HIPCC__
 
+// ---- which kernel serves a call (host only: the launcher, aamd_lfilter_plan and the CPU replay's sim_lfw_pick share it) ----
+// W doubles while the sequences leave workgroups idle (n_seq * 2 W <= 8192) and a block of W waves is shorter than the row,
+// then halves until the one-tile layout fits the LDS.  Aligned rows with W >= 8 run 8 filter waves on two tiles: the pipelined
+// kernel for 1 - 2 stages, the mover kernel from 3 stages on.  kPickGeneral: not a biquad-class call (or nothing fits): the
+// general-order kernel of lfilter.h, which sizes its own LDS (lds = 0, W = 0 here).
+enum PickKernel {
+  kPickGeneral = 0,      // lfilter_kernel<D>
+  kPickWave8Vec = 1,     // lfilter_wave_kernel<0, 8, true>
+  kPickWave8 = 2,        // lfilter_wave_kernel<0, 8, false>
+  kPickWave16Vec = 3,    // lfilter_wave_kernel<0, 16, true>
+  kPickWave16 = 4,       // lfilter_wave_kernel<0, 16, false>
+  kPickPipe = 5,         // lfilter_wave_pipe_kernel<0>
+  kPickMover = 6         // lfilter_wave_mover_kernel<0>
+};
+struct Pick {
+  int kernel;            // PickKernel
+  int W;                 // waves per sequence (pipe / mover: the 8 filter waves)
+  int blocks;            // workgroups: min(n_seq, 8 per CU), each walks the sequences blockIdx.x, + blocks, ...
+  size_t lds;            // dynamic LDS bytes of the launch
+};
+// vec_ok: the rows of x and y are 16-byte aligned (both bases and length % 4 == 0).  force_w (a power of two <= 16) and
+// force_pipe (0: never the two-tile kernels, 1: the pipelined kernel also from 3 stages on) are the lab build's overrides;
+// 0 and -1 leave the rule alone.
+inline Pick pick(int64_t n_seq, int64_t length, int n_order, int n_stages, bool vec_ok, size_t lds_cap, int cu_count,
+                 int force_w = 0, int force_pipe = -1) {
+  int64_t nb = n_seq < (int64_t)cu_count * 8 ? n_seq : (int64_t)cu_count * 8;
+  if (nb < 1) nb = 1;
+  const int blocks = (int)nb;
+  if (!(n_order <= 3 && n_stages <= kMaxCascade && length < (1ll << 30))) return Pick{kPickGeneral, 0, blocks, 0};
+  int W = 1;
+  while (W < kMaxWaves && n_seq * (2 * W) <= 8192 && (int64_t)W * kWaveBlock < length) W *= 2;
+  if (force_w >= 1 && force_w <= kMaxWaves && (force_w & (force_w - 1)) == 0) W = force_w;
+  while (W > 1 && lds_bytes(W, n_stages) > lds_cap) W /= 2;
+  const size_t lds = lds_bytes(W, n_stages);
+  if (lds > lds_cap) return Pick{kPickGeneral, 0, blocks, 0};
+  const bool pipe = vec_ok && W >= 8 && force_pipe != 0 && pipe_lds_bytes(8, n_stages) <= lds_cap;
+  if (pipe && n_stages >= 3 && force_pipe != 1) return Pick{kPickMover, 8, blocks, pipe_lds_bytes(8, n_stages)};
+  if (pipe) return Pick{kPickPipe, 8, blocks, pipe_lds_bytes(8, n_stages)};
+  if (W <= 8) return Pick{vec_ok ? kPickWave8Vec : kPickWave8, W, blocks, lds};      // 512 threads: the 256-register instantiation
+  return Pick{vec_ok ? kPickWave16Vec : kPickWave16, W, blocks, lds};
+}
+
 }  // namespace lfw
 }  // namespace aamd

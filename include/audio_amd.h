@@ -441,6 +441,14 @@ int aamd_resample_sparse_f32(const float* wav, const float* taps_compact, const 
 int aamd_lfilter_f32(const float* x, const float* a, const float* b, float* y, int64_t batch,
                      int32_t channels, int64_t length, int32_t n_order, int32_t n_coeff_rows,
                      int32_t n_stages, int32_t clamp, void* stream);
+/* aamd_lfilter_plan reports what aamd_lfilter_f32 launches for these buffers and sizes on the current device under the current
+ * kernel policy (no launch; x and y are only looked at for their 16-byte alignment):
+ * out = {kernel, W, workgroups, dynamic LDS bytes}.  kernel: 0 the general-order kernel (csrc/lfilter.h; W and LDS 0),
+ * 1 lfw::lfilter_wave_kernel<0, 8, true>, 2 <0, 8, false>, 3 <0, 16, true>, 4 <0, 16, false>, 5 lfw::lfilter_wave_pipe_kernel,
+ * 6 lfw::lfilter_wave_mover_kernel (csrc/lfilter_wave.h, lfw::pick).  W: waves per sequence; workgroup g filters the sequences
+ * g, g + workgroups, ... */
+int aamd_lfilter_plan(const void* x, const void* y, int64_t batch, int32_t channels, int64_t length, int32_t n_order,
+                      int32_t n_stages, int32_t out[4]);
 
 /* ---- fftconvolve ------------------------------------------------------------------------ */
 

@@ -1277,6 +1277,14 @@ int sim_rsm_b64_conflicted_steps(int ks, int orig, int tap_lo, int shift) {
   return bad_steps;
 }
 
+// lfw::pick itself, for the host mirror of tests/test_gpu_fuzz_lfilter.py: out = {kernel, W, blocks, LDS bytes}.
+int sim_lfw_pick(int64_t n_seq, int64_t length, int n_order, int n_stages, int vec_ok, int64_t lds_cap, int cu_count, int force_w,
+                 int force_pipe, int64_t* out) {
+  const lfw::Pick p = lfw::pick(n_seq, length, n_order, n_stages, vec_ok != 0, (size_t)lds_cap, cu_count, force_w, force_pipe);
+  out[0] = p.kernel; out[1] = p.W; out[2] = p.blocks; out[3] = (int64_t)p.lds;
+  return 0;
+}
+
 // The launch geometry of the FFT convolution plans by the headers' own plan functions, for the host mirror of
 // tests/test_gpu_fuzz_fftconv.py.  sim_fdr_plan: out = {n_part, hop, skip, segs, n_blocks, seg_blocks} of fdr::plan, returns 1
 // when plan 3 serves the shape.  sim_fco_plan: out = {n_part, part_taps, v, n_blocks, n_pairs} of fco::plan followed by

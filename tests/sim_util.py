@@ -266,6 +266,15 @@ def sim_lfilter_wave(x, a, b, clamp=True, waves=1):
     return rc, y
 
 
+def sim_lfw_pick(n_seq, length, n_order, n_stages, vec_ok, lds_cap, cu_count, force_w=0, force_pipe=-1):
+    """lfw::pick itself (csrc/lfilter_wave.h): dict(kernel, W, blocks, lds)."""
+    out = np.zeros(4, dtype=np.int64)
+    f = sim().sim_lfw_pick
+    f.argtypes = [C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_void_p]
+    assert f(n_seq, length, n_order, n_stages, int(vec_ok), lds_cap, cu_count, force_w, force_pipe, fptr(out)) == 0
+    return dict(zip(("kernel", "W", "blocks", "lds"), (int(v) for v in out)))
+
+
 def sim_fftconv(x, y, start, out_len, xmap=None, ymap=None, rows=None):
     x = np.ascontiguousarray(x, dtype=np.float32)
     y = np.ascontiguousarray(y, dtype=np.float32)

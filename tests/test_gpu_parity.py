@@ -632,7 +632,7 @@ def test_mel400_fast_path_layout_edge_cases():
 
 def test_lfilter_wave_kernel_shape_edges():
     """Workgroup-width selection of the biquad kernel: one long sequence (16 waves), thousands of short
-    ones (1 wave each, shorter than a block), gain-only 'filter', unaligned views."""
+    ones (1 wave each, shorter than a block), gain-only 'filter', a sliced (non-contiguous) view."""
     import audio_amd.functional as F
     from oracle import dsp_oracle as O
     g = torch.Generator().manual_seed(13)
@@ -646,7 +646,9 @@ def test_lfilter_wave_kernel_shape_edges():
     x = 0.3 * torch.randn(4, 5000, generator=g)
     got = F.lfilter(x.cuda(), torch.tensor([2.0]).cuda(), torch.tensor([0.5]).cuda())          # order 0
     assert float((got.cpu() - (0.25 * x).clamp(-1, 1)).abs().max()) <= 1e-6
-    xv = (0.3 * torch.randn(4, 9001, generator=g)).cuda()[:, 1:]                                 # unaligned rows
+    # a sliced view: NOT contiguous, so F.lfilter filters a contiguous, 16-byte aligned copy of length 9000 -- the aligned pipe
+    # kernel.  (Rows whose base is off a 16-byte boundary: tests/test_gpu_fuzz_lfilter.py, regime "unaligned".)
+    xv = (0.3 * torch.randn(4, 9001, generator=g)).cuda()[:, 1:]
     got = F.lfilter(xv, a.cuda(), b.cuda(), clamp=False)
     exp = O.lfilter(xv.cpu().numpy().astype(np.float64), a.numpy(), b.numpy(), False)
     assert peak_rel_err(got.cpu().numpy(), exp) <= 1e-4
