@@ -704,3 +704,32 @@ def lfilter_sos(a: np.ndarray, b: np.ndarray, max_pole_radius: float = 0.99, rel
         if not np.isfinite(scale) or scale == 0.0 or np.abs(y - ref).sum() > rel_tol * scale:
             return None
     return a_s.astype(np.float32), b_s.astype(np.float32)
+
+
+# ---- SoX-style effects (csrc/effects.h): the reference's modulation tables, built here in float64 -------------------------------
+def effects_wave_table(wave: str, kind: str, n: int, mn: float, mx: float, phase: float) -> np.ndarray:
+    """filtering.py `_generate_wave_table`: one period of ``n`` points of a "SINE" or "TRIANGLE" between ``mn`` and ``mx``
+    starting at ``phase`` radians; kind "INT": rounded half away from zero to int32, "FLOAT": float32.  The reference evaluates
+    the sine in float64 on the data's device; this is numpy's on the host."""
+    if wave not in ("SINE", "TRIANGLE") or kind not in ("INT", "FLOAT"):
+        raise ValueError(f"unknown wave table {wave!r} / {kind!r}")
+    if n < 1:
+        raise ValueError("a modulation table needs at least one entry")
+    off = int(phase / math.pi / 2 * n + 0.5)
+    p = (np.arange(n, dtype=np.int64) + off) % n
+    if wave == "SINE":
+        d = (np.sin(p.astype(np.float64) / n * 2 * math.pi) + 1) / 2
+    else:
+        d = p.astype(np.float64) * 2 / n
+        v = (4 * p) // n
+        d = np.where(v == 0, d + 0.5, np.where((v == 1) | (v == 2), 1.5 - d, d - 1.5))
+    d = d * (mx - mn) + mn
+    if kind == "INT":
+        return np.where(d < 0, d - 0.5, d + 0.5).astype(np.int32)
+    return d.astype(np.float32)
+
+
+def flanger_channel_phase(channels: int, table_len: int, channel_phase: float) -> np.ndarray:
+    """The reference's per-channel offsets into the lfo table, ``int(c * table_len * channel_phase + 0.5)`` evaluated in
+    float32 as torch evaluates it."""
+    return ((np.arange(channels) * table_len).astype(np.float32) * np.float32(channel_phase) + np.float32(0.5)).astype(np.int64)

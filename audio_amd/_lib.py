@@ -178,6 +178,13 @@ _SIGS = {
     "aamd_forced_align_workspace": (C.c_int64, [C.c_int64] * 3),
     "aamd_forced_align": (C.c_int, [C.c_int32, _P, _P, C.c_int32, _P, _P, C.c_int32] + [C.c_int64] * 4 + [C.c_int32, _P, _P, _P,
                                     _P]),
+    # SoX-style effects (additions to ABI 7)
+    "aamd_effects_tiles": (C.c_int32, [C.c_int32]),
+    "aamd_effects_workspace": (C.c_int64, [C.c_int32, C.c_int32] + [C.c_int64] * 3),
+    "aamd_overdrive": (C.c_int, [C.c_int32, _P, _P, _P] + [C.c_int64] * 3 + [C.c_double, C.c_double, _P]),
+    "aamd_phaser": (C.c_int, [C.c_int32, _P, _P, _P] + [C.c_int64] * 3 + [_P, C.c_int64, C.c_int64] + [C.c_double] * 3 + [_P]),
+    "aamd_flanger": (C.c_int, [C.c_int32, _P, _P, _P] + [C.c_int64] * 3 + [C.c_int32, _P, C.c_int64, C.POINTER(C.c_int64),
+                               C.c_int64] + [C.c_double] * 3 + [C.c_int32, C.c_int32, _P]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS)

@@ -36,6 +36,7 @@ __all__ = [
     "add_noise", "preemphasis", "deemphasis", "convolve",
     "psd", "mvdr_weights_souden", "mvdr_weights_rtf", "rtf_power", "rtf_evd", "apply_beamforming",
     "rnnt_loss", "forced_align", "merge_tokens", "TokenSpan",
+    "overdrive", "phaser", "flanger", "effects_tiles",
 ]
 
 # --------------------------------------------------------------------------- #
@@ -3353,6 +3354,200 @@ def _rnnt_loss_eager(logits: Tensor, targets: Tensor, logit_lengths: Tensor, tar
     if reduction == "sum":
         return costs.sum()
     return costs
+
+
+# --------------------------------------------------------------------------- #
+# SoX-style effects (csrc/effects.h)                                          #
+# --------------------------------------------------------------------------- #
+PHASER_MAX_RING = 512                # AAMD_PHASER_MAX_RING: the longest delay ring (samples) the phaser kernel serves
+FLANGER_MAX_RING = 4096              # AAMD_FLANGER_MAX_RING: 40 ms at 96 kHz
+EFFECTS_MAX_TABLE = 1 << 24          # AAMD_EFFECTS_MAX_TABLE: the longest modulation table
+_FX_OVERDRIVE, _FX_PHASER, _FX_FLANGER = 0, 1, 2
+_FX_TABLES: "collections.OrderedDict" = collections.OrderedDict()   # (parameters, device) -> device table, LRU
+_FX_PINNED: dict = {}                # tables a captured graph reads: kept for the life of the process
+_FX_TABLES_MAX = 64
+
+
+def effects_tiles() -> Tuple[int, int, int]:
+    """(rows per workgroup, samples per LDS tile) of the delay-line kernel and the samples per overdrive chunk
+    (csrc/effects.h: fx::kRows, fx::kTile, fx::kOdChunk)."""
+    lib = _lib.lib()
+    return int(lib.aamd_effects_tiles(0)), int(lib.aamd_effects_tiles(1)), int(lib.aamd_effects_tiles(2))
+
+
+def _fx_table(key, device, make) -> Tensor:
+    """The modulation table of `key` on `device`: built on the host (float64) and uploaded once.  A table is never allocated
+    from a capture's pool: the first call with these parameters must run eagerly."""
+    k = key + (str(device),)
+    capturing = torch.cuda.is_current_stream_capturing()
+    with _CACHE_LOCK:
+        t = _FX_PINNED.get(k)
+        if t is None:
+            t = _FX_TABLES.get(k)
+            if t is not None:
+                _FX_TABLES.move_to_end(k)
+                if capturing:
+                    _FX_PINNED[k] = t
+    if t is not None:
+        return t
+    if capturing:
+        raise RuntimeError("audio_amd: the modulation table of these effect parameters is not on the device yet and cannot be "
+                           "built inside a graph capture; run the call once eagerly before capturing it")
+    t = torch.from_numpy(make()).to(device)
+    with _CACHE_LOCK:
+        t = _FX_TABLES.setdefault(k, t)
+        _FX_TABLES.move_to_end(k)
+        while len(_FX_TABLES) > _FX_TABLES_MAX:
+            _FX_TABLES.popitem(last=False)
+    return t
+
+
+def _fx_check_type(waveform: Tensor, what: str) -> None:
+    if not isinstance(waveform, Tensor):
+        raise TypeError(f"audio_amd: {what}: waveform must be a tensor")
+    if waveform.dtype not in _WA_FLOATS:
+        raise TypeError(f"audio_amd: {what}: waveform must be float16, bfloat16, float32 or float64 (got {waveform.dtype})")
+
+
+def _fx_check_device(waveform: Tensor, what: str) -> None:
+    """After the checks of the parameters, which need no device: the refusal of a gradient and of a CPU tensor."""
+    if waveform.requires_grad and torch.is_grad_enabled():
+        raise RuntimeError(f"audio_amd: {what} is forward-only (no gradient is implemented); wrap the call in torch.no_grad() "
+                           "or detach the waveform.")
+    _wa_require(waveform, f"{what}: waveform")
+
+
+def _fx_rows(waveform: Tensor) -> Tuple[Tensor, int, int]:
+    """(rows, T) view through one row stride (gathered where the strides do not collapse), rows, T."""
+    shape = tuple(waveform.shape)
+    x2 = _wa_rows(waveform.detach(), shape[:-1], shape[-1])
+    return x2, x2.shape[0], x2.shape[1]
+
+
+def _fx_workspace(effect: int, x2: Tensor, ring: int) -> Tensor:
+    n = int(_lib.lib().aamd_effects_workspace(effect, _SA_DTYPES[x2.dtype], x2.shape[0], x2.shape[1], ring))
+    return torch.empty(((max(n, 16) + 7) // 8,), dtype=torch.float64, device=x2.device)
+
+
+def overdrive(waveform: Tensor, gain: float = 20, colour: float = 20) -> Tensor:
+    r"""Overdrive (reference: F.overdrive, SoX's effect): ``t = x * 10 ** (gain / 20) + colour / 200`` soft-clipped to
+    ``+-2/3`` (``t - t**3 / 3`` in between), ``y[i] = t[i] - t[i-1] + 0.995 y[i-1]``, ``out = clamp(x / 2 + 0.75 y, -1, 1)``
+    along the last dim of ``(..., time)``.  The reference is a Python loop over samples; here the recurrence is a chunked scan
+    in two launches with a float64 state for every dtype, so results agree with the reference to rounding, not bit for bit.
+    Deterministic; forward-only; a plain Python entry point through the C ABI (not registered as a dispatcher op).  Can be
+    captured in a graph."""
+    _fx_check_type(waveform, "overdrive")
+    if waveform.dim() < 1:
+        raise ValueError("audio_amd: overdrive expects (..., time), got a 0-dimensional tensor")
+    _fx_check_device(waveform, "overdrive")
+    out = torch.empty(tuple(waveform.shape), dtype=waveform.dtype, device=waveform.device)
+    if out.numel() == 0:
+        return out
+    x2, rows, T_ = _fx_rows(waveform)
+    ws = _fx_workspace(_FX_OVERDRIVE, x2, 0)
+    with torch.cuda.device(waveform.device):
+        _lib.check(_lib.lib().aamd_overdrive(_SA_DTYPES[x2.dtype], x2.data_ptr(), out.data_ptr(), ws.data_ptr(), rows, T_,
+                                             _wa_stride(x2), math.exp(float(gain) * math.log(10) / 20.0), float(colour) / 200,
+                                             _lib.current_stream(waveform.device)))
+    return out
+
+
+def phaser(waveform: Tensor, sample_rate: int, gain_in: float = 0.4, gain_out: float = 0.74, delay_ms: float = 3.0,
+           decay: float = 0.4, mod_speed: float = 0.5, sinusoidal: bool = True) -> Tensor:
+    r"""Phaser (reference: F.phaser, SoX's effect) along the last dim of ``(..., time)``: a delay line of
+    ``L = int(delay_ms * sample_rate / 1000 + 0.5)`` samples whose feedback tap is swept by a sine or triangle table of
+    ``int(sample_rate / mod_speed + 0.5)`` entries; the result is clamped to ``[-1, 1]``.  Equal to the reference's
+    per-sample loop bit for bit in float32 and float64 (float16 / bfloat16 compute in float32 and round once), one launch in
+    place of several per sample.  The table is built on the host in float64 and cached per (parameters, device): the first call
+    with new parameters cannot run inside a graph capture.  ``L`` up to 512, tables up to 2^24 entries
+    (``NotImplementedError`` beyond); ``L < 1`` or an empty table raise ``ValueError``.  Forward-only; a plain Python entry
+    point through the C ABI (not registered as a dispatcher op)."""
+    _fx_check_type(waveform, "phaser")
+    if waveform.dim() < 1:
+        raise ValueError("audio_amd: phaser expects (..., time), got a 0-dimensional tensor")
+    L = int(delay_ms * 0.001 * sample_rate + 0.5)
+    M = int(sample_rate / mod_speed + 0.5)
+    if L < 1:
+        raise ValueError(f"audio_amd: phaser: delay_ms * sample_rate / 1000 rounds to a delay of {L} samples; at least 1 is needed")
+    if M < 1:
+        raise ValueError(f"audio_amd: phaser: sample_rate / mod_speed rounds to a modulation table of {M} entries; at least 1 is needed")
+    if L > PHASER_MAX_RING:
+        raise NotImplementedError(f"audio_amd: phaser serves delays up to {PHASER_MAX_RING} samples (got {L})")
+    if M > EFFECTS_MAX_TABLE:
+        raise NotImplementedError(f"audio_amd: phaser serves modulation tables up to 2^24 = {EFFECTS_MAX_TABLE} entries (got {M})")
+    _fx_check_device(waveform, "phaser")
+    out = torch.empty(tuple(waveform.shape), dtype=waveform.dtype, device=waveform.device)
+    if out.numel() == 0:
+        return out
+    table = _fx_table(("phaser", L, M, bool(sinusoidal)), waveform.device,
+                      lambda: _host.effects_wave_table("SINE" if sinusoidal else "TRIANGLE", "INT", M, 1.0, float(L), math.pi / 2))
+    x2, rows, T_ = _fx_rows(waveform)
+    ws = _fx_workspace(_FX_PHASER, x2, L)
+    with torch.cuda.device(waveform.device):
+        _lib.check(_lib.lib().aamd_phaser(_SA_DTYPES[x2.dtype], x2.data_ptr(), out.data_ptr(), ws.data_ptr(), rows, T_,
+                                          _wa_stride(x2), table.data_ptr(), M, L, float(gain_in), float(gain_out), float(decay),
+                                          _lib.current_stream(waveform.device)))
+    return out
+
+
+def flanger(waveform: Tensor, sample_rate: int, delay: float = 0.0, depth: float = 2.0, regen: float = 0.0,
+            width: float = 71.0, speed: float = 0.5, phase: float = 25.0, modulation: str = "sinusoidal",
+            interpolation: str = "linear", *, _general: bool = False) -> Tensor:
+    r"""Flanger (reference: F.flanger, SoX's effect) on ``(..., channel, time)`` with at most 4 channels: a delay line of
+    ``L = int((delay + depth) / 1000 * sample_rate + 0.5) + 2`` samples read at a delay swept by a table of
+    ``int(sample_rate / speed)`` entries (each channel ``phase`` percent of a period further on), linear or quadratic
+    interpolation, ``regen`` percent fed back; the result is clamped to ``[-1, 1]``.  Equal to the reference's per-sample loop
+    bit for bit in float32 and float64 (float16 / bfloat16 compute in float32 and round once).  ``regen == 0`` has no
+    recurrence and runs as a streaming gather: there a non-finite sample reaches only the outputs whose taps read it (the
+    reference's ``last * 0`` keeps a NaN alive for the rest of the row) and a stored ``-0.0`` is read as stored.  The table
+    is built on the host in float64 and cached per (parameters, device): the first call with new parameters cannot run inside
+    a graph capture.  ``L`` up to 4096, tables up to 2^24 entries (``NotImplementedError`` beyond).  Forward-only; a plain
+    Python entry point through the C ABI (not registered as a dispatcher op)."""
+    if modulation not in ("sinusoidal", "triangular"):
+        raise ValueError('Only "sinusoidal" or "triangular" modulation allowed')
+    if interpolation not in ("linear", "quadratic"):
+        raise ValueError('Only "linear" or "quadratic" interpolation allowed')
+    _fx_check_type(waveform, "flanger")
+    if waveform.dim() < 2:
+        raise ValueError(f"audio_amd: flanger expects (..., channel, time), got {tuple(waveform.shape)}")
+    channels = waveform.shape[-2]
+    if channels > 4:
+        raise ValueError("Max 4 channels allowed")
+    feedback_gain = regen / 100
+    delay_gain = width / 100
+    channel_phase = phase / 100
+    in_gain = 1.0 / (1 + delay_gain)
+    delay_gain = delay_gain / (1 + delay_gain)
+    delay_gain = delay_gain * (1 - abs(feedback_gain))
+    delay_min = delay / 1000
+    L = int((delay_min + depth / 1000) * sample_rate + 0.5) + 2
+    N = int(sample_rate / speed)
+    if N < 1:
+        raise ValueError(f"audio_amd: flanger: sample_rate / speed gives a modulation table of {N} entries; at least 1 is needed")
+    if L < 2:
+        raise ValueError(f"audio_amd: flanger: delay and depth give a delay line of {L} samples; they must not be negative")
+    if L > FLANGER_MAX_RING:
+        raise NotImplementedError(f"audio_amd: flanger serves delay lines up to {FLANGER_MAX_RING} samples (got {L})")
+    if N > EFFECTS_MAX_TABLE:
+        raise NotImplementedError(f"audio_amd: flanger serves modulation tables up to 2^24 = {EFFECTS_MAX_TABLE} entries (got {N})")
+    _fx_check_device(waveform, "flanger")
+    out = torch.empty(tuple(waveform.shape), dtype=waveform.dtype, device=waveform.device)
+    if out.numel() == 0:
+        return out
+    table_min = float(math.floor(delay_min * sample_rate + 0.5))
+    table = _fx_table(("flanger", N, table_min, L, modulation), waveform.device,
+                      lambda: _host.effects_wave_table("SINE" if modulation == "sinusoidal" else "TRIANGLE", "FLOAT", N,
+                                                       table_min, float(L) - 2.0, 3 * math.pi / 2))
+    cph = (C.c_int64 * 4)(*[int(v) % N for v in _host.flanger_channel_phase(channels, N, channel_phase)])
+    x2, rows, T_ = _fx_rows(waveform)
+    general = bool(_general) or feedback_gain != 0.0
+    ws = _fx_workspace(_FX_FLANGER, x2, L if general else 0)
+    with torch.cuda.device(waveform.device):
+        _lib.check(_lib.lib().aamd_flanger(_SA_DTYPES[x2.dtype], x2.data_ptr(), out.data_ptr(), ws.data_ptr(), rows, T_,
+                                           _wa_stride(x2), channels, table.data_ptr(), N, cph, L, float(feedback_gain),
+                                           float(in_gain), float(delay_gain), int(interpolation == "quadratic"), int(general),
+                                           _lib.current_stream(waveform.device)))
+    return out
 
 
 # --------------------------------------------------------------------------- #

@@ -57,6 +57,9 @@
  *   aamd_rnnt_loss_backward   one read of the logits forward, one read and one write backward -- additions to ABI 7 as well
  *   aamd_forced_align         F.forced_align (the reference's libtorchaudio/forced_align: one launch per frame and a host
  *                             backtrack there; two launches here) -- an addition to ABI 7 as well
+ *   aamd_overdrive            F.overdrive / F.phaser / F.flanger (the reference's Python loops over samples: a chunked
+ *   aamd_phaser               float64 scan in two launches; one launch with the delay ring in LDS, bit for bit; a streaming
+ *   aamd_flanger              gather where nothing is fed back) -- additions to ABI 7 as well
  *   aamd_detect_pitch_f32     F.detect_pitch_frequency (_compute_nccf + _find_max_per_frame + _median_smoothing in the
  *                             reference; an addition to ABI 7 as well)
  *
@@ -731,6 +734,46 @@ int aamd_forced_align(int32_t dtype, const void* log_probs, const void* targets,
                       const void* input_lengths, const void* target_lengths, int32_t lengths_int64, int64_t batch,
                       int64_t max_t, int64_t classes, int64_t max_l, int32_t blank, void* workspace, void* paths, void* scores,
                       void* stream);
+
+/* ---- SoX-style effects (additions to ABI 7; csrc/effects.h) ----------------------------------------------------------- */
+
+enum { AAMD_FX_OVERDRIVE = 0, AAMD_FX_PHASER = 1, AAMD_FX_FLANGER = 2 };
+#define AAMD_PHASER_MAX_RING 512      /* the longest delay ring (samples) the phaser kernel serves */
+#define AAMD_FLANGER_MAX_RING 4096    /* ... and the flanger kernels: 40 ms at 96 kHz */
+#define AAMD_EFFECTS_MAX_TABLE (1 << 24) /* the longest modulation table */
+
+/* which = 0: rows per workgroup of the delay-line kernel; 1: samples per LDS tile; 2: samples per overdrive chunk. */
+int32_t aamd_effects_tiles(int32_t which);
+
+/* Bytes of device workspace a call needs (written and read on the device only).  AAMD_FX_OVERDRIVE: one double per (row,
+ * chunk); `ring` is ignored.  AAMD_FX_PHASER / AAMD_FX_FLANGER: 0 where the delay ring of `ring` samples per row fits the
+ * LDS for `dtype` (AAMD_SA_*), else one ring per row of every workgroup (16-byte aligned). */
+int64_t aamd_effects_workspace(int32_t effect, int32_t dtype, int64_t rows, int64_t length, int64_t ring);
+
+/* Every effect: x is (rows, length) of `dtype` (AAMD_SA_*) with unit stride along time and row_stride elements between
+ * rows, out is dense (rows, length) of the same type; float16 / bfloat16 compute in float32 and are rounded once.  Results
+ * are clamped to [-1, 1]; a NaN stays a NaN.
+ *
+ * F.overdrive: gain = 10 ^ (dB / 20) and colour = colour / 200 are rounded to the compute type; the recurrence state is
+ * float64 for every type.  Two launches (one for rows of one chunk), no atomics: two calls give the same bits. */
+int aamd_overdrive(int32_t dtype, const void* x, void* out, void* workspace, int64_t rows, int64_t length,
+                   int64_t row_stride, double gain, double colour, void* stream);
+
+/* F.phaser: table is int32[table_len] on the device with entries in [1, ring] (the reference's modulation buffer); the
+ * result equals the reference's loop bit for bit.  ring > AAMD_PHASER_MAX_RING or table_len > AAMD_EFFECTS_MAX_TABLE:
+ * AAMD_EUNSUPPORTED. */
+int aamd_phaser(int32_t dtype, const void* x, void* out, void* workspace, int64_t rows, int64_t length, int64_t row_stride,
+                const int32_t* table, int64_t table_len, int64_t ring, double gain_in, double gain_out, double decay,
+                void* stream);
+
+/* F.flanger: row r is channel r % channels (channels <= 4); table is float[table_len] on the device with entries in
+ * [0, ring - 2] (the reference's lfo); channel_phase is a HOST array of `channels` offsets into the table.  The result equals
+ * the reference's loop bit for bit.  feedback_gain == 0 and general == 0: the streaming gather, which reads x as stored
+ * (a -0.0 is not turned into +0.0, a non-finite sample reaches only the outputs whose taps read it) and needs no workspace.
+ * ring > AAMD_FLANGER_MAX_RING or table_len > AAMD_EFFECTS_MAX_TABLE: AAMD_EUNSUPPORTED. */
+int aamd_flanger(int32_t dtype, const void* x, void* out, void* workspace, int64_t rows, int64_t length, int64_t row_stride,
+                 int32_t channels, const float* table, int64_t table_len, const int64_t* channel_phase, int64_t ring,
+                 double feedback_gain, double in_gain, double delay_gain, int32_t quadratic, int32_t general, void* stream);
 
 #ifdef __cplusplus
 }
