@@ -178,6 +178,17 @@ _SIGS = {
     "aamd_forced_align_workspace": (C.c_int64, [C.c_int64] * 3),
     "aamd_forced_align": (C.c_int, [C.c_int32, _P, _P, C.c_int32, _P, _P, C.c_int32] + [C.c_int64] * 4 + [C.c_int32, _P, _P, _P,
                                     _P]),
+    # CTC prefix beam search (additions to ABI 7)
+    "aamd_ctc_decoder_max_beam": (C.c_int32, []),
+    "aamd_ctc_decoder_row_threads": (C.c_int32, []),
+    "aamd_ctc_decoder_beam_threads": (C.c_int32, []),
+    "aamd_ctc_decoder_record_slots": (C.c_int32, [C.c_int32]),
+    "aamd_ctc_decoder_candidates": (C.c_int32, [C.c_int32]),
+    "aamd_ctc_decoder_max_frames": (C.c_int64, []),
+    "aamd_ctc_decoder_max_nodes": (C.c_int64, []),
+    "aamd_ctc_decoder_workspace": (C.c_int64, [C.c_int64] * 4),
+    "aamd_ctc_beam_search": (C.c_int, [C.c_int32, _P, _P, C.c_int32] + [C.c_int64] * 3 + [C.c_int32] * 3 + [C.c_double] +
+                             [_P] * 5),
     # SoX-style effects (additions to ABI 7)
     "aamd_effects_tiles": (C.c_int32, [C.c_int32]),
     "aamd_effects_workspace": (C.c_int64, [C.c_int32, C.c_int32] + [C.c_int64] * 3),

@@ -60,6 +60,8 @@
  *   aamd_overdrive            F.overdrive / F.phaser / F.flanger (the reference's Python loops over samples: a chunked
  *   aamd_phaser               float64 scan in two launches; one launch with the delay ring in LDS, bit for bit; a streaming
  *   aamd_flanger              gather where nothing is fed back) -- additions to ABI 7 as well
+ *   aamd_ctc_beam_search      models.decoder.cuda_ctc_decoder (the reference's CUDA-only libctc_prefix_decoder); a row pass and
+ *                             a beam pass, float64 scores -- an addition to ABI 7 as well
  *   aamd_detect_pitch_f32     F.detect_pitch_frequency (_compute_nccf + _find_max_per_frame + _median_smoothing in the
  *                             reference; an addition to ABI 7 as well)
  *
@@ -774,6 +776,40 @@ int aamd_phaser(int32_t dtype, const void* x, void* out, void* workspace, int64_
 int aamd_flanger(int32_t dtype, const void* x, void* out, void* workspace, int64_t rows, int64_t length, int64_t row_stride,
                  int32_t channels, const float* table, int64_t table_len, const int64_t* channel_phase, int64_t ring,
                  double feedback_gain, double in_gain, double delay_gain, int32_t quadratic, int32_t general, void* stream);
+
+/* ---- CTC prefix beam search (additions to ABI 7; csrc/ctc_decoder.h) ------------------------------------------------- */
+
+#define AAMD_CTC_DECODER_MAX_BEAM 32 /* the widest beam the beam kernel serves */
+
+/* The widest beam; threads per workgroup of the row pass (one wave per frame) and of the beam pass (one workgroup of four
+ * waves per example); for a beam of `beam`, the (value, token) slots of a frame's record (beam + 1) and the candidates of a
+ * frame (per entry: the stay, one extension per record slot, the extension by its own last token: beam * (beam + 3)); the
+ * two size limits beyond the 32-bit ones: the most frames of a call (batch * max_t) and the most trie nodes of an example
+ * (1 + beam * max_t). */
+int32_t aamd_ctc_decoder_max_beam(void);
+int32_t aamd_ctc_decoder_row_threads(void);
+int32_t aamd_ctc_decoder_beam_threads(void);
+int32_t aamd_ctc_decoder_record_slots(int32_t beam);
+int32_t aamd_ctc_decoder_candidates(int32_t beam);
+int64_t aamd_ctc_decoder_max_frames(void);
+int64_t aamd_ctc_decoder_max_nodes(void);
+
+/* Bytes of device workspace a call needs (16-byte aligned; written and read on the device only): a record of beam + 1
+ * (value, token) pairs per frame and 1 + beam * max_t trie nodes per example.  0 for sizes the search does not serve. */
+int64_t aamd_ctc_decoder_workspace(int64_t batch, int64_t max_t, int64_t vocab, int64_t beam);
+
+/* audio_amd.models.decoder.ctc_beam_search: CTC prefix beam search without a language model.  log_probs dense (batch,
+ * max_t, vocab) of `dtype` (AAMD_SA_*), lengths (batch,) int32 or int64 (lengths_int64), on the device and read there: no
+ * synchronisation.  A frame with log_probs[b][t][blank] > threshold is skipped entirely; float64 accumulation for every
+ * dtype; a candidate whose score is -inf or NaN is never kept.  tokens (batch, nbest, max_t) int32, zero beyond each
+ * length; token_lengths (batch, nbest) int32, -1 where the beam held fewer hypotheses; scores (batch, nbest) float64 in
+ * descending order, -inf for a missing hypothesis.  An example with a length outside [0, max_t] gets lengths -1 and scores
+ * NaN, and nothing is indexed with that length.  beam > AAMD_CTC_DECODER_MAX_BEAM, batch / max_t / vocab >= 2^31,
+ * batch * max_t > aamd_ctc_decoder_max_frames() (2^36) or 1 + beam * max_t > aamd_ctc_decoder_max_nodes() (2^31 - 1):
+ * AAMD_EUNSUPPORTED.  Two launches (row pass, beam pass). */
+int aamd_ctc_beam_search(int32_t dtype, const void* log_probs, const void* lengths, int32_t lengths_int64, int64_t batch,
+                         int64_t max_t, int64_t vocab, int32_t blank, int32_t beam, int32_t nbest, double threshold,
+                         void* workspace, int32_t* tokens, int32_t* token_lengths, double* scores, void* stream);
 
 #ifdef __cplusplus
 }
