@@ -733,3 +733,41 @@ def flanger_channel_phase(channels: int, table_len: int, channel_phase: float) -
     """The reference's per-channel offsets into the lfo table, ``int(c * table_len * channel_phase + 0.5)`` evaluated in
     float32 as torch evaluates it."""
     return ((np.arange(channels) * table_len).astype(np.float32) * np.float32(channel_phase) + np.float32(0.5)).astype(np.int64)
+
+
+# ---- InverseMelScale (csrc/inverse_mel.h): the filterbank's pseudo-inverse, built here in float64 ----------------------------
+def inverse_mel_rank_and_pinv(fb) -> Tuple[int, np.ndarray]:
+    """(rank, P) of ``A = fb^T`` (n_mels x n_stft), the filterbank's values taken as float64:
+    ``P = sum over sigma_i > rcond * sigma_max of v_i u_i^T / sigma_i`` with ``rcond = 2^-23 * max(n_stft, n_mels)``, as
+    float64 (n_stft, n_mels).  The cut is float32's, because the filterbank is a float32 object: the default 201 x 80 one has
+    75 singular values above it and the next at 1.9e-7 sigma_max, rounding noise of narrow filters that share bins; a float64
+    cut would keep that noise and return entries near 9e5."""
+    a = np.asarray(fb, dtype=np.float64).T
+    if a.ndim != 2 or a.size == 0:
+        raise ValueError("inverse_mel_matrix expects a non-empty (n_stft, n_mels) filterbank")
+    u, s, vt = np.linalg.svd(a, full_matrices=False)
+    rcond = 2.0 ** -23 * max(a.shape)
+    keep = s > rcond * s[0]
+    rank = int(keep.sum())
+    p = (vt[:rank].T / s[:rank]) @ u[:, :rank].T if rank else np.zeros(a.shape[::-1])
+    return rank, np.ascontiguousarray(p)
+
+
+def inverse_mel_matrix(fb) -> np.ndarray:
+    """The (n_stft, n_mels) float32 row-major pseudo-inverse the InverseMelScale kernel multiplies by: computed in float64
+    (`inverse_mel_rank_and_pinv`), rounded once."""
+    return np.ascontiguousarray(inverse_mel_rank_and_pinv(fb)[1].astype(np.float32))
+
+
+def inverse_mel_fragments(p: np.ndarray, bins: int = 64) -> np.ndarray:
+    """The (n_stft, n_mels) float32 matrix `p` as the InverseMelScale kernel reads it (csrc/inverse_mel.h, iml::frag_index):
+    tiles of `bins` rows, each tile `bins * K4` floats (K4 = n_mels rounded up to 4) with element (m, j) of the tile at
+    ``((m // 4) * 4 + j // 16) * 64 + (m % 4) * 16 + j % 16`` -- the order in which the matrix instruction's operand is read,
+    so that the kernel's staging is a straight copy.  Rows beyond n_stft and mels beyond n_mels are zeros."""
+    p = np.asarray(p, dtype=np.float32)
+    n_stft, n_mels = p.shape
+    k4, tiles = (n_mels + 3) // 4 * 4, (n_stft + bins - 1) // bins
+    padded = np.zeros((tiles * bins, k4), dtype=np.float32)
+    padded[:n_stft, :n_mels] = p
+    # (tile, j // 16, j % 16, m // 4, m % 4) -> (tile, m // 4, j // 16, m % 4, j % 16)
+    return np.ascontiguousarray(padded.reshape(tiles, bins // 16, 16, k4 // 4, 4).transpose(0, 3, 1, 4, 2)).reshape(-1)

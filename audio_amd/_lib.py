@@ -196,6 +196,9 @@ _SIGS = {
     "aamd_phaser": (C.c_int, [C.c_int32, _P, _P, _P] + [C.c_int64] * 3 + [_P, C.c_int64, C.c_int64] + [C.c_double] * 3 + [_P]),
     "aamd_flanger": (C.c_int, [C.c_int32, _P, _P, _P] + [C.c_int64] * 3 + [C.c_int32, _P, C.c_int64, C.POINTER(C.c_int64),
                                C.c_int64] + [C.c_double] * 3 + [C.c_int32, C.c_int32, _P]),
+    # InverseMelScale (additions to ABI 7)
+    "aamd_inverse_mel_tiles": (C.c_int32, [C.c_int32]),
+    "aamd_inverse_mel": (C.c_int, [C.c_int32, _P, _P, _P] + [C.c_int64] * 5 + [C.c_int32] * 3 + [_P]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS)

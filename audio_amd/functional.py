@@ -37,6 +37,7 @@ __all__ = [
     "psd", "mvdr_weights_souden", "mvdr_weights_rtf", "rtf_power", "rtf_evd", "apply_beamforming",
     "rnnt_loss", "forced_align", "merge_tokens", "TokenSpan",
     "overdrive", "phaser", "flanger", "effects_tiles",
+    "inverse_mel_scale", "inverse_mel_tiles",
 ]
 
 # --------------------------------------------------------------------------- #
@@ -3548,6 +3549,114 @@ def flanger(waveform: Tensor, sample_rate: int, delay: float = 0.0, depth: float
                                            float(in_gain), float(delay_gain), int(interpolation == "quadratic"), int(general),
                                            _lib.current_stream(waveform.device)))
     return out
+
+
+# --------------------------------------------------------------------------- #
+# InverseMelScale (csrc/inverse_mel.h)                                        #
+# --------------------------------------------------------------------------- #
+_IMEL_DRIVERS = ("gels", "gelsy", "gelsd", "gelss")
+_IMEL_PINNED: dict = {}              # id(P) -> P: pseudo-inverses a captured graph reads, kept for the life of the process
+
+
+def inverse_mel_tiles() -> Tuple[int, int, int]:
+    """(frames of one row per workgroup, bins of n_stft per LDS tile, the most mel bins the kernel serves) of
+    csrc/inverse_mel.h (iml::kFrames, iml::kBins, iml::kMaxMels)."""
+    lib = _lib.lib()
+    return int(lib.aamd_inverse_mel_tiles(0)), int(lib.aamd_inverse_mel_tiles(1)), int(lib.aamd_inverse_mel_tiles(2))
+
+
+def _inverse_mel_matrix(fb: Tensor, device, dtype: torch.dtype = torch.float32, fragments: bool = False) -> Tensor:
+    """The (n_stft, n_mels) pseudo-inverse of `fb` on `device` (`_host.inverse_mel_rank_and_pinv`: float64 SVD, float32
+    rank cut), rounded once to `dtype` (float64: not rounded); `fragments`: the float32 one as the flat tile image the kernel
+    reads (`_host.inverse_mel_fragments`).  Cached per buffer like every constant derived from one: the
+    key holds the buffer's identity, in-place version and storage, so `load_state_dict`, `fb.mul_()` and `.to()` rebuild it.
+    Building it copies `fb` to the host, which a graph capture cannot do: the first call must run eagerly."""
+    def make():
+        if fb.is_cuda and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("audio_amd: the pseudo-inverse of this filterbank is not on the device yet and cannot be built "
+                               "inside a graph capture (it needs the filterbank on the host); run the call once eagerly "
+                               "before capturing it")
+        p = _host.inverse_mel_rank_and_pinv(fb.detach().to(torch.float32).cpu().numpy())[1]
+        if dtype != torch.float64:
+            p = p.astype(np.float32)
+        if fragments:
+            p = _host.inverse_mel_fragments(p, inverse_mel_tiles()[1])
+        t = torch.from_numpy(np.ascontiguousarray(p)).to(device)
+        return t.to(dtype) if dtype in LOW_PRECISION else t
+    p = _tensor_cached(fb, ("inverse_mel", str(device), dtype, fragments), make)
+    if p.is_cuda and torch.cuda.is_current_stream_capturing():
+        with _CACHE_LOCK:
+            _IMEL_PINNED[id(p)] = p           # (an id is not reused while its tensor is held here)
+    return p
+
+
+def _imel_rows(x: Tensor) -> Tuple[Tensor, int, int, int]:
+    """(..., n_mels, T) as (rows, n_mels, T) that the kernel reads in place -- one row stride, unit stride along mel (the
+    frame-major view of a MelSpectrogram) or along time (a contiguous tensor) -- gathered where the strides are anything else.
+    Returns the tensor and its (row, mel, frame) strides as the kernel takes them."""
+    K, T_ = x.shape[-2], x.shape[-1]
+    rows = x.numel() // (K * T_)
+
+    def strides(t):
+        sr, sm, st = t.stride()
+        return (0 if rows == 1 else sr), (1 if K == 1 else sm), (1 if T_ == 1 else st)
+
+    x3 = x
+    if x3.dim() != 3:
+        try:
+            x3 = x.view(rows, K, T_)
+        except RuntimeError:
+            x3 = x.contiguous().view(rows, K, T_)
+    sr, sm, st = strides(x3)
+    if sr < 0 or sm < 1 or st < 1 or (sm != 1 and st != 1):
+        x3 = x3.contiguous()
+        sr, sm, st = strides(x3)
+    return x3, sr, sm, st
+
+
+def inverse_mel_scale(melspec: Tensor, fb: Tensor, log_input: bool = False) -> Tensor:
+    r"""EXTENSION (as ``mel_scale`` is): T.InverseMelScale.forward on a filterbank ``fb`` of shape ``(n_stft, n_mels)``:
+    ``(..., n_mels, time) -> (..., n_stft, time)``, ``relu(P @ y)`` per frame with ``P`` the pseudo-inverse of ``fb^T``
+    cut at float32's rank (``_host.inverse_mel_rank_and_pinv``; the minimum-norm least-squares solution, what the reference's
+    ``lstsq`` drivers return for a full-rank filterbank and ``gelsd`` for a rank-deficient one) and ``y = melspec`` or, with
+    ``log_input``, ``exp(melspec)`` evaluated in the load.
+
+    One launch (csrc/inverse_mel.h) on the float32 matrix instructions: FMA chains in ascending mel, one accumulator per
+    output, so the bits do not depend on layout, alignment or batch.  float32, float16 and bfloat16 are read in place (unit
+    stride along mel or along time; anything else is gathered first), computed in float32 and rounded once.  The result is
+    frame-major, returned as the ``(..., n_stft, time)`` view, the layout ``GriffinLim`` and ``InverseSpectrogram`` read.
+    ``n_mels`` up to 256 (``NotImplementedError`` beyond).  float64 input, or an input or ``fb`` that requires grad under
+    grad mode, takes ``torch.relu(torch.matmul(P, y))`` with ``P`` in the input's dtype (the precision / training path; ``P``
+    is a constant of ``fb``: no gradient reaches ``fb``).  The first call for a filterbank builds ``P`` on the host and cannot
+    run inside a graph capture; later calls can.  A plain Python entry point through the C ABI (not a dispatcher op)."""
+    if not isinstance(melspec, Tensor) or not isinstance(fb, Tensor):
+        raise TypeError("audio_amd: inverse_mel_scale: melspec and fb must be tensors")
+    if melspec.dtype not in _WA_FLOATS:
+        raise TypeError(f"audio_amd: inverse_mel_scale: melspec must be float16, bfloat16, float32 or float64 (got {melspec.dtype})")
+    if fb.dim() != 2 or not fb.is_floating_point():
+        raise ValueError(f"audio_amd: inverse_mel_scale: fb must be a floating-point (n_stft, n_mels) matrix (got {tuple(fb.shape)})")
+    n_stft, n_mels = int(fb.shape[0]), int(fb.shape[1])
+    if melspec.dim() < 2 or melspec.shape[-2] != n_mels:
+        raise ValueError("Expected an input with {} mel bins. Found: {}".format(
+            n_mels, melspec.shape[-2] if melspec.dim() >= 2 else tuple(melspec.shape)))
+    _wa_require(melspec, "inverse_mel_scale: melspec")
+    if melspec.dtype == torch.float64 or (torch.is_grad_enabled() and (melspec.requires_grad or fb.requires_grad)):
+        P = _inverse_mel_matrix(fb, melspec.device, melspec.dtype)
+        return torch.relu(torch.matmul(P, melspec.exp() if log_input else melspec))
+    limit = inverse_mel_tiles()[2]
+    if n_mels > limit:
+        raise NotImplementedError(f"audio_amd: inverse_mel_scale serves up to {limit} mel bins (got {n_mels})")
+    lead, T_ = tuple(melspec.shape[:-2]), int(melspec.shape[-1])
+    out = torch.empty(lead + (T_, n_stft), dtype=melspec.dtype, device=melspec.device)
+    if out.numel() == 0 or n_mels == 0:
+        return out.zero_().transpose(-1, -2)
+    x3, sr, sm, st = _imel_rows(melspec.detach())
+    P = _inverse_mel_matrix(fb, melspec.device, fragments=True)
+    with torch.cuda.device(melspec.device):
+        _lib.check(_lib.lib().aamd_inverse_mel(_SA_DTYPES[x3.dtype], x3.data_ptr(), P.data_ptr(), out.data_ptr(), x3.shape[0],
+                                               T_, sr, sm, st, n_stft, n_mels, int(bool(log_input)),
+                                               _lib.current_stream(melspec.device)))
+    return out.transpose(-1, -2)
 
 
 # --------------------------------------------------------------------------- #

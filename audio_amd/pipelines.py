@@ -26,7 +26,7 @@ from torch import Tensor
 from . import functional as F
 from . import transforms as T
 
-__all__ = ["RNNTFeatureExtractor", "piecewise_linear_log", "GAIN"]
+__all__ = ["RNNTFeatureExtractor", "piecewise_linear_log", "GAIN", "GriffinLimVocoder"]
 
 _decibel = 2 * 20 * math.log10(torch.iinfo(torch.int16).max)
 GAIN = pow(10, 0.05 * _decibel)                     # rnnt_pipeline.py:16-17
@@ -84,3 +84,31 @@ class RNNTFeatureExtractor(torch.nn.Module):
         if input.dim() == 1:
             return feats, torch.tensor([feats.shape[0]])
         return feats
+
+
+class GriffinLimVocoder(torch.nn.Module):
+    r"""Mel spectrogram -> waveform without a neural vocoder: the chain of the reference's Tacotron2 Griffin-Lim bundles
+    (``exp`` -> ``InverseMelScale(n_stft = n_fft // 2 + 1, n_mels, sample_rate, f_min, f_max, slaney / slaney)`` ->
+    ``GriffinLim(n_fft, power=1, hop_length, win_length=n_fft)``).  Here ``exp`` is the prologue of the InverseMelScale
+    launch (``F.inverse_mel_scale(log_input=True)``), whose frame-major result is the layout Griffin-Lim iterates on.
+
+    ``forward(mel_spec, lengths=None) -> (waveforms, lengths)``: ``mel_spec`` is ``(B, n_mels, T)`` natural-log mel,
+    ``waveforms`` is ``(B, hop_length * (T - 1))``; ``lengths`` is passed through unchanged, as the reference's bundle
+    does (it does not scale them by the hop).  Griffin-Lim starts from random phases: seed ``torch.manual_seed`` for
+    repeatable output."""
+
+    def __init__(self, sample_rate: int = 22050, n_fft: int = 1024, n_mels: int = 80, hop_length: int = 256,
+                 f_min: float = 0.0, f_max: float = 8000.0, n_iter: int = 32) -> None:
+        super().__init__()
+        self._sample_rate = sample_rate
+        self.inv_mel = T.InverseMelScale(n_stft=n_fft // 2 + 1, n_mels=n_mels, sample_rate=sample_rate, f_min=f_min,
+                                         f_max=f_max, norm="slaney", mel_scale="slaney")
+        self.griffin_lim = T.GriffinLim(n_fft=n_fft, n_iter=n_iter, power=1, hop_length=hop_length, win_length=n_fft)
+
+    @property
+    def sample_rate(self) -> int:
+        return self._sample_rate
+
+    def forward(self, mel_spec: Tensor, lengths: Optional[Tensor] = None) -> Tuple[Tensor, Optional[Tensor]]:
+        spec = F.inverse_mel_scale(mel_spec, self.inv_mel.fb, log_input=True)
+        return self.griffin_lim(spec), lengths

@@ -33,7 +33,7 @@ _norm_mode = F._norm_mode      # `normalized` as the op schemas' integer: 0 none
 # scripted module keeps ``state_dict`` keys, buffers and attributes.
 
 __all__ = ["Spectrogram", "InverseSpectrogram", "GriffinLim", "TimeStretch", "PitchShift", "Speed", "SpeedPerturbation",
-           "MelScale", "MelSpectrogram", "AmplitudeToDB", "MFCC", "Resample", "FFTConvolve", "ComputeDeltas",
+           "MelScale", "InverseMelScale", "MelSpectrogram", "AmplitudeToDB", "MFCC", "Resample", "FFTConvolve", "ComputeDeltas",
            "SlidingWindowCmn", "FrequencyMasking", "TimeMasking", "SpecAugment", "AddNoise", "Preemphasis", "Deemphasis",
            "Convolve", "PSD", "MVDR", "SoudenMVDR", "RTFMVDR", "RNNTLoss"]
 
@@ -431,6 +431,49 @@ class MelScale(torch.nn.Module):
 
     def forward(self, specgram: Tensor) -> Tensor:
         return F.mel_scale(specgram, self.fb)
+
+
+class InverseMelScale(torch.nn.Module):
+    r"""Mel bins -> STFT bins (reference: T.InverseMelScale, the ``lstsq`` form): ``(..., n_mels, time) -> (..., n_stft, time)``.
+
+    The reference solves ``fb^T x = melspec`` with ``torch.linalg.lstsq(driver=...)`` and applies ``relu``; ``gels`` assumes
+    a full-rank filterbank, which the default filterbanks are not (``melscale_fbanks(201, 0, 8000, 80, 16000)`` has rank 75 in
+    float32).  Here the result is DEFINED as ``relu(P @ melspec)`` with ``P`` the pseudo-inverse of ``fb^T`` built in float64
+    and cut at ``sigma_i > 2^-23 max(n_stft, n_mels) sigma_max``: the minimum-norm least-squares solution -- what all four
+    drivers return for a full-rank ``fb`` and ``gelsd`` (default float32 ``rcond``) for a rank-deficient one.  ``driver`` is
+    checked and stored and does not change the result.  One launch (``F.inverse_mel_scale``, csrc/inverse_mel.h); the module
+    calls a plain Python entry point, so it is not scriptable as one op."""
+    __constants__ = ["n_stft", "n_mels", "sample_rate", "f_min", "f_max"]
+
+    def __init__(
+        self,
+        n_stft: int,
+        n_mels: int = 128,
+        sample_rate: int = 16000,
+        f_min: float = 0.0,
+        f_max: Optional[float] = None,
+        norm: Optional[str] = None,
+        mel_scale: str = "htk",
+        driver: str = "gels",
+    ) -> None:
+        super().__init__()
+        self.n_mels = n_mels
+        self.sample_rate = sample_rate
+        self.f_max = f_max if f_max is not None else float(sample_rate // 2)
+        self.f_min = f_min
+        self.n_stft = n_stft
+        self.norm = norm
+        self.mel_scale = mel_scale
+        self.driver = driver
+        if f_min > self.f_max:
+            raise ValueError("Require f_min: {} <= f_max: {}".format(f_min, self.f_max))
+        if driver not in ["gels", "gelsy", "gelsd", "gelss"]:
+            raise ValueError(f'driver must be one of ["gels", "gelsy", "gelsd", "gelss"]. Found {driver}.')
+        fb = F.melscale_fbanks(n_stft, self.f_min, self.f_max, self.n_mels, self.sample_rate, self.norm, self.mel_scale)
+        self.register_buffer("fb", fb)
+
+    def forward(self, melspec: Tensor) -> Tensor:
+        return F.inverse_mel_scale(melspec, self.fb)
 
 
 class MelSpectrogram(torch.nn.Module):

@@ -811,6 +811,26 @@ int aamd_ctc_beam_search(int32_t dtype, const void* log_probs, const void* lengt
                          int64_t max_t, int64_t vocab, int32_t blank, int32_t beam, int32_t nbest, double threshold,
                          void* workspace, int32_t* tokens, int32_t* token_lengths, double* scores, void* stream);
 
+/* ---- InverseMelScale (additions to ABI 7; csrc/inverse_mel.h) -------------------------------------------------------- */
+
+#define AAMD_INVERSE_MEL_MAX_MELS 256 /* the most mel bins the kernel serves (both operands of a tile live in LDS) */
+
+/* which = 0: frames of one row per workgroup; 1: bins of n_stft per LDS tile; 2: the most mel bins (the define above). */
+int32_t aamd_inverse_mel_tiles(int32_t which);
+
+/* F.inverse_mel_scale: out[r][t][f] = relu(sum_m pinv[f][m] * y[r][m][t]), y = x or, with log_input, expf(x).  x is
+ * (rows, n_mels, frames) of `dtype` (AAMD_SA_F32 / F16 / BF16) read in place through its strides in elements: unit stride
+ * along mel (stride_mel == 1: frame-major) or along time (stride_frame == 1); anything else is AAMD_EINVAL (gather first).
+ * pinv is the (n_stft, n_mels) float32 matrix on the device, 16-byte aligned, laid out tile by tile as the kernel reads it:
+ * ceil(n_stft / 64) tiles of 64 * K4 floats (K4 = n_mels rounded up to 4), element (m, j) of a tile -- j the row within
+ * the tile -- at ((m / 4) * 4 + j / 16) * 64 + (m % 4) * 16 + j % 16, zeros beyond n_stft and n_mels
+ * (_host.inverse_mel_fragments).  out is dense (rows, frames, n_stft) of `dtype`.  float32 FMA chains
+ * in ascending m on the matrix cores, one accumulator per output, rounded once to `dtype`: the result does not depend on
+ * the layout, the alignment or the number of rows.  n_mels > AAMD_INVERSE_MEL_MAX_MELS: AAMD_EUNSUPPORTED.  One launch. */
+int aamd_inverse_mel(int32_t dtype, const void* x, const float* pinv, void* out, int64_t rows, int64_t frames,
+                     int64_t stride_row, int64_t stride_mel, int64_t stride_frame, int32_t n_stft, int32_t n_mels,
+                     int32_t log_input, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
