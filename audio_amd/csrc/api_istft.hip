@@ -35,9 +35,7 @@ int aamd_istft_f32(const float* spec, const float* window, const float* twiddle,
     m400::Inv400Geom ig{g, og.interior};
     const int tiles_per_row = (g.n_frames + m400::kFramesPerWave - 1) / m400::kFramesPerWave;
     const int64_t n_tiles = g.rows * tiles_per_row;
-    int64_t blocks = dev_props().cu_count;
-    const int64_t need = (n_tiles + m400::kInvWaves - 1) / m400::kInvWaves;
-    if (blocks > need) blocks = need;
+    const int64_t blocks = m400::inv_blocks(dev_props().cu_count, n_tiles);
     const auto* sp = reinterpret_cast<const cplx<float>*>(spec);
 #define AAMD_I400(HH)                                                                                             \
     return launch(m400::istft400_kernel<HH>, blocks, 64 * m400::kInvWaves,                                        \
@@ -49,21 +47,14 @@ int aamd_istft_f32(const float* spec, const float* window, const float* twiddle,
   if ((g.n_fft == 256 || g.n_fft == 512 || g.n_fft == 1024 || g.n_fft == 2048) && !force_generic()) {
     // register-resident wave FFT run as the inverse (stft_pow2.h)
     p2::InvGeom ig{g, og.interior};
-    const int64_t ppr = (g.n_frames + 1) / 2, n_pairs = g.rows * ppr;
     const auto* sp = reinterpret_cast<const p2::C32*>(spec);
     const auto* twc = reinterpret_cast<const p2::C32*>(twiddle);
-    int64_t blocks = (int64_t)dev_props().cu_count * (g.n_fft <= 512 ? 8 : g.n_fft == 1024 ? 4 : 2);
-    const int64_t need = (n_pairs + p2::kWaves - 1) / p2::kWaves;
-    if (blocks > need) blocks = need;
-    // runs of consecutive pairs per wave (overlap-add in an LDS ring, plain stores); hop > n_fft leaves gaps the ring
-    // logic does not model: pair-at-a-time atomics there
-    const bool use_runs = g.hop <= g.n_fft && (policy() & AAMD_POLICY_ISTFT_ATOMIC) == 0;
-    const int run_len = 16;
-    const int64_t rpr = (ppr + run_len - 1) / run_len, n_runs = g.rows * rpr;
-    if (use_runs) {
-      const int64_t need_r = (n_runs + p2::kWaves - 1) / p2::kWaves;
-      if (blocks > need_r) blocks = need_r;
-    }
+    // runs of consecutive pairs per wave, or pair-at-a-time atomics (hop > n_fft, or by policy): p2::inv_plan
+    const p2::InvPlan pl = p2::inv_plan(g.n_fft, g.hop, dev_props().cu_count, g.rows, g.n_frames,
+                                        (policy() & AAMD_POLICY_ISTFT_ATOMIC) != 0);
+    const bool use_runs = pl.use_runs;
+    const int run_len = pl.run_len;
+    const int64_t ppr = pl.pairs_per_row, n_pairs = pl.n_pairs, rpr = pl.runs_per_row, n_runs = pl.n_runs, blocks = pl.blocks;
 #define AAMD_IP2(EE)                                                                                              \
     return use_runs                                                                                               \
         ? launch(p2::istft_pow2_run_kernel<EE>, blocks, 64 * p2::kWaves,                                          \

@@ -61,9 +61,7 @@ int aamd_kaldi_features_f32(const float* wav, const float* window, const float* 
     return launch(kk, nblk, kgen::kThreads, lds, (hipStream_t)stream, kg, plan, pb, (int)bpu, wav, window, twg, mb, out);
   }
   const int64_t n_pairs = (d->n_frames + 1) / 2 * kg.n_utt;
-  int64_t blocks = (int64_t)dev_props().cu_count * 4;
-  const int64_t need = (n_pairs + p2::kWaves - 1) / p2::kWaves;
-  if (blocks > need) blocks = need;
+  const int64_t blocks = p2::kaldi_blocks(dev_props().cu_count, n_pairs);
   const auto* twc = reinterpret_cast<const p2::C32*>(twiddle);
 #define AAMD_KALDI(EE, MODE)                                                                                  \
   return launch(p2::kaldi_pow2_kernel<EE, MODE>, blocks, 64 * p2::kWaves,                                     \

@@ -55,11 +55,7 @@ int launch_pow2(const StftGeom& g, const MelBandsDev& mb, const float* wav, cons
   if (EPI == EPI_MEL && p2::mel_in_lds(mb.n_mels, mb.max_width))
     lds += (size_t)p2::mel_lds_floats(mb.n_mels, mb.max_width) * sizeof(float);
   auto kern = p2::stft_pow2_kernel<E, EPI>;
-  // persistent waves striding over the pairs; workgroups per CU measured best on 256 x 10 s (among 2..16):
-  // 4 / 2 / 1 workgroups of 4 waves are resident at 126 / 204 / 256 VGPRs, the grid is two resident rounds
-  int64_t blocks = (int64_t)dev_props().cu_count * (E <= 8 ? 8 : E == 16 ? 4 : 2);
-  const int64_t need = (n_pairs + p2::kWaves - 1) / p2::kWaves;
-  if (blocks > need) blocks = need;
+  const int64_t blocks = p2::fwd_blocks(E, dev_props().cu_count, n_pairs);     // persistent waves striding over the pairs
   return launch(kern, blocks, 64 * p2::kWaves, lds, s, g, wav, window, reinterpret_cast<const p2::C32*>(twiddle), mb, out,
                 pairs_per_row, n_pairs);
 }

@@ -142,6 +142,11 @@ AAMD_HD void inv400_flush(int lane, const Inv400Geom& ig, int64_t t0, int n_vali
 // 8 waves per workgroup (2 per SIMD, 256-VGPR budget): with 12 the 40 spectrum loads in flight + the two 20-point
 // register sets spilled 26 VGPRs, and every spill reload was a serialised memory round trip inside the tile loop
 constexpr int kInvWaves = 8;
+// launch arithmetic (host): one workgroup per CU, persistent waves striding over the six-frame tiles
+inline int64_t inv_blocks(int cu_count, int64_t n_tiles) {
+  const int64_t need = (n_tiles + kInvWaves - 1) / kInvWaves;
+  return cu_count > need ? need : cu_count;
+}
 
 #if defined(__HIPCC__)
 template <int H>

@@ -1,4 +1,4 @@
-// Spectrogram / MelSpectrogram for power-of-two n_fft = 64 E (E = 8, 16, 32: n_fft = 512, 1024, 2048), any hop, window
+// Spectrogram / MelSpectrogram for power-of-two n_fft = 64 E (E = 4, 8, 16, 32: n_fft = 256, 512, 1024, 2048), any hop, window
 // and padding mode (functional/functional.py:112-145, transforms/_transforms.py:403-415, 612-622): the frames
 // the radix-20x20 kernel (melspec400.h) does not cover but that TTS / vocoder / librosa-style front-ends use.
 //
@@ -39,6 +39,37 @@ struct Cfg {
 };
 
 using C32 = cplx<float>;
+
+// ---- launch arithmetic (host; tests/test_gpu_fuzz_stft_pow2.py mirrors these through the CPU replay) ----------------------
+// Persistent waves striding over the pairs; workgroups per CU measured best on 256 x 10 s (among 2..16):
+// 4 / 2 / 1 workgroups of 4 waves are resident at 126 / 204 / 256 VGPRs, the grid is two resident rounds.
+inline int64_t blocks_for(int64_t cap, int64_t n_items) {
+  const int64_t need = (n_items + kWaves - 1) / kWaves;
+  return cap > need ? need : cap;
+}
+inline int64_t fwd_blocks(int E, int cu_count, int64_t n_pairs) {
+  return blocks_for((int64_t)cu_count * (E <= 8 ? 8 : E == 16 ? 4 : 2), n_pairs);
+}
+inline int64_t kaldi_blocks(int cu_count, int64_t n_pairs) { return blocks_for((int64_t)cu_count * 4, n_pairs); }
+// The inverse: runs of `run_len` consecutive pairs per wave (overlap-add in an LDS ring, plain stores); hop > n_fft leaves
+// gaps the ring logic does not model: pair-at-a-time atomics there, and under AAMD_POLICY_ISTFT_ATOMIC (`atomic_policy`).
+struct InvPlan {
+  bool use_runs;
+  int run_len;
+  int64_t pairs_per_row, n_pairs, runs_per_row, n_runs, blocks;
+};
+inline InvPlan inv_plan(int n_fft, int hop, int cu_count, int64_t rows, int64_t n_frames, bool atomic_policy) {
+  InvPlan p{};
+  p.pairs_per_row = (n_frames + 1) / 2;
+  p.n_pairs = rows * p.pairs_per_row;
+  p.blocks = fwd_blocks(n_fft / 64, cu_count, p.n_pairs);
+  p.use_runs = hop <= n_fft && !atomic_policy;
+  p.run_len = 16;
+  p.runs_per_row = (p.pairs_per_row + p.run_len - 1) / p.run_len;
+  p.n_runs = rows * p.runs_per_row;
+  if (p.use_runs) p.blocks = blocks_for(p.blocks, p.n_runs);
+  return p;
+}
 
 // cos / sin of 2 pi q / 32
 AAMD_HD constexpr float cos32(int q) {

@@ -1305,6 +1305,19 @@ int sim_fco_plan(int64_t rows, int64_t ny, int64_t out_len, int cu_count, int64_
   return cheaper ? 1 : 0;
 }
 
+// The grid sizes of the register-FFT STFT / ISTFT / Kaldi launchers and of the n_fft = 400 inverse by the headers' own functions,
+// for the host mirror of tests/test_gpu_fuzz_stft_pow2.py.  sim_p2_inv_plan: out = {use_runs, run_len, runs_per_row, n_runs,
+// blocks, pairs_per_row, n_pairs} of p2::inv_plan.
+int64_t sim_p2_fwd_blocks(int E, int cu_count, int64_t n_pairs) { return p2::fwd_blocks(E, cu_count, n_pairs); }
+int64_t sim_p2_kaldi_blocks(int cu_count, int64_t n_pairs) { return p2::kaldi_blocks(cu_count, n_pairs); }
+int64_t sim_m400_inv_blocks(int cu_count, int64_t n_tiles) { return m400::inv_blocks(cu_count, n_tiles); }
+int sim_p2_inv_plan(int n_fft, int hop, int cu_count, int64_t rows, int64_t n_frames, int atomic_policy, int64_t* out) {
+  const p2::InvPlan p = p2::inv_plan(n_fft, hop, cu_count, rows, n_frames, atomic_policy != 0);
+  out[0] = p.use_runs ? 1 : 0; out[1] = p.run_len; out[2] = p.runs_per_row; out[3] = p.n_runs; out[4] = p.blocks;
+  out[5] = p.pairs_per_row; out[6] = p.n_pairs;
+  return 0;
+}
+
 // Replay of the overlap-save path (fco::spectrum_kernel + fco::overlap_save_kernel): the same
 // launcher logic as aamd_fftconvolve_f32, 1024 "threads" per phase, phases separated where the
 // kernel has barriers.  Twiddles as the device twiddle_kernel computes them (fp64 -> fp32).

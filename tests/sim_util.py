@@ -345,6 +345,38 @@ def sim_fco_plan(rows, ny, out_len, cu_count):
             dict(zip(("n_part", "segs", "n_blocks", "seg_blocks"), v[5:])))
 
 
+def sim_p2_fwd_blocks(E, cu_count, n_pairs):
+    """p2::fwd_blocks itself (csrc/stft_pow2.h)."""
+    f = sim().sim_p2_fwd_blocks
+    f.argtypes, f.restype = [C.c_int, C.c_int, C.c_int64], C.c_int64
+    return int(f(E, cu_count, n_pairs))
+
+
+def sim_p2_kaldi_blocks(cu_count, n_pairs):
+    """p2::kaldi_blocks itself (csrc/stft_pow2.h)."""
+    f = sim().sim_p2_kaldi_blocks
+    f.argtypes, f.restype = [C.c_int, C.c_int64], C.c_int64
+    return int(f(cu_count, n_pairs))
+
+
+def sim_m400_inv_blocks(cu_count, n_tiles):
+    """m400::inv_blocks itself (csrc/istft400.h)."""
+    f = sim().sim_m400_inv_blocks
+    f.argtypes, f.restype = [C.c_int, C.c_int64], C.c_int64
+    return int(f(cu_count, n_tiles))
+
+
+def sim_p2_inv_plan(n_fft, hop, cu_count, rows, n_frames, atomic_policy):
+    """p2::inv_plan itself (csrc/stft_pow2.h): dict(use_runs, run_len, runs_per_row, n_runs, blocks, pairs_per_row, n_pairs)."""
+    out = np.zeros(7, dtype=np.int64)
+    f = sim().sim_p2_inv_plan
+    f.argtypes = [C.c_int] * 3 + [C.c_int64] * 2 + [C.c_int, C.c_void_p]
+    assert f(n_fft, hop, cu_count, rows, n_frames, int(bool(atomic_policy)), fptr(out)) == 0
+    d = dict(zip(("use_runs", "run_len", "runs_per_row", "n_runs", "blocks", "pairs_per_row", "n_pairs"), (int(v) for v in out)))
+    d["use_runs"] = bool(d["use_runs"])
+    return d
+
+
 def sim_istft(spec_fm, window_padded, length, n_fft, hop, center=True, pad_mode="constant", pad=0, scale=1.0,
               adjoint=False, inv_env=None, pow2=False, runs=0, fast400=False, trace=None):
     """trace: optional dict; filled with 'stores' / 'adds' int32 arrays (rows, length): plain stores / atomic adds per sample."""

@@ -1384,7 +1384,7 @@ def test_speed_and_speed_perturbation_vs_reference():
 
 @pytest.mark.parametrize("n_fft,hop", [(256, 64), (256, 100), (512, 128), (512, 160), (1024, 256), (1024, 411), (2048, 512)])
 def test_pow2_wave_fft_equals_generic_and_torch_stft(n_fft, hop):
-    """The register-resident wave FFT (csrc/stft_pow2.h; n_fft = 512 / 1024 / 2048) against the generic Stockham
+    """The register-resident wave FFT (csrc/stft_pow2.h; n_fft = 256 / 512 / 1024 / 2048) against the generic Stockham
     kernel and torch.stft in float64 on the CPU: power, magnitude, complex and mel outputs, every padding mode,
     ragged lengths (odd frame counts, rows shorter than a frame)."""
     import audio_amd.transforms as T
