@@ -771,3 +771,19 @@ def inverse_mel_fragments(p: np.ndarray, bins: int = 64) -> np.ndarray:
     padded[:n_stft, :n_mels] = p
     # (tile, j // 16, j % 16, m // 4, m % 4) -> (tile, m // 4, j // 16, m % 4, j % 16)
     return np.ascontiguousarray(padded.reshape(tiles, bins // 16, 16, k4 // 4, 4).transpose(0, 3, 1, 4, 2)).reshape(-1)
+
+
+# ---- voice-activity trimming (csrc/vad.h): the two Hann windows and the transform's twiddles, built here in float64 --------------
+def vad_tables(win: int, bins: int, n_fft: int) -> np.ndarray:
+    """float32[win + bins + n_fft]: ``2 / sqrt(win)`` times the periodic Hann window of the measurement, ``2 / sqrt(bins)``
+    times that of the cepstrum, and ``(cos, -sin)(2 pi k / n_fft)`` for ``k < n_fft / 2`` -- each evaluated in float64 and
+    rounded once (the reference builds its windows in float32)."""
+    if win < 1 or bins < 1 or n_fft < 2 or n_fft & (n_fft - 1):
+        raise ValueError("vad_tables: need win >= 1, bins >= 1 and a power-of-two n_fft")
+    i = np.arange(win, dtype=np.float64)
+    w = 2.0 / math.sqrt(win) * (0.5 - 0.5 * np.cos(2 * math.pi * i / win))
+    k = np.arange(bins, dtype=np.float64)
+    cw = 2.0 / math.sqrt(bins) * (0.5 - 0.5 * np.cos(2 * math.pi * k / bins))
+    a = 2 * math.pi * np.arange(n_fft // 2, dtype=np.float64) / n_fft
+    tw = np.stack([np.cos(a), -np.sin(a)], axis=-1).reshape(-1)
+    return np.concatenate([w, cw, tw]).astype(np.float32)

@@ -199,6 +199,12 @@ _SIGS = {
     # InverseMelScale (additions to ABI 7)
     "aamd_inverse_mel_tiles": (C.c_int32, [C.c_int32]),
     "aamd_inverse_mel": (C.c_int, [C.c_int32, _P, _P, _P] + [C.c_int64] * 5 + [C.c_int32] * 3 + [_P]),
+    # voice-activity trimming (additions to ABI 7)
+    "aamd_vad_tiles": (C.c_int32, [C.c_int32]),
+    "aamd_vad_workspace": (C.c_int64, [C.c_int64] * 3),
+    "aamd_vad_measure": (C.c_int, [C.c_int32, _P] + [C.c_int64] * 3 + [C.c_int32] * 8 + [C.c_double] * 4 + [_P, _P, _P, C.c_int64,
+                                   _P]),
+    "aamd_vad_trigger": (C.c_int, [_P] + [C.c_int64] * 6 + [C.c_double] * 2 + [_P] * 4),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS)

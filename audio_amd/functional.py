@@ -37,6 +37,7 @@ __all__ = [
     "psd", "mvdr_weights_souden", "mvdr_weights_rtf", "rtf_power", "rtf_evd", "apply_beamforming",
     "rnnt_loss", "forced_align", "merge_tokens", "TokenSpan",
     "overdrive", "phaser", "flanger", "effects_tiles",
+    "vad", "vad_start", "vad_tiles",
     "inverse_mel_scale", "inverse_mel_tiles",
 ]
 
@@ -3657,6 +3658,230 @@ def inverse_mel_scale(melspec: Tensor, fb: Tensor, log_input: bool = False) -> T
                                                T_, sr, sm, st, n_stft, n_mels, int(bool(log_input)),
                                                _lib.current_stream(melspec.device)))
     return out.transpose(-1, -2)
+
+
+# --------------------------------------------------------------------------- #
+# Voice-activity trimming (csrc/vad.h)                                        #
+# --------------------------------------------------------------------------- #
+VAD_MAX_FFT = 8192                   # AAMD_VAD_MAX_FFT: the largest measurement transform (the defaults up to 81.9 kHz)
+_VAD_TABLES: "collections.OrderedDict" = collections.OrderedDict()   # (win, bins, n_fft, device) -> device tables, LRU
+_VAD_PINNED: dict = {}               # tables a captured graph reads: kept for the life of the process
+_VAD_TABLES_MAX = 16
+
+_VadPlan = collections.namedtuple("_VadPlan", "L N P M gap fixed s0 s1 c0 c1 boot_max up down smooth trig nra level")
+
+
+def vad_tiles() -> Tuple[int, int, int, int]:
+    """(threads per workgroup of the measurement kernels, the largest and the smallest measurement transform, rows per
+    workgroup of the trigger kernel) of csrc/vad.h: vad::kThreads, kMaxN, kMinN, kTrigThreads."""
+    lib = _lib.lib()
+    return tuple(int(lib.aamd_vad_tiles(i)) for i in range(4))
+
+
+def _vad_plan(sample_rate, trigger_level, trigger_time, search_time, allowed_gap, pre_trigger_time, boot_time, noise_up_time,
+              noise_down_time, noise_reduction_amount, measure_freq, measure_duration, measure_smooth_time, hp_filter_freq,
+              lp_filter_freq, hp_lifter_freq, lp_lifter_freq) -> _VadPlan:
+    """The reference's derived quantities, in Python arithmetic on the host; the parameter errors."""
+    named = dict(sample_rate=sample_rate, trigger_level=trigger_level, trigger_time=trigger_time, search_time=search_time,
+                 allowed_gap=allowed_gap, pre_trigger_time=pre_trigger_time, boot_time=boot_time, noise_up_time=noise_up_time,
+                 noise_down_time=noise_down_time, noise_reduction_amount=noise_reduction_amount, measure_freq=measure_freq,
+                 measure_smooth_time=measure_smooth_time, hp_filter_freq=hp_filter_freq, lp_filter_freq=lp_filter_freq,
+                 hp_lifter_freq=hp_lifter_freq, lp_lifter_freq=lp_lifter_freq)
+    if measure_duration is not None:
+        named["measure_duration"] = measure_duration
+    for k, v in named.items():
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v):
+            raise ValueError(f"audio_amd: vad: {k} must be a finite number (got {v!r})")
+    for k in ("sample_rate", "measure_freq", "trigger_time", "search_time", "noise_up_time", "noise_down_time",
+              "measure_smooth_time", "hp_lifter_freq", "lp_lifter_freq", "measure_duration"):
+        if k in named and not named[k] > 0:
+            raise ValueError(f"audio_amd: vad: {k} must be positive (got {named[k]!r})")
+    for k in ("allowed_gap", "pre_trigger_time", "boot_time", "hp_filter_freq", "lp_filter_freq"):
+        if named[k] < 0:
+            raise ValueError(f"audio_amd: vad: {k} must not be negative (got {named[k]!r})")
+    sr, mf = sample_rate, measure_freq
+    md = 2.0 / mf if measure_duration is None else measure_duration
+    L = int(sr * md + 0.5)
+    if L < 1:
+        raise ValueError(f"audio_amd: vad: sample_rate * measure_duration rounds to a measurement of {L} samples; at least 1 is "
+                         "needed")
+    N = 16
+    while N < L:
+        N *= 2
+    P = int(sr / mf + 0.5)
+    if P < 1:
+        raise ValueError(f"audio_amd: vad: sample_rate / measure_freq rounds to a measurement period of {P} samples; at least 1 "
+                         "is needed")
+    s0 = max(int(hp_filter_freq / sr * N + 0.5), 1)
+    s1 = min(int(lp_filter_freq / sr * N + 0.5), N // 2)
+    if s1 <= s0:
+        raise ValueError(f"audio_amd: vad: hp_filter_freq and lp_filter_freq leave no spectrum bin: start {s0}, end {s1}")
+    c0 = math.ceil(sr * 0.5 / lp_lifter_freq)
+    c1 = min(math.floor(sr * 0.5 / hp_lifter_freq), N // 4)
+    if c1 <= c0:
+        raise ValueError("Expected cepstrum_start to be smaller than cepstrum_end."
+                         f"Found: cepstrum_start: {c0}, cepstrum_end: {c1}.")
+    if N > VAD_MAX_FFT:
+        raise NotImplementedError(f"audio_amd: vad serves measurement transforms up to {VAD_MAX_FFT} points (the defaults up to "
+                                  f"81.9 kHz); {L} samples per measurement need {N}")
+    mult = lambda t: math.exp(-1.0 / (t * mf))      # noqa: E731
+    return _VadPlan(L=L, N=N, P=P, M=math.ceil(search_time * mf), gap=int(allowed_gap * mf + 0.5),
+                    fixed=int(pre_trigger_time * sr + 0.5), s0=s0, s1=s1, c0=c0, c1=c1, boot_max=int(boot_time * mf - 0.5),
+                    up=mult(noise_up_time), down=mult(noise_down_time), smooth=mult(measure_smooth_time), trig=mult(trigger_time),
+                    nra=float(noise_reduction_amount), level=float(trigger_level))
+
+
+def _vad_tables(plan: _VadPlan, device) -> Tensor:
+    """The two windows and the twiddles of `plan` on `device`: built on the host (float64, rounded once) and uploaded once.
+    Never allocated from a capture's pool: the first call with this plan must run eagerly."""
+    k = (plan.L, plan.s1 - plan.s0, plan.N, str(device))
+    capturing = torch.cuda.is_current_stream_capturing()
+    with _CACHE_LOCK:
+        t = _VAD_PINNED.get(k)
+        if t is None:
+            t = _VAD_TABLES.get(k)
+            if t is not None:
+                _VAD_TABLES.move_to_end(k)
+                if capturing:
+                    _VAD_PINNED[k] = t
+    if t is not None:
+        return t
+    if capturing:
+        raise RuntimeError("audio_amd: the window tables of these vad parameters are not on the device yet and cannot be built "
+                           "inside a graph capture; run the call once eagerly before capturing it")
+    t = torch.from_numpy(_host.vad_tables(k[0], k[1], k[2])).to(device)
+    with _CACHE_LOCK:
+        t = _VAD_TABLES.setdefault(k, t)
+        _VAD_TABLES.move_to_end(k)
+        while len(_VAD_TABLES) > _VAD_TABLES_MAX:
+            _VAD_TABLES.popitem(last=False)
+    return t
+
+
+def _vad_frames(T_: int, plan: _VadPlan) -> int:
+    return 0 if T_ <= plan.L else (T_ - plan.L - 1) // plan.P + 1
+
+
+def _vad_measure_rows(x2: Tensor, plan: _VadPlan) -> Tensor:
+    """(rows, frames) float32 measurements of the rows of x2, every row a recording of its own: three launches."""
+    rows, T_ = x2.shape
+    frames = _vad_frames(T_, plan)
+    meas = torch.empty((rows, frames), dtype=torch.float32, device=x2.device)
+    if meas.numel() == 0:
+        return meas
+    tables = _vad_tables(plan, x2.device)
+    lib = _lib.lib()
+    ws = torch.empty((int(lib.aamd_vad_workspace(rows, frames, plan.s1 - plan.s0)) // 4,), dtype=torch.float32, device=x2.device)
+    with torch.cuda.device(x2.device):
+        _lib.check(lib.aamd_vad_measure(_SA_DTYPES[x2.dtype], x2.data_ptr(), rows, T_, _wa_stride(x2), plan.L, plan.N, plan.P,
+                                        plan.s0, plan.s1, plan.c0, plan.c1, plan.boot_max, plan.smooth, plan.up, plan.down,
+                                        plan.nra, tables.data_ptr(), ws.data_ptr(), meas.data_ptr(), frames,
+                                        _lib.current_stream(x2.device)))
+    return meas
+
+
+def _vad_trigger(meas: Tensor, ring: int, gap: int, period: int, fixed: int, trigger_level: float, trigger_mult: float,
+                 joint: bool = True) -> Tuple[Tensor, Tensor, Optional[Tensor]]:
+    """The trigger pass over dense float32 (rows, frames) measurements on the device (private: F.vad and F.vad_start call it,
+    the tests drive it with synthetic measurements): int64 (first frame per row or -1, start per row or -1, the joint start
+    as a 1-element tensor where `joint`).  One launch, two with the joint start; no synchronisation."""
+    if meas.dim() != 2 or meas.dtype != torch.float32 or not meas.is_contiguous():
+        raise ValueError("audio_amd: vad: the measurements must be a contiguous float32 (rows, frames) tensor")
+    _wa_require(meas, "vad: measurements")
+    rows, frames = meas.shape
+    first = torch.empty((rows,), dtype=torch.int64, device=meas.device)
+    start = torch.empty((rows,), dtype=torch.int64, device=meas.device)
+    jt = torch.empty((1,), dtype=torch.int64, device=meas.device) if joint else None
+    with torch.cuda.device(meas.device):
+        _lib.check(_lib.lib().aamd_vad_trigger(_lib.ptr(meas), rows, frames, int(ring), int(gap), int(period), int(fixed),
+                                               float(trigger_level), float(trigger_mult), _lib.ptr(first), _lib.ptr(start),
+                                               jt.data_ptr() if joint else 0, _lib.current_stream(meas.device)))
+    return first, start, jt
+
+
+def _vad_prepare(waveform: Tensor, what: str, plan_args) -> Tuple[Tensor, _VadPlan]:
+    _fx_check_type(waveform, what)
+    if waveform.dim() < 1:
+        raise ValueError(f"audio_amd: {what} expects (..., time), got a 0-dimensional tensor")
+    plan = _vad_plan(*plan_args)
+    _fx_check_device(waveform, what)
+    return _fx_rows(waveform)[0], plan
+
+
+def vad_start(waveform: Tensor, sample_rate: int, trigger_level: float = 7.0, trigger_time: float = 0.25,
+              search_time: float = 1.0, allowed_gap: float = 0.25, pre_trigger_time: float = 0.0, boot_time: float = 0.35,
+              noise_up_time: float = 0.1, noise_down_time: float = 0.01, noise_reduction_amount: float = 1.35,
+              measure_freq: float = 20.0, measure_duration: Optional[float] = None, measure_smooth_time: float = 0.4,
+              hp_filter_freq: float = 50.0, lp_filter_freq: float = 6000.0, hp_lifter_freq: float = 150.0,
+              lp_lifter_freq: float = 2000.0) -> Tensor:
+    r"""Where :func:`vad` would start each row of ``(..., time)`` if the row were a single-channel recording of its own (an
+    extension; the reference has no batched form): int64 of shape ``waveform.shape[:-1]`` on the device, the first sample to
+    keep, or ``-1`` where the row never triggers -- what a batched pipeline builds lengths and masks from.  Parameters as
+    :func:`vad`.  Four launches and no synchronisation; can be captured in a graph once the window tables of the parameters
+    are cached, i.e. after one eager call (the first call inside a capture raises).  Rows are read in place through their row
+    stride; a non-unit sample stride is gathered first.  Deterministic; forward-only; a plain Python entry point through the C
+    ABI (not registered as a dispatcher op)."""
+    x2, plan = _vad_prepare(waveform, "vad_start", (sample_rate, trigger_level, trigger_time, search_time, allowed_gap,
+                                                   pre_trigger_time, boot_time, noise_up_time, noise_down_time,
+                                                   noise_reduction_amount, measure_freq, measure_duration, measure_smooth_time,
+                                                   hp_filter_freq, lp_filter_freq, hp_lifter_freq, lp_lifter_freq))
+    meas = _vad_measure_rows(x2, plan)
+    _, start, _ = _vad_trigger(meas, plan.M, plan.gap, plan.P, plan.fixed, plan.level, plan.trig, joint=False)
+    return start.view(tuple(waveform.shape[:-1]))
+
+
+def _vad_measures(waveform: Tensor, sample_rate: int, trigger_level: float = 7.0, trigger_time: float = 0.25,
+                  search_time: float = 1.0, allowed_gap: float = 0.25, pre_trigger_time: float = 0.0, boot_time: float = 0.35,
+                  noise_up_time: float = 0.1, noise_down_time: float = 0.01, noise_reduction_amount: float = 1.35,
+                  measure_freq: float = 20.0, measure_duration: Optional[float] = None, measure_smooth_time: float = 0.4,
+                  hp_filter_freq: float = 50.0, lp_filter_freq: float = 6000.0, hp_lifter_freq: float = 150.0,
+                  lp_lifter_freq: float = 2000.0) -> Tensor:
+    """Diagnostic (private, like ``_compute_nccf``): the ``(rows, frames)`` float32 measurements that the trigger pass of
+    :func:`vad` / :func:`vad_start` reads, bit for bit; rows = all leading dimensions flattened."""
+    x2, plan = _vad_prepare(waveform, "vad", (sample_rate, trigger_level, trigger_time, search_time, allowed_gap,
+                                             pre_trigger_time, boot_time, noise_up_time, noise_down_time, noise_reduction_amount,
+                                             measure_freq, measure_duration, measure_smooth_time, hp_filter_freq, lp_filter_freq,
+                                             hp_lifter_freq, lp_lifter_freq))
+    return _vad_measure_rows(x2, plan)
+
+
+def vad(waveform: Tensor, sample_rate: int, trigger_level: float = 7.0, trigger_time: float = 0.25, search_time: float = 1.0,
+        allowed_gap: float = 0.25, pre_trigger_time: float = 0.0, boot_time: float = 0.35, noise_up_time: float = 0.1,
+        noise_down_time: float = 0.01, noise_reduction_amount: float = 1.35, measure_freq: float = 20.0,
+        measure_duration: Optional[float] = None, measure_smooth_time: float = 0.4, hp_filter_freq: float = 50.0,
+        lp_filter_freq: float = 6000.0, hp_lifter_freq: float = 150.0, lp_lifter_freq: float = 2000.0) -> Tensor:
+    r"""Voice-activity detector (reference: F.vad, SoX's effect): trims the silence in front of the first speech of
+    ``(..., time)``.  As in the reference all leading dimensions are channels of ONE recording: every ``1 / measure_freq``
+    seconds each channel's last ``measure_duration`` seconds are measured (noise-reduced spectrum, cepstral power on a log
+    scale); the first channel whose smoothed measurement reaches ``trigger_level`` trims all channels at one common sample,
+    found by scanning back over ``search_time``; the result is the view ``waveform[..., start:]``, or ``waveform[..., :0]``
+    where nothing triggers.  More than 2 dimensions warn, as the reference does: a batch is not trimmed row by row
+    (use :func:`vad_start` for that).
+
+    The reference runs some two dozen small tensor operations and a host read-back per measurement and channel; here all
+    measurements of all channels take three launches and the trigger two.  The slice bound is a Python int, so the call makes
+    exactly one 8-byte device-to-host copy and therefore cannot be captured in a graph (:func:`vad_start` can).  Arithmetic is
+    float32 for every dtype, the trigger float64 and integers.  Differences from the reference: the start is clamped at 0 (the
+    reference's negative bound, where ``pre_trigger_time`` reaches before the first sample, wraps to the end of the signal);
+    the Hann windows are built on the host in float64 and rounded once, cached per (plan, device); every frame of every
+    channel is measured; a channel with a NaN sample measures 0 from there on and does not trigger; a signal of at most
+    ``measure_duration`` seconds has no measurement and never triggers.  ``ValueError`` for an empty cepstrum or spectrum
+    range and non-positive rates and times, ``TypeError`` for integer dtypes, ``NotImplementedError`` above 8192 samples per
+    measurement (the defaults up to 81.9 kHz).  Forward-only; a plain Python entry point through the C ABI (not registered as
+    a dispatcher op)."""
+    if isinstance(waveform, Tensor) and waveform.dim() > 2:
+        warnings.warn("Expected input tensor dimension of 1 for single channel or 2 for multi-channel. Got "
+                      f"{waveform.dim()} instead. All leading dimensions are treated as channels of one recording and are "
+                      "trimmed at one common sample; use audio_amd.functional.vad_start (F.vad_start) for a start per row of a "
+                      "batch.", UserWarning, stacklevel=2)
+    x2, plan = _vad_prepare(waveform, "vad", (sample_rate, trigger_level, trigger_time, search_time, allowed_gap, pre_trigger_time,
+                                             boot_time, noise_up_time, noise_down_time, noise_reduction_amount, measure_freq,
+                                             measure_duration, measure_smooth_time, hp_filter_freq, lp_filter_freq,
+                                             hp_lifter_freq, lp_lifter_freq))
+    meas = _vad_measure_rows(x2, plan)
+    _, _, joint = _vad_trigger(meas, plan.M, plan.gap, plan.P, plan.fixed, plan.level, plan.trig, joint=True)
+    start = int(joint.item())                      # the one device-to-host copy: 8 bytes
+    return waveform[..., :0] if start < 0 else waveform[..., start:]
 
 
 # --------------------------------------------------------------------------- #

@@ -35,7 +35,7 @@ _norm_mode = F._norm_mode      # `normalized` as the op schemas' integer: 0 none
 __all__ = ["Spectrogram", "InverseSpectrogram", "GriffinLim", "TimeStretch", "PitchShift", "Speed", "SpeedPerturbation",
            "MelScale", "InverseMelScale", "MelSpectrogram", "AmplitudeToDB", "MFCC", "Resample", "FFTConvolve", "ComputeDeltas",
            "SlidingWindowCmn", "FrequencyMasking", "TimeMasking", "SpecAugment", "AddNoise", "Preemphasis", "Deemphasis",
-           "Convolve", "PSD", "MVDR", "SoudenMVDR", "RTFMVDR", "RNNTLoss"]
+           "Convolve", "PSD", "MVDR", "SoudenMVDR", "RTFMVDR", "RNNTLoss", "Vad"]
 
 
 class Spectrogram(torch.nn.Module):
@@ -740,6 +740,42 @@ class AddNoise(torch.nn.Module):
 
     def forward(self, waveform: Tensor, noise: Tensor, snr: Tensor, lengths: Optional[Tensor] = None) -> Tensor:
         return F.add_noise(waveform, noise, snr, lengths)
+
+
+class Vad(torch.nn.Module):
+    r"""Voice-activity detector: trims the silence in front of the first speech (reference: T.Vad, SoX's effect); the
+    parameters, semantics and limits of :func:`audio_amd.functional.vad`.  No buffers, an empty ``state_dict``; one 8-byte
+    device-to-host copy per call (the slice bound), so not capturable in a graph; not scriptable."""
+
+    def __init__(self, sample_rate: int, trigger_level: float = 7.0, trigger_time: float = 0.25, search_time: float = 1.0,
+                 allowed_gap: float = 0.25, pre_trigger_time: float = 0.0, boot_time: float = 0.35, noise_up_time: float = 0.1,
+                 noise_down_time: float = 0.01, noise_reduction_amount: float = 1.35, measure_freq: float = 20.0,
+                 measure_duration: Optional[float] = None, measure_smooth_time: float = 0.4, hp_filter_freq: float = 50.0,
+                 lp_filter_freq: float = 6000.0, hp_lifter_freq: float = 150.0, lp_lifter_freq: float = 2000.0) -> None:
+        super().__init__()
+        self.sample_rate = sample_rate
+        self.trigger_level = trigger_level
+        self.trigger_time = trigger_time
+        self.search_time = search_time
+        self.allowed_gap = allowed_gap
+        self.pre_trigger_time = pre_trigger_time
+        self.boot_time = boot_time
+        self.noise_up_time = noise_up_time
+        self.noise_down_time = noise_down_time
+        self.noise_reduction_amount = noise_reduction_amount
+        self.measure_freq = measure_freq
+        self.measure_duration = measure_duration
+        self.measure_smooth_time = measure_smooth_time
+        self.hp_filter_freq = hp_filter_freq
+        self.lp_filter_freq = lp_filter_freq
+        self.hp_lifter_freq = hp_lifter_freq
+        self.lp_lifter_freq = lp_lifter_freq
+
+    def forward(self, waveform: Tensor) -> Tensor:
+        return F.vad(waveform, self.sample_rate, self.trigger_level, self.trigger_time, self.search_time, self.allowed_gap,
+                     self.pre_trigger_time, self.boot_time, self.noise_up_time, self.noise_down_time, self.noise_reduction_amount,
+                     self.measure_freq, self.measure_duration, self.measure_smooth_time, self.hp_filter_freq, self.lp_filter_freq,
+                     self.hp_lifter_freq, self.lp_lifter_freq)
 
 
 class Preemphasis(torch.nn.Module):

@@ -62,6 +62,8 @@
  *   aamd_flanger              gather where nothing is fed back) -- additions to ABI 7 as well
  *   aamd_ctc_beam_search      models.decoder.cuda_ctc_decoder (the reference's CUDA-only libctc_prefix_decoder); a row pass and
  *                             a beam pass, float64 scores -- an addition to ABI 7 as well
+ *   aamd_vad_measure          F.vad / F.vad_start / T.Vad (the reference's Python loop over measurements: three launches
+ *   aamd_vad_trigger          for all measurements of all rows, one or two for the trigger) -- additions to ABI 7 as well
  *   aamd_detect_pitch_f32     F.detect_pitch_frequency (_compute_nccf + _find_max_per_frame + _median_smoothing in the
  *                             reference; an addition to ABI 7 as well)
  *
@@ -830,6 +832,41 @@ int32_t aamd_inverse_mel_tiles(int32_t which);
 int aamd_inverse_mel(int32_t dtype, const void* x, const float* pinv, void* out, int64_t rows, int64_t frames,
                      int64_t stride_row, int64_t stride_mel, int64_t stride_frame, int32_t n_stft, int32_t n_mels,
                      int32_t log_input, void* stream);
+
+/* ---- Voice-activity trimming (additions to ABI 7; csrc/vad.h) --------------------------------------------------------- */
+
+#define AAMD_VAD_MAX_FFT 8192 /* the largest measurement transform the kernels serve (the defaults up to 81.9 kHz) */
+
+/* which = 0: threads per workgroup of the measurement kernels; 1: the largest transform (the define above); 2: the
+ * smallest (16); 3: rows per workgroup of the trigger kernel. */
+int32_t aamd_vad_tiles(int32_t which);
+
+/* Bytes of device workspace of aamd_vad_measure: one float per (row, frame, spectrum bin), bins = s1 - s0. */
+int64_t aamd_vad_workspace(int64_t rows, int64_t frames, int64_t bins);
+
+/* The measurements of F.vad: x is (rows, length) of `dtype` (AAMD_SA_*) with unit stride along time and row_stride elements
+ * between rows, every row a recording of its own; arithmetic is float32 for every type.  Frame f = 0 .. frames - 1 ends at
+ * sample win + f * period (frames = the count of f with win + f * period < length, checked): the magnitude spectrum of the
+ * last `win` samples (n_fft points, a power of two in [16, AAMD_VAD_MAX_FFT]; larger: AAMD_EUNSUPPORTED) over the bins
+ * [s0, s1), smoothed (f / (1 + f) while f <= boot_max, then `smooth`), reduced by noise_reduction times the tracked noise
+ * floor (`up` where the smoothed power exceeds it, else `down`), and the power of the n_fft / 2-point transform of the
+ * result over [c0, c1): meas[row][f] = max(0, 21 + log(power / (c1 - c0))), 0 unless power > 0.  tables is float[win +
+ * (s1 - s0) + n_fft] on the device: the measurement window, the cepstrum window and (cos, -sin)(2 pi k / n_fft) for
+ * k < n_fft / 2 (_host.vad_tables).  meas is dense (rows, frames).  Three launches, no atomics: two calls give the same
+ * bits. */
+int aamd_vad_measure(int32_t dtype, const void* x, int64_t rows, int64_t length, int64_t row_stride, int32_t win, int32_t n_fft,
+                     int32_t period, int32_t s0, int32_t s1, int32_t c0, int32_t c1, int32_t boot_max, double smooth, double up,
+                     double down, double noise_reduction, const float* tables, void* workspace, float* meas, int64_t frames,
+                     void* stream);
+
+/* The trigger of F.vad over dense (rows, frames) measurements (any float32 values, a NaN never triggers): first[row] = the
+ * first frame at which the float64 mean, mean = mean * trigger_mult + meas * (1 - trigger_mult), reaches trigger_level, or
+ * -1; start[row] = max(0, (first - flush) * period - fixed) with flush from the scan back over the last `ring` measurements
+ * (zeros before frame 0; `gap` measurements below the level are bridged), or -1.  joint, where not null, receives one
+ * value: the same with the least first of all rows and the largest flush, at that frame, of the rows from the least row
+ * that has it on; -1 where no row triggers.  One launch, two with joint; exact, in integers and float64. */
+int aamd_vad_trigger(const float* meas, int64_t rows, int64_t frames, int64_t ring, int64_t gap, int64_t period, int64_t fixed,
+                     double trigger_level, double trigger_mult, int64_t* first, int64_t* start, int64_t* joint, void* stream);
 
 #ifdef __cplusplus
 }

@@ -6,6 +6,7 @@ import re
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DESC = [
     (r'r0\d_.*bench_inverse_mel.*', 'tools/bench_inverse_mel.py: F.inverse_mel_scale on (256, 80, 1001) -> 201 and (32, 80, 800) -> 513, float32, time-major and frame-major inputs rotating over more than twice the Infinity Cache, beside relu(matmul(P, x)) restated in torch on the same device, both by one protocol in alternating rounds', 'DESIGN 4.18, README kernel table'),
+    (r'r0\d_.*bench_vad.*', "tools/bench_vad.py: F.vad_start on (256, 160000) float32 at 16 kHz and (8, 441000) at 44.1 kHz, inputs rotating over more than twice the Infinity Cache, beside the reference's loop over measurements and channels restated in torch on 2 rows x 20 measurements and scaled, the device time of each launch from a profiled run of its own, and one read of the waveform at 8 TB/s", 'DESIGN 4.19, README kernel table'),
     (r'r0\d_.*bench_effects.*', 'tools/bench_effects.py: F.overdrive, F.phaser and F.flanger (regen = 0 and 50) on (256, 160000) float32 beside the reference\'s per-sample loops restated in torch on 2 000 samples and scaled, and the copy floor of the streaming flanger', 'DESIGN 4.16, README kernel table'),
     (r'r0\d_.*bench_forced_align.*', 'tools/bench_forced_align.py: F.forced_align on 32 x 1500 x 32 with 200 labels and 1 x 30000 x 32 with 2000 labels, float32, beside the reference\'s per-step algorithm restated in torch, alternating rounds', 'DESIGN 4.15, README kernel table'),
     (r'r0\d_.*bench_rnnt_loss.*', 'tools/bench_rnnt_loss.py: F.rnnt_loss forward and forward + backward on 32 x 300 x 100 x 1024 and x 29 float32 beside the reference restated in torch, alternating rounds', 'DESIGN 4.14, README kernel table'),
