@@ -1227,6 +1227,18 @@ int64_t sim_gen_lds_bytes(int n_fft, int pb, int layout) {
   return (int64_t)(kgen::lds_floats_long(n_fft, pb) * sizeof(float));
 }
 
+// The generic kernels' planning functions themselves (stft_generic.h, kaldi_generic.h), for the host mirror of
+// tests/generic_census.py.  sim_plan_radices: radix[kMaxStages] out, returns the stage count or -1.
+int sim_plan_radices(int n, int* radix) { return plan_radices(n, radix); }
+int sim_gen_pairs_per_block(int n_fft) { return gen_pairs_per_block(n_fft); }
+int sim_gen_seq_len(int n_fft) { return gen_seq_len(n_fft); }
+int64_t sim_gen_lds_floats(int n_fft, int n_freq, int pb) { return (int64_t)gen_lds_floats(n_fft, n_freq, pb); }
+int64_t sim_gen_lds_floats_long(int n_fft, int pb) { return (int64_t)gen_lds_floats_long(n_fft, pb); }
+int sim_kgen_pairs_per_block(int n_fft) { return kgen::pairs_per_block(n_fft); }
+int64_t sim_kgen_lds_floats(int n_fft, int pb, int long_layout) {
+  return (int64_t)(long_layout ? kgen::lds_floats_long(n_fft, pb) : kgen::lds_floats(n_fft, pb));
+}
+
 // The launcher's chunk geometry of the banded resampler for one set of phase tiles (rsm::plan_chunk), for property tests:
 // out = {qg, rounds, n_loaders, buf_floats, waves, chunk_q}; returns 0 when even one q-group does not fit.
 int sim_rsm_plan(int orig, int new_, int width, int tap_span, int max_lo, int64_t nq, int f16, int64_t lds_cap, int* out) {

@@ -352,6 +352,31 @@ def sim_p2_fwd_blocks(E, cu_count, n_pairs):
     return int(f(E, cu_count, n_pairs))
 
 
+def sim_plan_radices(n):
+    """plan_radices itself (csrc/stft_generic.h): the list of radices, or None where the launchers refuse n."""
+    radix = (C.c_int * 16)()
+    f = sim().sim_plan_radices
+    f.argtypes, f.restype = [C.c_int, C.POINTER(C.c_int)], C.c_int
+    ns = int(f(n, radix))
+    return None if ns < 0 else [int(radix[i]) for i in range(ns)]
+
+
+def sim_generic_sizes(n_fft):
+    """The generic kernels' sizing functions themselves (csrc/stft_generic.h, csrc/kaldi_generic.h) at n_fft, in floats:
+    dict(pb, seq_len, lds_full(pb, n_freq), lds_long(pb), kaldi_pb, kaldi_full, kaldi_long)."""
+    s = sim()
+    for name, args, res in (("sim_gen_pairs_per_block", [C.c_int], C.c_int), ("sim_gen_seq_len", [C.c_int], C.c_int),
+                            ("sim_gen_lds_floats", [C.c_int] * 3, C.c_int64), ("sim_gen_lds_floats_long", [C.c_int] * 2, C.c_int64),
+                            ("sim_kgen_pairs_per_block", [C.c_int], C.c_int), ("sim_kgen_lds_floats", [C.c_int] * 3, C.c_int64)):
+        getattr(s, name).argtypes, getattr(s, name).restype = args, res
+    kpb = int(s.sim_kgen_pairs_per_block(n_fft))
+    return dict(pb=int(s.sim_gen_pairs_per_block(n_fft)), seq_len=int(s.sim_gen_seq_len(n_fft)),
+                lds_full=lambda pb, n_freq: int(s.sim_gen_lds_floats(n_fft, n_freq, pb)),
+                lds_long=lambda pb: int(s.sim_gen_lds_floats_long(n_fft, pb)),
+                kaldi_pb=kpb, kaldi_full=int(s.sim_kgen_lds_floats(n_fft, kpb, 0)),
+                kaldi_long=int(s.sim_kgen_lds_floats(n_fft, kpb, 1)))
+
+
 def sim_p2_kaldi_blocks(cu_count, n_pairs):
     """p2::kaldi_blocks itself (csrc/stft_pow2.h)."""
     f = sim().sim_p2_kaldi_blocks
