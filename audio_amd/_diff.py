@@ -438,3 +438,42 @@ def bf_rtf_power(psd_s, psd_n, reference_channel, n_iter, diagonal_loading, diag
 def bf_apply(beamform_weights: Tensor, specgram: Tensor) -> Tensor:
     return (beamform_weights.conj().transpose(-1, -2).unsqueeze(-1) * specgram).sum(-3)
 
+
+
+# ---- spectral centroid and the pointwise waveform ops: the reference's expressions as torch compositions on the device ------
+# (the training path of F.spectral_centroid, F.gain, T.Vol, F.contrast, F.DB_to_amplitude, F.mu_law_decoding and T.Fade, and
+# the float64 path of the centroid; autograd differentiates them to any order)
+
+def spectral_centroid(specgram: Tensor, freqs: Tensor) -> Tensor:
+    """(..., freq, time) magnitudes and the float32 frequency column -> (..., time)."""
+    f = freqs.to(specgram.device).reshape(-1, 1)
+    return (f * specgram).sum(dim=-2) / specgram.sum(dim=-2)
+
+
+def scale(x: Tensor, ratio: float, clamp: bool) -> Tensor:
+    y = x * ratio
+    return torch.clamp(y, -1, 1) if clamp else y
+
+
+def contrast(x: Tensor, enhancement_amount: float) -> Tensor:
+    t = x * (math.pi / 2)
+    return torch.sin(t + (enhancement_amount / 750.0) * torch.sin(t * 4))
+
+
+def db_to_amplitude(x: Tensor, ref: float, power: float) -> Tensor:
+    return ref * torch.pow(torch.pow(10.0, 0.1 * x), power)
+
+
+def mu_law_decoding(x_mu: Tensor, quantization_channels: int) -> Tensor:
+    mu = torch.tensor(quantization_channels - 1.0, dtype=x_mu.dtype, device=x_mu.device)
+    x = (x_mu / mu) * 2 - 1.0
+    return torch.sign(x) * (torch.exp(torch.abs(x) * torch.log1p(mu)) - 1.0) / mu
+
+
+def fade(x: Tensor, fade_in: Tensor, fade_out: Tensor) -> Tensor:
+    """fade_in, fade_out: the two ramps on the device, in x's dtype."""
+    n = x.shape[-1]
+    ones = x.new_ones(n)
+    fi = torch.cat([fade_in, ones[fade_in.shape[0]:]])
+    fo = torch.cat([ones[:n - fade_out.shape[0]], fade_out])
+    return (fi * fo) * x

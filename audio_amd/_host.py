@@ -787,3 +787,64 @@ def vad_tables(win: int, bins: int, n_fft: int) -> np.ndarray:
     a = 2 * math.pi * np.arange(n_fft // 2, dtype=np.float64) / n_fft
     tw = np.stack([np.cos(a), -np.sin(a)], axis=-1).reshape(-1)
     return np.concatenate([w, cw, tw]).astype(np.float32)
+
+
+# ---- linear filterbank (LFCC), the centroid's frequency table, the fade ramps -----------------------------------------------
+def linear_fbanks(n_freqs: int, f_min: float, f_max: float, n_filter: int, sample_rate: int) -> torch.Tensor:
+    """Triangular filterbank on a LINEAR frequency scale, (n_freqs, n_filter): float32 torch CPU ops in the reference's
+    order (F.linear_fbanks), so the buffer is what the reference stores in ``LFCC.filter_mat``."""
+    all_freqs = torch.linspace(0, sample_rate // 2, n_freqs)
+    f_pts = torch.linspace(f_min, f_max, n_filter + 2)
+    f_diff = f_pts[1:] - f_pts[:-1]                             # (n_filter + 1)
+    slopes = f_pts.unsqueeze(0) - all_freqs.unsqueeze(1)        # (n_freqs, n_filter + 2)
+    down_slopes = (-1.0 * slopes[:, :-2]) / f_diff[:-1]
+    up_slopes = slopes[:, 2:] / f_diff[1:]
+    return torch.max(torch.zeros(1), torch.min(down_slopes, up_slopes))
+
+
+def centroid_freqs(sample_rate: int, n_fft: int) -> np.ndarray:
+    """float32[1 + n_fft // 2]: the reference's ``torch.linspace(0, sample_rate // 2, 1 + n_fft // 2)``."""
+    return torch.linspace(0, sample_rate // 2, steps=1 + n_fft // 2).numpy()
+
+
+FADE_SHAPES = ("linear", "exponential", "logarithmic", "quarter_sine", "half_sine")
+
+
+def fade_ramps(fade_in_len: int, fade_out_len: int, fade_shape: str) -> Tuple[np.ndarray, np.ndarray]:
+    """The two ramps of T.Fade in float64: ``clamp(shape(linspace(0, 1, n)), 0, 1)`` with the reference's expressions."""
+    if fade_shape not in FADE_SHAPES:
+        raise ValueError(f"fade_shape must be one of {', '.join(FADE_SHAPES)} (got {fade_shape!r})")
+    fi = np.linspace(0.0, 1.0, int(fade_in_len))
+    fo = np.linspace(0.0, 1.0, int(fade_out_len))
+    if fade_shape == "linear":
+        fo = 1.0 - fo
+    elif fade_shape == "exponential":
+        fi, fo = np.power(2.0, fi - 1.0) * fi, np.power(2.0, -fo) * (1.0 - fo)
+    elif fade_shape == "logarithmic":
+        fi, fo = np.log10(0.1 + fi) + 1.0, np.log10(1.1 - fo) + 1.0
+    elif fade_shape == "quarter_sine":
+        fi, fo = np.sin(fi * math.pi / 2), np.sin(fo * math.pi / 2 + math.pi / 2)
+    else:
+        fi, fo = np.sin(fi * math.pi - math.pi / 2) / 2 + 0.5, np.sin(fo * math.pi + math.pi / 2) / 2 + 0.5
+    return np.clip(fi, 0.0, 1.0), np.clip(fo, 0.0, 1.0)
+
+
+def round_once(a: np.ndarray, dtype: torch.dtype) -> torch.Tensor:
+    """Finite float64 values rounded ONCE (to nearest, ties to even) to `dtype`, as a CPU tensor.  float16 and float32 are
+    numpy's direct conversions; bfloat16 goes through float32 rounded to odd, which the second rounding cannot see."""
+    a = np.ascontiguousarray(a, dtype=np.float64)
+    if dtype == torch.float64:
+        return torch.from_numpy(a.copy())
+    if dtype == torch.float32:
+        return torch.from_numpy(a.astype(np.float32))
+    if dtype == torch.float16:
+        return torch.from_numpy(a.astype(np.float16))
+    if dtype != torch.bfloat16:
+        raise TypeError(f"round_once: {dtype} is not a floating type")
+    t = a.astype(np.float32)
+    toward = np.where(t.astype(np.float64) < a, np.float32(np.inf), np.float32(-np.inf)).astype(np.float32)
+    other = np.nextafter(t, toward)
+    inexact_even = (t.astype(np.float64) != a) & ((t.view(np.uint32) & 1) == 0)
+    bits = np.where(inexact_even, other, t).astype(np.float32).view(np.uint32).astype(np.uint64)
+    bits = (bits + 0x7FFF + ((bits >> 16) & 1)) >> 16
+    return torch.from_numpy(bits.astype(np.uint16).view(np.int16).copy()).view(torch.bfloat16)

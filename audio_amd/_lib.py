@@ -205,6 +205,14 @@ _SIGS = {
     "aamd_vad_measure": (C.c_int, [C.c_int32, _P] + [C.c_int64] * 3 + [C.c_int32] * 8 + [C.c_double] * 4 + [_P, _P, _P, C.c_int64,
                                    _P]),
     "aamd_vad_trigger": (C.c_int, [_P] + [C.c_int64] * 6 + [C.c_double] * 2 + [_P] * 4),
+    # spectral centroid (additions to ABI 7)
+    "aamd_spectral_tiles": (C.c_int32, [C.c_int32]),
+    "aamd_spectral_lanes": (C.c_int32, [C.c_int64]),
+    "aamd_spectral_centroid": (C.c_int, [C.c_int32, _P, _P, _P] + [C.c_int64] * 6 + [_P]),
+    # pointwise waveform ops (additions to ABI 7)
+    "aamd_pointwise_tiles": (C.c_int32, [C.c_int32]),
+    "aamd_pointwise": (C.c_int, [C.c_int32, C.c_int32, _P, _P] + [C.c_int64] * 3 + [C.c_double, C.c_double, C.c_int32, _P,
+                                 C.c_int64, C.c_int64, _P]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS)

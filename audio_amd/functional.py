@@ -25,7 +25,7 @@ from . import _host
 from . import _lib
 from . import _shim
 from . import _diff
-from ._host import create_dct, melscale_fbanks  # noqa: F401  (re-exported, host-side constants)
+from ._host import create_dct, linear_fbanks, melscale_fbanks  # noqa: F401  (re-exported, host-side constants)
 
 __all__ = [
     "spectrogram", "inverse_spectrogram", "griffinlim", "phase_vocoder", "pitch_shift", "speed", "amplitude_to_DB", "melscale_fbanks", "create_dct", "resample",
@@ -39,6 +39,8 @@ __all__ = [
     "overdrive", "phaser", "flanger", "effects_tiles",
     "vad", "vad_start", "vad_tiles",
     "inverse_mel_scale", "inverse_mel_tiles",
+    "linear_fbanks", "spectral_centroid", "spectral_tiles",
+    "gain", "contrast", "DB_to_amplitude", "mu_law_encoding", "mu_law_decoding", "pointwise_tiles",
 ]
 
 # --------------------------------------------------------------------------- #
@@ -3882,6 +3884,260 @@ def vad(waveform: Tensor, sample_rate: int, trigger_level: float = 7.0, trigger_
     _, _, joint = _vad_trigger(meas, plan.M, plan.gap, plan.P, plan.fixed, plan.level, plan.trig, joint=True)
     start = int(joint.item())                      # the one device-to-host copy: 8 bytes
     return waveform[..., :0] if start < 0 else waveform[..., start:]
+
+
+# --------------------------------------------------------------------------- #
+# spectral centroid (csrc/spectral_feat.h)                                    #
+# --------------------------------------------------------------------------- #
+
+
+def spectral_tiles() -> Tuple[int, int, int]:
+    """(threads per workgroup, float32 values per 16-byte vector, the most lanes that share a frame line) of the centroid
+    kernel (csrc/spectral_feat.h: sf::kThreads, sf::kVec, sf::kMaxLanes)."""
+    lib = _lib.lib()
+    return int(lib.aamd_spectral_tiles(0)), int(lib.aamd_spectral_tiles(1)), int(lib.aamd_spectral_tiles(2))
+
+
+def _device_table(what: str, key, device, make) -> Tensor:
+    """A small host-built constant of `key` on `device` (``make()`` returns a CPU tensor), uploaded once and shared with the
+    effects' tables (`_FX_TABLES`).  Never allocated from a capture's pool: the first call with these parameters must run
+    eagerly."""
+    k = key + (str(device),)
+    capturing = torch.cuda.is_current_stream_capturing()
+    with _CACHE_LOCK:
+        t = _FX_PINNED.get(k)
+        if t is None:
+            t = _FX_TABLES.get(k)
+            if t is not None:
+                _FX_TABLES.move_to_end(k)
+                if capturing:
+                    _FX_PINNED[k] = t
+    if t is not None:
+        return t
+    if capturing:
+        raise RuntimeError(f"audio_amd: the {what} of these parameters is not on the device yet and cannot be built inside a "
+                           "graph capture; run the call once eagerly before capturing it")
+    t = make().to(device)
+    with _CACHE_LOCK:
+        t = _FX_TABLES.setdefault(k, t)
+        _FX_TABLES.move_to_end(k)
+        while len(_FX_TABLES) > _FX_TABLES_MAX:
+            _FX_TABLES.popitem(last=False)
+    return t
+
+
+def _centroid_freqs(sample_rate: int, n_fft: int, device) -> Tensor:
+    return _device_table("frequency table", ("centroid_freqs", int(sample_rate), int(n_fft)), device,
+                         lambda: torch.from_numpy(_host.centroid_freqs(sample_rate, n_fft)))
+
+
+def _centroid_reduce(specgram: Tensor, freqs: Tensor, out_dtype: torch.dtype = torch.float32) -> Tensor:
+    """The reduction kernel alone: float32 magnitudes ``(..., freq, time)`` in either layout (read in place through their
+    strides) and the float32 frequency table ``[freq]`` on the device -> ``(..., time)`` of `out_dtype`."""
+    if specgram.dtype != torch.float32 or freqs.dtype != torch.float32:
+        raise TypeError("audio_amd: spectral_centroid: the reduction reads float32 magnitudes and frequencies")
+    if out_dtype not in (torch.float32, torch.float16, torch.bfloat16):
+        raise TypeError(f"audio_amd: spectral_centroid: the reduction writes float32, float16 or bfloat16 (got {out_dtype})")
+    _wa_require(specgram, "spectral_centroid: specgram")
+    if specgram.dim() < 2 or freqs.dim() != 1 or freqs.shape[0] != specgram.shape[-2] or freqs.device != specgram.device:
+        raise ValueError("audio_amd: spectral_centroid: expected (..., freq, time) magnitudes and [freq] frequencies on one device")
+    lead, n_freq, frames = tuple(specgram.shape[:-2]), specgram.shape[-2], specgram.shape[-1]
+    out = torch.empty(lead + (frames,), dtype=out_dtype, device=specgram.device)
+    if out.numel() == 0:
+        return out
+    if n_freq == 0:
+        raise ValueError("audio_amd: spectral_centroid: no frequency bins")
+    rows = out.numel() // frames
+    m3 = specgram.detach().transpose(-1, -2).reshape(rows, frames, n_freq)      # a view wherever the leading strides collapse
+    if freqs.data_ptr() % 16 or not freqs.is_contiguous():
+        freqs = freqs.clone(memory_format=torch.contiguous_format)
+    with torch.cuda.device(specgram.device):
+        _lib.check(_lib.lib().aamd_spectral_centroid(_SA_DTYPES[out_dtype], m3.data_ptr(), freqs.data_ptr(), out.data_ptr(), rows,
+                                                     frames, n_freq, m3.stride(0) if rows > 1 else 0, m3.stride(1), m3.stride(2),
+                                                     _lib.current_stream(specgram.device)))
+    return out
+
+
+def spectral_centroid(waveform: Tensor, sample_rate: int, pad: int, window: Tensor, n_fft: int, hop_length: int,
+                      win_length: int) -> Tensor:
+    r"""Spectral centroid of ``(..., time)`` audio -> ``(..., time)`` frames (reference: F.spectral_centroid): the mean of the
+    frequencies ``linspace(0, sample_rate // 2, 1 + n_fft // 2)`` weighted by the magnitude spectrogram.  Two launches: the
+    magnitude spectrogram of whichever STFT family serves `n_fft`, then one reduction over its frame-major memory with
+    float64 sums in a fixed order (two calls give the same bits).  A frame of silence gives NaN (0 / 0), as in the reference.
+    float16 / bfloat16 compute in float32 and return their dtype; float64, or an input that requires grad, takes the
+    differentiable composition.  The frequency table is cached per (sample_rate, n_fft, device): run the call once eagerly
+    before capturing it in a graph.  A plain Python entry point through the C ABI (not registered as a dispatcher op)."""
+    if not isinstance(waveform, Tensor) or not isinstance(window, Tensor):
+        raise TypeError("audio_amd: spectral_centroid: waveform and window must be tensors")
+    _wa_require(waveform, "spectral_centroid: waveform")
+    if waveform.dtype == torch.float64 or _learnable(waveform, window):
+        spec = spectrogram(waveform, pad, window, n_fft, hop_length, win_length, 1.0, False)
+        return _diff.spectral_centroid(spec, torch.from_numpy(_host.centroid_freqs(sample_rate, n_fft)))
+    freqs = _centroid_freqs(sample_rate, n_fft, waveform.device)        # first: inside a capture a missing table raises here
+    spec = _spectrogram_eager(waveform.float() if waveform.dtype in LOW_PRECISION else waveform, pad, window, n_fft, hop_length,
+                              win_length, 1.0, False)                  # (..., freq, time) over frame-major memory
+    return _centroid_reduce(spec, freqs, waveform.dtype)
+
+
+# --------------------------------------------------------------------------- #
+# pointwise waveform ops (csrc/wave_pointwise.h)                              #
+# --------------------------------------------------------------------------- #
+_PW_SCALE, _PW_CONTRAST, _PW_DB_TO_AMPLITUDE, _PW_MU_ENCODE, _PW_MU_DECODE, _PW_FADE = range(6)      # AAMD_PW_*
+_PW_INTS = {torch.int64: 4, torch.int32: 5, torch.int16: 6, torch.int8: 7, torch.uint8: 8}          # AAMD_PW_I64 ..
+
+
+def pointwise_tiles() -> Tuple[int, int, int]:
+    """(threads per workgroup, samples per workgroup, 16-byte groups a thread keeps in flight) of the pointwise kernel
+    (csrc/wave_pointwise.h: pw::kThreads, pw::kChunk, pw::kBatch)."""
+    lib = _lib.lib()
+    return int(lib.aamd_pointwise_tiles(0)), int(lib.aamd_pointwise_tiles(1)), int(lib.aamd_pointwise_tiles(2))
+
+
+def _pw_check(x: Tensor, what: str, ints: bool = False) -> None:
+    """The type (TypeError); the parameter checks of an op follow, then the device (RuntimeError)."""
+    if not isinstance(x, Tensor):
+        raise TypeError(f"audio_amd: {what}: the input must be a tensor")
+    if x.dtype not in _WA_FLOATS and not (ints and x.dtype in _PW_INTS):
+        raise TypeError(f"audio_amd: {what}: the input must be float16, bfloat16, float32 or float64"
+                        f"{' or an integer tensor' if ints else ''} (got {x.dtype})")
+
+
+def _pw_grad(x: Tensor) -> bool:
+    return x.requires_grad and torch.is_grad_enabled()
+
+
+def _pw_launch(op: int, x: Tensor, out_dtype: torch.dtype, p0: float = 0.0, p1: float = 0.0, flag: int = 0,
+               table: Optional[Tensor] = None, n_in: int = 0, n_out: int = 0) -> Tensor:
+    """One launch of the pointwise kernel over `x` read in place (rows of a wider tensor through one row stride; a non-unit
+    sample stride is gathered first) into a new contiguous tensor."""
+    out = torch.empty(tuple(x.shape), dtype=out_dtype, device=x.device)
+    if out.numel() == 0:
+        return out
+    x1 = x.detach().reshape(1) if x.dim() == 0 else x.detach()
+    x2 = _wa_rows(x1, tuple(x1.shape[:-1]), x1.shape[-1])
+    code = _SA_DTYPES[x.dtype] if x.dtype in _SA_DTYPES else _PW_INTS[x.dtype]
+    with torch.cuda.device(x.device):
+        _lib.check(_lib.lib().aamd_pointwise(op, code, x2.data_ptr(), out.data_ptr(), x2.shape[0], x2.shape[1], _wa_stride(x2),
+                                             float(p0), float(p1), int(flag), 0 if table is None else table.data_ptr(),
+                                             int(n_in), int(n_out), _lib.current_stream(x.device)))
+    return out
+
+
+def _scale(waveform: Tensor, ratio: float, clamp: bool, what: str) -> Tensor:
+    """``waveform * ratio`` (ratio rounded once to the compute type), clamped to [-1, 1] where asked: one launch."""
+    _wa_require(waveform, f"{what}: waveform")
+    if _pw_grad(waveform):
+        return _diff.scale(waveform, ratio, clamp)
+    return _pw_launch(_PW_SCALE, waveform, waveform.dtype, ratio, 0.0, int(clamp))
+
+
+def gain(waveform: Tensor, gain_db: float = 1.0) -> Tensor:
+    r"""Apply amplification or attenuation to the whole waveform (reference: F.gain): ``waveform * 10 ** (gain_db / 20)``,
+    the ratio a Python double rounded once to the compute type, so float32 and float64 results are bit-exact against numpy.
+    ``gain_db == 0`` returns the input object.  One launch; float16 / bfloat16 compute in float32; an input that requires
+    grad takes the torch expression.  A plain Python entry point through the C ABI."""
+    if gain_db == 0:
+        return waveform
+    _pw_check(waveform, "gain")
+    return _scale(waveform, 10 ** (gain_db / 20), False, "gain")
+
+
+def _vol(waveform: Tensor, gain: float, gain_type: str) -> Tensor:
+    """T.Vol.forward: the gain of its type and the clamp to [-1, 1] in one launch."""
+    _pw_check(waveform, "Vol")
+    if gain_type == "amplitude":
+        ratio = float(gain)
+    elif gain_type == "db":
+        ratio = 10 ** (gain / 20)
+    elif gain_type == "power":
+        ratio = 10 ** ((10 * math.log10(gain)) / 20)
+    else:
+        raise ValueError(f"gain_type must be one of amplitude, power or db (got {gain_type!r})")
+    return _scale(waveform, ratio, True, "Vol")
+
+
+def contrast(waveform: Tensor, enhancement_amount: float = 75.0) -> Tensor:
+    r"""Contrast enhancement (reference: F.contrast, SoX's effect): ``t = waveform * (pi / 2)``,
+    ``sin(t + enhancement_amount / 750 * sin(t * 4))``, with the accurate ``sin``.  One launch; float16 / bfloat16 compute in
+    float32; an input that requires grad takes the torch expression.  A plain Python entry point through the C ABI."""
+    _pw_check(waveform, "contrast")
+    if not 0 <= enhancement_amount <= 100:
+        raise ValueError("Allowed range of values for enhancement_amount : 0-100")
+    _wa_require(waveform, "contrast: waveform")
+    if _pw_grad(waveform):
+        return _diff.contrast(waveform, float(enhancement_amount))
+    return _pw_launch(_PW_CONTRAST, waveform, waveform.dtype, math.pi / 2, enhancement_amount / 750.0)
+
+
+def DB_to_amplitude(x: Tensor, ref: float, power: float) -> Tensor:
+    r"""Decibels back to power or amplitude (reference: F.DB_to_amplitude): ``ref * pow(pow(10, 0.1 * x), power)`` with the
+    accurate ``pow``.  One launch; float16 / bfloat16 compute in float32; an input that requires grad takes the torch
+    expression.  A plain Python entry point through the C ABI."""
+    _pw_check(x, "DB_to_amplitude")
+    _wa_require(x, "DB_to_amplitude: x")
+    if _pw_grad(x):
+        return _diff.db_to_amplitude(x, float(ref), float(power))
+    return _pw_launch(_PW_DB_TO_AMPLITUDE, x, x.dtype, float(ref), float(power))
+
+
+def _mu_channels(quantization_channels: int) -> float:
+    if not isinstance(quantization_channels, int) or isinstance(quantization_channels, bool) or quantization_channels < 2:
+        raise ValueError(f"quantization_channels must be an integer of at least 2 (got {quantization_channels!r})")
+    return quantization_channels - 1.0
+
+
+def mu_law_encoding(x: Tensor, quantization_channels: int) -> Tensor:
+    r"""Mu-law companding (reference: F.mu_law_encoding): a signal in [-1, 1] -> int64 codes in [0, quantization_channels - 1],
+    ``int64((sign(x) log1p(mu |x|) / log1p(mu) + 1) / 2 * mu + 0.5)`` with ``mu = quantization_channels - 1``.  An integer
+    input is converted to float32 with the reference's warning.  One launch; float16 / bfloat16 compute in float32; no
+    gradient (the result is integer).  A plain Python entry point through the C ABI."""
+    _pw_check(x, "mu_law_encoding", ints=True)
+    mu = _mu_channels(quantization_channels)
+    _wa_require(x, "mu_law_encoding: x", floating=False)
+    if not x.is_floating_point():
+        warnings.warn("The input Tensor must be of floating type. This will be an error in the v0.12 release.")
+        x = x.to(torch.float)
+    return _pw_launch(_PW_MU_ENCODE, x, torch.int64, mu)
+
+
+def mu_law_decoding(x_mu: Tensor, quantization_channels: int) -> Tensor:
+    r"""Mu-law expansion (reference: F.mu_law_decoding): codes in [0, quantization_channels - 1] -> a signal in [-1, 1],
+    ``y = x_mu / mu * 2 - 1``, ``sign(y) (exp(|y| log1p(mu)) - 1) / mu``.  Integer codes of any integer dtype are read as
+    they are and give float32; a floating input keeps its dtype.  One launch; an input that requires grad takes the torch
+    expression.  A plain Python entry point through the C ABI."""
+    _pw_check(x_mu, "mu_law_decoding", ints=True)
+    mu = _mu_channels(quantization_channels)
+    _wa_require(x_mu, "mu_law_decoding: x_mu", floating=False)
+    if _pw_grad(x_mu):
+        return _diff.mu_law_decoding(x_mu, quantization_channels)
+    return _pw_launch(_PW_MU_DECODE, x_mu, x_mu.dtype if x_mu.is_floating_point() else torch.float32, mu)
+
+
+def _fade(waveform: Tensor, fade_in_len: int, fade_out_len: int, fade_shape: str) -> Tensor:
+    """T.Fade.forward: ``(fade_in * fade_out) * waveform`` along the last axis.  The two ramps are built on the host in float64,
+    rounded once to the waveform's dtype and cached per (parameters, dtype, device); the kernel multiplies inside the ramps
+    and copies bits elsewhere."""
+    _pw_check(waveform, "Fade")
+    if fade_shape not in _host.FADE_SHAPES:
+        raise ValueError(f"fade_shape must be one of {', '.join(_host.FADE_SHAPES)} (got {fade_shape!r})")
+    n_in, n_out = int(fade_in_len), int(fade_out_len)
+    if n_in < 0 or n_out < 0:
+        raise ValueError("fade_in_len and fade_out_len must not be negative")
+    if waveform.dim() < 1:
+        raise ValueError("audio_amd: Fade expects (..., time), got a 0-dimensional tensor")
+    length = waveform.shape[-1]
+    if n_in > length or n_out > length:
+        raise ValueError(f"a fade ({n_in} in, {n_out} out) is longer than the signal ({length} samples)")
+    _wa_require(waveform, "Fade: waveform")
+    if n_in + n_out == 0:
+        table = None
+    else:
+        table = _device_table("fade table", ("fade", n_in, n_out, fade_shape, str(waveform.dtype)), waveform.device,
+                              lambda: _host.round_once(np.concatenate(_host.fade_ramps(n_in, n_out, fade_shape)), waveform.dtype))
+    if _pw_grad(waveform):
+        ramps = waveform.new_zeros(0) if table is None else table
+        return _diff.fade(waveform, ramps[:n_in], ramps[n_in:])
+    return _pw_launch(_PW_FADE, waveform, waveform.dtype, table=table, n_in=n_in, n_out=n_out)
 
 
 # --------------------------------------------------------------------------- #

@@ -1,7 +1,7 @@
 """Drop-in replacements for the hot-path modules of ``torchaudio.transforms``:
 Spectrogram, MelScale, MelSpectrogram, AmplitudeToDB, MFCC, Resample, FFTConvolve, ComputeDeltas, SlidingWindowCmn,
 FrequencyMasking, TimeMasking, SpecAugment, AddNoise, Preemphasis, Deemphasis, Convolve, PSD, MVDR, SoudenMVDR, RTFMVDR,
-RNNTLoss.
+RNNTLoss, Vad, LFCC, SpectralCentroid, MuLawEncoding, MuLawDecoding, Fade, Vol.
 
 Constructor / forward signatures, registered buffer names (``window``, ``fb``, ``dct_mat``,
 ``kernel``), shapes, strides, warnings and error messages follow
@@ -35,7 +35,8 @@ _norm_mode = F._norm_mode      # `normalized` as the op schemas' integer: 0 none
 __all__ = ["Spectrogram", "InverseSpectrogram", "GriffinLim", "TimeStretch", "PitchShift", "Speed", "SpeedPerturbation",
            "MelScale", "InverseMelScale", "MelSpectrogram", "AmplitudeToDB", "MFCC", "Resample", "FFTConvolve", "ComputeDeltas",
            "SlidingWindowCmn", "FrequencyMasking", "TimeMasking", "SpecAugment", "AddNoise", "Preemphasis", "Deemphasis",
-           "Convolve", "PSD", "MVDR", "SoudenMVDR", "RTFMVDR", "RNNTLoss", "Vad"]
+           "Convolve", "PSD", "MVDR", "SoudenMVDR", "RTFMVDR", "RNNTLoss", "Vad", "LFCC", "SpectralCentroid", "MuLawEncoding",
+           "MuLawDecoding", "Fade", "Vol"]
 
 
 class Spectrogram(torch.nn.Module):
@@ -776,6 +777,150 @@ class Vad(torch.nn.Module):
                      self.pre_trigger_time, self.boot_time, self.noise_up_time, self.noise_down_time, self.noise_reduction_amount,
                      self.measure_freq, self.measure_duration, self.measure_smooth_time, self.hp_filter_freq, self.lp_filter_freq,
                      self.hp_lifter_freq, self.lp_lifter_freq)
+
+
+class LFCC(torch.nn.Module):
+    r"""Linear-frequency cepstral coefficients (reference: T.LFCC): the spectrogram through a filterbank that is triangular
+    on a LINEAR frequency scale (buffer ``filter_mat``), then dB (+ top_db = 80 with the reference's grouping of the
+    cut-off) or ``log(x + 1e-6)``, then the DCT-II (buffer ``dct_mat``).  The exact two-kernel path of :class:`MFCC` with
+    ``filter_mat`` in place of the mel filterbank: float64, gradients, half precision and learnable buffers as there.  Not
+    registered as a dispatcher op (not scriptable as one op)."""
+    __constants__ = ["sample_rate", "n_filter", "n_lfcc", "dct_type", "top_db", "log_lf"]
+
+    def __init__(
+        self,
+        sample_rate: int = 16000,
+        n_filter: int = 128,
+        f_min: float = 0.0,
+        f_max: Optional[float] = None,
+        n_lfcc: int = 40,
+        dct_type: int = 2,
+        norm: str = "ortho",
+        log_lf: bool = False,
+        speckwargs: Optional[dict] = None,
+    ) -> None:
+        super().__init__()
+        supported_dct_types = [2]
+        if dct_type not in supported_dct_types:
+            raise ValueError("DCT type not supported: {}".format(dct_type))
+        self.sample_rate = sample_rate
+        self.f_min = f_min
+        self.f_max = f_max if f_max is not None else float(sample_rate // 2)
+        self.n_filter = n_filter
+        self.n_lfcc = n_lfcc
+        self.dct_type = dct_type
+        self.norm = norm
+        self.top_db = 80.0
+        self.amplitude_to_DB = AmplitudeToDB("power", self.top_db)
+        speckwargs = speckwargs or {}
+        self.Spectrogram = Spectrogram(**speckwargs)
+        if self.n_lfcc > self.Spectrogram.n_fft:
+            raise ValueError("Cannot select more LFCC coefficients than # fft bins")
+        filter_mat = F.linear_fbanks(n_freqs=self.Spectrogram.n_fft // 2 + 1, f_min=self.f_min, f_max=self.f_max,
+                                     n_filter=self.n_filter, sample_rate=self.sample_rate)
+        self.register_buffer("filter_mat", filter_mat)
+        dct_mat = F.create_dct(self.n_lfcc, self.n_filter, self.norm)
+        self.register_buffer("dct_mat", dct_mat)
+        self.log_lf = log_lf
+        self._plans: dict = {}      # launch plans of the filterbank kernel (see MelSpectrogram)
+
+    def __getstate__(self):
+        state = dict(self.__dict__)
+        state["_plans"] = {}
+        return state
+
+    def forward(self, waveform: Tensor) -> Tensor:
+        sp, a2db = self.Spectrogram, self.amplitude_to_DB
+        return F._mfcc_module(waveform, sp.window, self.filter_mat, self.dct_mat, sp.pad, sp.n_fft, sp.hop_length,
+                              sp.win_length, sp.power, sp.normalized, sp.center, sp.pad_mode, self.log_lf, self.top_db,
+                              (a2db.multiplier, a2db.amin, a2db.db_multiplier), 0, None, None, self._plans)
+
+
+class SpectralCentroid(torch.nn.Module):
+    r"""Spectral centroid per frame, ``(..., time) -> (..., frames)`` (reference: T.SpectralCentroid); one buffer,
+    ``window``; the launches and limits of :func:`audio_amd.functional.spectral_centroid`."""
+    __constants__ = ["sample_rate", "n_fft", "win_length", "hop_length", "pad"]
+
+    def __init__(
+        self,
+        sample_rate: int,
+        n_fft: int = 400,
+        win_length: Optional[int] = None,
+        hop_length: Optional[int] = None,
+        pad: int = 0,
+        window_fn: Callable[..., Tensor] = torch.hann_window,
+        wkwargs: Optional[dict] = None,
+    ) -> None:
+        super().__init__()
+        self.sample_rate = sample_rate
+        self.n_fft = n_fft
+        self.win_length = win_length if win_length is not None else n_fft
+        self.hop_length = hop_length if hop_length is not None else self.win_length // 2
+        window = window_fn(self.win_length) if wkwargs is None else window_fn(self.win_length, **wkwargs)
+        self.register_buffer("window", window)
+        self.pad = pad
+
+    def forward(self, waveform: Tensor) -> Tensor:
+        return F.spectral_centroid(waveform, self.sample_rate, self.pad, self.window, self.n_fft, self.hop_length,
+                                   self.win_length)
+
+
+class MuLawEncoding(torch.nn.Module):
+    r"""Mu-law companding of a signal in [-1, 1] into int64 codes (reference: T.MuLawEncoding); no buffers."""
+    __constants__ = ["quantization_channels"]
+
+    def __init__(self, quantization_channels: int = 256) -> None:
+        super().__init__()
+        self.quantization_channels = quantization_channels
+
+    def forward(self, x: Tensor) -> Tensor:
+        return F.mu_law_encoding(x, self.quantization_channels)
+
+
+class MuLawDecoding(torch.nn.Module):
+    r"""Mu-law codes back to a signal in [-1, 1] (reference: T.MuLawDecoding); no buffers."""
+    __constants__ = ["quantization_channels"]
+
+    def __init__(self, quantization_channels: int = 256) -> None:
+        super().__init__()
+        self.quantization_channels = quantization_channels
+
+    def forward(self, x_mu: Tensor) -> Tensor:
+        return F.mu_law_decoding(x_mu, self.quantization_channels)
+
+
+class Fade(torch.nn.Module):
+    r"""Fade in and / or out along the last axis (reference: T.Fade): ``(fade_in * fade_out) * waveform`` with ramps of shape
+    "linear", "exponential", "logarithmic", "quarter_sine" or "half_sine".  The ramps are host tables (float64, rounded once
+    to the waveform's dtype, cached per parameters, dtype and device: run the call once eagerly before capturing it in a
+    graph); one launch that multiplies inside the ramps and copies bits elsewhere.  A fade longer than the signal raises
+    ``ValueError`` (the reference fails in ``torch.ones`` with a negative size).  No buffers."""
+
+    def __init__(self, fade_in_len: int = 0, fade_out_len: int = 0, fade_shape: str = "linear") -> None:
+        super().__init__()
+        if fade_shape not in _host.FADE_SHAPES:
+            raise ValueError(f"fade_shape must be one of {', '.join(_host.FADE_SHAPES)} (got {fade_shape!r})")
+        self.fade_in_len = fade_in_len
+        self.fade_out_len = fade_out_len
+        self.fade_shape = fade_shape
+
+    def forward(self, waveform: Tensor) -> Tensor:
+        return F._fade(waveform, self.fade_in_len, self.fade_out_len, self.fade_shape)
+
+
+class Vol(torch.nn.Module):
+    r"""Adjust the volume and clamp to [-1, 1] (reference: T.Vol): ``gain_type`` "amplitude" multiplies by ``gain``, "db" is
+    ``F.gain(x, gain)``, "power" is ``F.gain(x, 10 * log10(gain))``; the product and the clamp share one launch."""
+
+    def __init__(self, gain: float, gain_type: str = "amplitude") -> None:
+        super().__init__()
+        self.gain = gain
+        self.gain_type = gain_type
+        if gain_type in ["amplitude", "power"] and gain < 0:
+            raise ValueError("If gain_type = amplitude or power, gain must be positive.")
+
+    def forward(self, waveform: Tensor) -> Tensor:
+        return F._vol(waveform, self.gain, self.gain_type)
 
 
 class Preemphasis(torch.nn.Module):

@@ -868,6 +868,50 @@ int aamd_vad_measure(int32_t dtype, const void* x, int64_t rows, int64_t length,
 int aamd_vad_trigger(const float* meas, int64_t rows, int64_t frames, int64_t ring, int64_t gap, int64_t period, int64_t fixed,
                      double trigger_level, double trigger_mult, int64_t* first, int64_t* start, int64_t* joint, void* stream);
 
+/* ---- Spectral centroid (additions to ABI 7; csrc/spectral_feat.h) ---------------------------------------------------- */
+
+/* which = 0: threads per workgroup; 1: float32 values per 16-byte vector; 2: the most lanes that share a frame line. */
+int32_t aamd_spectral_tiles(int32_t which);
+
+/* Lanes that share a frame line of n_freq bins with unit stride along frequency: the power of two that leaves a lane about
+ * four 16-byte vectors (it covers ceil(ceil(n_freq / 4) / 4)), at most 64; 0 for n_freq < 1. */
+int32_t aamd_spectral_lanes(int64_t n_freq);
+
+/* The reduction of F.spectral_centroid: out[r][t] = sum_k freqs[k] mag[r][t][k] / sum_k mag[r][t][k].  mag is float32
+ * (rows, frames, n_freq) read in place through its strides in elements (any non-negative strides; unit stride along
+ * frequency takes 16-byte loads, several lanes per frame line); freqs is float32[n_freq] on the device, 16-byte aligned;
+ * out is dense (rows, frames) of out_dtype (AAMD_SA_F32 / F16 / BF16).  Both sums are float64, each lane adds its bins in
+ * ascending order and the lanes of a frame combine in one fixed tree, then one float64 division and one rounding.  A frame
+ * of zeros gives NaN.  One launch, no atomics: two calls give the same bits. */
+int aamd_spectral_centroid(int32_t out_dtype, const float* mag, const float* freqs, void* out, int64_t rows, int64_t frames,
+                           int64_t n_freq, int64_t stride_row, int64_t stride_frame, int64_t stride_freq, void* stream);
+
+/* ---- Pointwise waveform ops (additions to ABI 7; csrc/wave_pointwise.h) ---------------------------------------------- */
+
+enum { AAMD_PW_SCALE = 0, AAMD_PW_CONTRAST = 1, AAMD_PW_DB_TO_AMPLITUDE = 2, AAMD_PW_MU_ENCODE = 3, AAMD_PW_MU_DECODE = 4,
+       AAMD_PW_FADE = 5 };
+/* element types beyond AAMD_SA_*: the integer codes AAMD_PW_MU_DECODE reads */
+enum { AAMD_PW_I64 = 4, AAMD_PW_I32 = 5, AAMD_PW_I16 = 6, AAMD_PW_I8 = 7, AAMD_PW_U8 = 8 };
+
+/* which = 0: threads per workgroup; 1: samples per workgroup; 2: 16-byte groups a thread keeps in flight. */
+int32_t aamd_pointwise_tiles(int32_t which);
+
+/* One streaming pass over x, (rows, length) of `dtype` with unit stride along time and row_stride elements between rows,
+ * into dense out.  float32 and float64 compute in their own precision; float16 and bfloat16 in float32, rounded once.
+ *   AAMD_PW_SCALE            out = x * p0, clamped to [-1, 1] where flag != 0                  (F.gain, T.Vol)
+ *   AAMD_PW_CONTRAST         t = x * p0; out = sin(t + p1 * sin(t * 4))                        (F.contrast: p0 = pi / 2)
+ *   AAMD_PW_DB_TO_AMPLITUDE  out = p0 * pow(pow(10, 0.1 * x), p1)                              (p0 = ref, p1 = power)
+ *   AAMD_PW_MU_ENCODE        v = sign(x) log1p(p0 |x|) / log1p(p0); out = int64((v + 1) / 2 * p0 + 0.5), toward zero;
+ *                            out is int64 for every dtype (p0 = quantization_channels - 1 >= 1)
+ *   AAMD_PW_MU_DECODE        y = x / p0 * 2 - 1; out = sign(y) (exp(|y| log1p(p0)) - 1) / p0; dtype may be AAMD_PW_I64 ..
+ *                            AAMD_PW_U8: the codes are read as they are and out is float32
+ *   AAMD_PW_FADE             out = (fade_in * fade_out) * x: table holds the fade-in ramp (n_in values) and the fade-out
+ *                            ramp (n_out values, the last n_out samples of a row) in `dtype`, n_in, n_out <= length;
+ *                            a sample outside both ramps is copied bit for bit
+ * table, n_in and n_out are read by AAMD_PW_FADE only.  One launch. */
+int aamd_pointwise(int32_t op, int32_t dtype, const void* x, void* out, int64_t rows, int64_t length, int64_t row_stride,
+                   double p0, double p1, int32_t flag, const void* table, int64_t n_in, int64_t n_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
