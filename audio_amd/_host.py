@@ -848,3 +848,42 @@ def round_once(a: np.ndarray, dtype: torch.dtype) -> torch.Tensor:
     bits = np.where(inexact_even, other, t).astype(np.float32).view(np.uint32).astype(np.uint64)
     bits = (bits + 0x7FFF + ((bits >> 16) & 1)) >> 16
     return torch.from_numpy(bits.astype(np.uint16).view(np.int16).copy()).view(torch.bfloat16)
+
+
+# ---- image-source room impulse responses (csrc/rir.h): the image lattice and the size bookkeeping of the default length --------
+def rir_image_count(max_order: int, D: int) -> int:
+    n = int(max_order)
+    return 2 * n * n + 2 * n + 1 if D == 2 else (2 * n + 1) * (2 * n * n + 2 * n + 3) // 3
+
+
+def rir_lattice(max_order: int, D: int) -> np.ndarray:
+    """int16 (n_img, D): every integer vector ``v`` in ``[-max_order, max_order]^D`` with ``sum |v_d| <= max_order``, in the
+    order of ``cartesian_prod`` (last axis fastest)."""
+    if D not in (2, 3) or max_order < 0 or max_order > 16000:
+        raise ValueError("rir_lattice: need D in {2, 3} and 0 <= max_order <= 16000")
+    r = np.arange(-max_order, max_order + 1, dtype=np.int64)
+    grid = np.stack(np.meshgrid(*([r] * D), indexing="ij"), axis=-1).reshape(-1, D)
+    v = grid[np.abs(grid).sum(axis=1) <= max_order]
+    assert v.shape[0] == rir_image_count(max_order, D)
+    return np.ascontiguousarray(v.astype(np.int16))
+
+
+def rir_length(room, source, mic_array, max_order: int, sample_rate: float = 16000.0, sound_speed: float = 343.0,
+               delay_filter_length: int = 81) -> int:
+    """``ceil(max tau) + delay_filter_length`` of the definition for one room -- room (D,), source (D,), mic_array (M, D) as
+    STORED (float32 values are widened) -- in numpy float64 with the kernel's order of operations: the squares of
+    ``loc - mic`` added axis by axis, ``tau = sqrt(d2) * sample_rate / sound_speed`` left to right.  Raises ValueError when the
+    largest delay is not finite."""
+    room, source, mic = (np.asarray(t, dtype=np.float64) for t in (room, source, mic_array))
+    v = rir_lattice(max_order, room.shape[0]).astype(np.int64)
+    d2 = np.zeros((v.shape[0], mic.shape[0]), np.float64)
+    for d in range(room.shape[0]):
+        vd = v[:, d]
+        loc = np.where(vd % 2 == 1, room[d] * (vd + 1).astype(np.float64) - source[d], room[d] * vd.astype(np.float64) + source[d])
+        diff = loc[:, None] - mic[None, :, d]
+        d2 = d2 + diff * diff
+    tau = np.sqrt(d2) * np.float64(sample_rate) / np.float64(sound_speed)
+    top = tau.max() if tau.size else np.float64(0.0)
+    if not np.isfinite(top) or top >= 2.0 ** 31:
+        raise ValueError("audio_amd: simulate_rir_ism: the largest delay is not finite (or beyond 2^31 samples); pass output_length")
+    return int(np.ceil(top)) + int(delay_filter_length)

@@ -213,6 +213,10 @@ _SIGS = {
     "aamd_pointwise_tiles": (C.c_int32, [C.c_int32]),
     "aamd_pointwise": (C.c_int, [C.c_int32, C.c_int32, _P, _P] + [C.c_int64] * 3 + [C.c_double, C.c_double, C.c_int32, _P,
                                  C.c_int64, C.c_int64, _P]),
+    # image-source room impulse responses (additions to ABI 7)
+    "aamd_rir_tiles": (C.c_int32, [C.c_int32]),
+    "aamd_simulate_rir": (C.c_int, [C.c_int32] + [_P] * 5 + [C.c_int64, _P, C.c_int64, C.c_int64] + [C.c_int32] * 3 +
+                          [C.c_int64, C.c_double, C.c_double, _P]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS)

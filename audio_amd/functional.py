@@ -41,6 +41,7 @@ __all__ = [
     "inverse_mel_scale", "inverse_mel_tiles",
     "linear_fbanks", "spectral_centroid", "spectral_tiles",
     "gain", "contrast", "DB_to_amplitude", "mu_law_encoding", "mu_law_decoding", "pointwise_tiles",
+    "simulate_rir_ism", "simulate_rir_ism_batch", "rir_tiles",
 ]
 
 # --------------------------------------------------------------------------- #
@@ -4138,6 +4139,198 @@ def _fade(waveform: Tensor, fade_in_len: int, fade_out_len: int, fade_shape: str
         ramps = waveform.new_zeros(0) if table is None else table
         return _diff.fade(waveform, ramps[:n_in], ramps[n_in:])
     return _pw_launch(_PW_FADE, waveform, waveform.dtype, table=table, n_in=n_in, n_out=n_out)
+
+
+# --------------------------------------------------------------------------- #
+# image-source room impulse responses (csrc/rir.h)                            #
+# --------------------------------------------------------------------------- #
+RIR_MAX_FILTER = 1025                # AAMD_RIR_MAX_FILTER: the longest delay filter (taps) the kernel serves
+RIR_MAX_ORDER = 64                   # AAMD_RIR_MAX_ORDER: the largest reflection order (357 889 images in 3-D)
+_RIR_TABLES: "collections.OrderedDict" = collections.OrderedDict()   # (max_order, D, device) -> int16 lattice, LRU
+_RIR_PINNED: dict = {}               # tables a captured graph reads: kept for the life of the process
+_RIR_TABLES_MAX = 16
+
+
+def rir_tiles() -> Tuple[int, int, int, int]:
+    """(samples per workgroup, images per chunk, the largest delay_filter_length, the largest max_order) of csrc/rir.h:
+    rir::kTile, kChunk, kMaxFl, kMaxOrder."""
+    lib = _lib.lib()
+    return tuple(int(lib.aamd_rir_tiles(i)) for i in range(4))
+
+
+def _rir_lattice(max_order: int, D: int, device) -> Tensor:
+    """The image lattice of (max_order, D) on `device`: built on the host and uploaded once.  Never allocated from a capture's
+    pool: the first call with this (max_order, D) must run eagerly."""
+    k = (max_order, D, str(device))
+    capturing = torch.cuda.is_current_stream_capturing()
+    with _CACHE_LOCK:
+        t = _RIR_PINNED.get(k)
+        if t is None:
+            t = _RIR_TABLES.get(k)
+            if t is not None:
+                _RIR_TABLES.move_to_end(k)
+                if capturing:
+                    _RIR_PINNED[k] = t
+    if t is not None:
+        return t
+    if capturing:
+        raise RuntimeError("audio_amd: the image lattice of this max_order is not on the device yet and cannot be built inside "
+                           "a graph capture; run the call once eagerly before capturing it")
+    t = torch.from_numpy(_host.rir_lattice(max_order, D)).to(device)
+    with _CACHE_LOCK:
+        t = _RIR_TABLES.setdefault(k, t)
+        _RIR_TABLES.move_to_end(k)
+        while len(_RIR_TABLES) > _RIR_TABLES_MAX:
+            _RIR_TABLES.popitem(last=False)
+    return t
+
+
+def _rir_check(what: str, room, source, mic_array, batched: bool, max_order, delay_filter_length, output_length,
+               sample_rate, sound_speed) -> int:
+    """The checks that need no device, in the order ranks, sizes, dtypes, parameters, limits; returns D."""
+    lead = 1 if batched else 0
+    for name, t, rank in (("room", room, lead + 1), ("source", source, lead + 1), ("mic_array", mic_array, lead + 2)):
+        if not isinstance(t, Tensor):
+            raise TypeError(f"audio_amd: {what}: {name} must be a tensor")
+        if t.dim() != rank:
+            raise ValueError(f"audio_amd: {what}: {name} must have {rank} dimensions (got {t.dim()})")
+    D = room.shape[-1]
+    if D not in (2, 3):
+        raise ValueError(f"audio_amd: {what}: room must have 2 or 3 coordinates (got {D})")
+    if source.shape[-1] != D or mic_array.shape[-1] != D:
+        raise ValueError(f"audio_amd: {what}: room, source and mic_array must have the same number of coordinates (got {D}, "
+                         f"{source.shape[-1]}, {mic_array.shape[-1]})")
+    if batched and not (room.shape[0] == source.shape[0] == mic_array.shape[0]):
+        raise ValueError(f"audio_amd: {what}: room, source and mic_array must have the same number of rooms (got "
+                         f"{room.shape[0]}, {source.shape[0]}, {mic_array.shape[0]})")
+    if room.dtype not in (torch.float32, torch.float64):
+        raise TypeError(f"audio_amd: {what}: room must be float32 or float64 (got {room.dtype})")
+    if source.dtype != room.dtype or mic_array.dtype != room.dtype:
+        raise TypeError(f"audio_amd: {what}: room, source and mic_array must have one dtype (got {room.dtype}, {source.dtype}, "
+                        f"{mic_array.dtype})")
+    for name, v in (("max_order", max_order), ("delay_filter_length", delay_filter_length)):
+        if isinstance(v, bool) or not isinstance(v, int):
+            raise TypeError(f"audio_amd: {what}: {name} must be an int (got {v!r})")
+    if max_order < 0:
+        raise ValueError(f"audio_amd: {what}: max_order must not be negative (got {max_order})")
+    if delay_filter_length < 3 or delay_filter_length % 2 == 0:
+        raise ValueError(f"audio_amd: {what}: delay_filter_length must be odd and at least 3 (got {delay_filter_length})")
+    if output_length is not None:
+        if isinstance(output_length, bool) or not isinstance(output_length, int):
+            raise TypeError(f"audio_amd: {what}: output_length must be an int (got {output_length!r})")
+        if output_length < 1:
+            raise ValueError(f"audio_amd: {what}: output_length must be at least 1 (got {output_length})")
+    for name, v in (("sample_rate", sample_rate), ("sound_speed", sound_speed)):
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v) or not v > 0:
+            raise ValueError(f"audio_amd: {what}: {name} must be a positive finite number (got {v!r})")
+    if delay_filter_length > RIR_MAX_FILTER:
+        raise NotImplementedError(f"audio_amd: {what} serves delay filters up to {RIR_MAX_FILTER} taps (got {delay_filter_length})")
+    if max_order > RIR_MAX_ORDER:
+        raise NotImplementedError(f"audio_amd: {what} serves max_order up to {RIR_MAX_ORDER} (got {max_order})")
+    return D
+
+
+def _rir_absorption(what: str, absorption, B: int, D: int, like: Tensor, batched: bool) -> Tensor:
+    """Dense (B, 2 D) of `like`'s dtype on its device, from a float, (B,) / (B, 2 D) (batched) or (2 D,) / (1, 2 D)."""
+    if isinstance(absorption, Tensor):
+        a = absorption
+        if a.dtype != like.dtype:
+            raise TypeError(f"audio_amd: {what}: absorption must have the dtype of room ({like.dtype}; got {a.dtype})")
+        if not batched:
+            if a.dim() == 2 and a.shape[0] > 1:
+                raise NotImplementedError(f"audio_amd: {what}: a multi-band absorption of shape {tuple(a.shape)} needs the "
+                                          "reference's octave-band filter bank, which is not implemented; pass one band")
+            if a.dim() not in (1, 2) or a.shape[-1] != 2 * D:
+                raise ValueError(f"audio_amd: {what}: absorption must be a float, ({2 * D},) or (1, {2 * D}) (got {tuple(a.shape)})")
+            a = a.reshape(1, 2 * D)
+        elif a.dim() == 1 and a.shape[0] == B:
+            a = a.unsqueeze(1).expand(B, 2 * D)
+        elif a.dim() != 2 or tuple(a.shape) != (B, 2 * D):
+            raise ValueError(f"audio_amd: {what}: absorption must be a float, ({B},) or ({B}, {2 * D}) (got {tuple(a.shape)})")
+        if a.requires_grad and torch.is_grad_enabled():
+            raise RuntimeError(f"audio_amd: {what} is forward-only (no gradient is implemented); wrap the call in "
+                               "torch.no_grad() or detach the inputs.")
+        _wa_require(a, f"{what}: absorption")
+        return a.detach().contiguous()
+    if isinstance(absorption, bool) or not isinstance(absorption, (int, float)):
+        raise TypeError(f"audio_amd: {what}: absorption must be a float or a tensor (got {type(absorption).__name__})")
+    return torch.full((B, 2 * D), float(absorption), dtype=like.dtype, device=like.device)
+
+
+def _rir_launch(what: str, room: Tensor, source: Tensor, mic_array: Tensor, max_order: int, absorption, output_length: int,
+                sound_speed: float, delay_filter_length: int, sample_rate: float, batched: bool) -> Tensor:
+    D = room.shape[-1]
+    if torch.is_grad_enabled() and (room.requires_grad or source.requires_grad or mic_array.requires_grad):
+        raise RuntimeError(f"audio_amd: {what} is forward-only (no gradient is implemented); wrap the call in "
+                           "torch.no_grad() or detach the inputs.")
+    for name, t in (("room", room), ("source", source), ("mic_array", mic_array)):
+        _wa_require(t, f"{what}: {name}")
+    if not batched:
+        room, source, mic_array = room.unsqueeze(0), source.unsqueeze(0), mic_array.unsqueeze(0)
+    B, M = mic_array.shape[0], mic_array.shape[1]
+    ab = _rir_absorption(what, absorption, B, D, room, batched)
+    room, source, mic_array = room.detach().contiguous(), source.detach().contiguous(), mic_array.detach().contiguous()
+    out = torch.empty((B, M, output_length), dtype=room.dtype, device=room.device)
+    if out.numel():
+        table = _rir_lattice(max_order, D, room.device)
+        with torch.cuda.device(room.device):
+            _lib.check(_lib.lib().aamd_simulate_rir(_SA_DTYPES[room.dtype], room.data_ptr(), source.data_ptr(), mic_array.data_ptr(),
+                                                    ab.data_ptr(), table.data_ptr(), table.shape[0], out.data_ptr(), B, M, D,
+                                                    max_order, delay_filter_length, output_length, float(sample_rate),
+                                                    float(sound_speed), _lib.current_stream(room.device)))
+    return out if batched else out[0]
+
+
+def simulate_rir_ism_batch(room: Tensor, source: Tensor, mic_array: Tensor, max_order: int,
+                           absorption: Union[float, Tensor], output_length: int, sound_speed: float = 343.0,
+                           delay_filter_length: int = 81, sample_rate: float = 16000.0) -> Tensor:
+    r"""Room impulse responses of a batch of shoebox rooms by the image-source method (an extension; the reference simulates
+    one room per call, on the CPU): ``room (B, D)``, ``source (B, D)``, ``mic_array (B, M, D)`` with ``D`` 2 or 3 give
+    ``(B, M, output_length)``; every row is a room of its own.  ``absorption`` is a float, ``(B,)`` (one coefficient per
+    room) or ``(B, 2 D)`` (per wall: west, east, south, north, floor, ceiling).  The definition is :func:`simulate_rir_ism`'s.
+    One launch and no synchronisation: can be captured in a graph once the image lattice of ``(max_order, D)`` is cached,
+    i.e. after one eager call (the first call inside a capture raises).  float32 or float64; geometry and sums are float64
+    for both and a float32 result is rounded once; a row whose images include a non-finite delay or amplitude (a microphone
+    on an image, an absorption above 1) is NaN throughout.  Deterministic: a sample's bits do not depend on ``B``, ``M`` or
+    ``output_length``.  Forward-only; a plain Python entry point through the C ABI (not registered as a dispatcher op)."""
+    what = "simulate_rir_ism_batch"
+    if output_length is None:
+        raise ValueError(f"audio_amd: {what}: output_length is required (the default length needs the positions on the host)")
+    _rir_check(what, room, source, mic_array, True, max_order, delay_filter_length, output_length, sample_rate, sound_speed)
+    return _rir_launch(what, room, source, mic_array, max_order, absorption, output_length, sound_speed, delay_filter_length,
+                       sample_rate, True)
+
+
+def simulate_rir_ism(room: Tensor, source: Tensor, mic_array: Tensor, max_order: int, absorption: Union[float, Tensor],
+                     sound_speed: float = 343.0, delay_filter_length: int = 81, center_frequency: Optional[Tensor] = None,
+                     sample_rate: float = 16000.0, output_length: Optional[int] = None) -> Tensor:
+    r"""Room impulse response of a shoebox room by the image-source method (reference:
+    ``torchaudio.prototype.functional.simulate_rir_ism``, single band): ``room (D,)``, ``source (D,)``, ``mic_array (M, D)``
+    give ``(M, L)``.
+
+    Images are the integer vectors ``v`` with ``sum |v_d| <= max_order`` (last axis fastest); per axis ``loc = room (v + 1) -
+    source`` for odd ``v`` and ``room v + source`` for even ``v``, ``att = prod_d tr_lower^|floor(v / 2)| tr_upper^|floor((v +
+    1) / 2)|`` with ``tr = sqrt(1 - absorption)``; per microphone ``a = att / dist`` and ``tau = dist sample_rate /
+    sound_speed``.  With ``pad = delay_filter_length // 2`` and ``g(x) = sinc(x) (1 + cos(pi x / pad)) / 2`` on ``|x| <=
+    pad``, ``rir[c, n] = sum_i a g(n - pad - tau)``: the reference's scatter from ``ceil(tau)`` on, written as a gather.
+    ``L`` is ``output_length`` or ``ceil(max tau) + delay_filter_length``; the latter copies the three position tensors to
+    the host once to size the result (`_host.rir_length`).  ``absorption`` is a float, ``(2 D,)`` or ``(1, 2 D)``; more than
+    one band raises NotImplementedError (the octave-band filter bank is out of scope) and ``center_frequency`` is accepted
+    and unused.  Precision, NaN rows, determinism and the limits (:func:`rir_tiles`) as :func:`simulate_rir_ism_batch`."""
+    what = "simulate_rir_ism"
+    _rir_check(what, room, source, mic_array, False, max_order, delay_filter_length, output_length, sample_rate, sound_speed)
+    if isinstance(absorption, Tensor) and absorption.dim() == 2 and absorption.shape[0] > 1:
+        raise NotImplementedError(f"audio_amd: {what}: a multi-band absorption of shape {tuple(absorption.shape)} needs the "
+                                  "reference's octave-band filter bank, which is not implemented; pass one band")
+    if output_length is None:
+        for name, t in (("room", room), ("source", source), ("mic_array", mic_array)):
+            _wa_require(t, f"{what}: {name}")
+        if mic_array.shape[0] == 0:
+            raise ValueError(f"audio_amd: {what}: the default length needs at least one microphone; pass output_length")
+        output_length = _host.rir_length(room.detach().cpu().numpy(), source.detach().cpu().numpy(),
+                                         mic_array.detach().cpu().numpy(), max_order, sample_rate, sound_speed, delay_filter_length)
+    return _rir_launch(what, room, source, mic_array, max_order, absorption, output_length, sound_speed, delay_filter_length,
+                       sample_rate, False)
 
 
 # --------------------------------------------------------------------------- #

@@ -1,0 +1,4 @@
+"""The reference's ``torchaudio.prototype`` import path for what this package serves of it."""
+from . import functional  # noqa: F401
+
+__all__ = ["functional"]

@@ -64,6 +64,8 @@
  *                             a beam pass, float64 scores -- an addition to ABI 7 as well
  *   aamd_vad_measure          F.vad / F.vad_start / T.Vad (the reference's Python loop over measurements: three launches
  *   aamd_vad_trigger          for all measurements of all rows, one or two for the trigger) -- additions to ABI 7 as well
+ *   aamd_simulate_rir         prototype.functional.simulate_rir_ism (the reference's Python image lattice around the CPU-only
+ *                             torchaudio::_simulate_rir) and a batch of rooms per call; one launch -- an addition to ABI 7
  *   aamd_detect_pitch_f32     F.detect_pitch_frequency (_compute_nccf + _find_max_per_frame + _median_smoothing in the
  *                             reference; an addition to ABI 7 as well)
  *
@@ -911,6 +913,31 @@ int32_t aamd_pointwise_tiles(int32_t which);
  * table, n_in and n_out are read by AAMD_PW_FADE only.  One launch. */
 int aamd_pointwise(int32_t op, int32_t dtype, const void* x, void* out, int64_t rows, int64_t length, int64_t row_stride,
                    double p0, double p1, int32_t flag, const void* table, int64_t n_in, int64_t n_out, void* stream);
+
+/* ---- Image-source room impulse responses (additions to ABI 7; csrc/rir.h) --------------------------------------------- */
+
+#define AAMD_RIR_MAX_FILTER 1025 /* the longest fractional-delay filter (taps, odd) the kernel serves */
+#define AAMD_RIR_MAX_ORDER 64    /* the largest reflection order: 357 889 images in 3-D */
+
+/* which = 0: samples per workgroup; 1: images per chunk; 2: AAMD_RIR_MAX_FILTER; 3: AAMD_RIR_MAX_ORDER. */
+int32_t aamd_rir_tiles(int32_t which);
+
+/* F.simulate_rir_ism_batch: out[b][c][n] = sum_i a g(n - pad - tau), 0 <= n < out_len, over the images i of `lattice` in
+ * ascending order, with pad = filter_len / 2, g(x) = sinc(x) (1 + cos(pi x / pad)) / 2 for |x| <= pad and 0 elsewhere.
+ * room and source are dense (batch, dims), mic dense (batch, mics, dims), absorption dense (batch, 2 dims) in the order lower
+ * wall, upper wall of each axis, out dense (batch, mics, out_len): all of `dtype` (AAMD_SA_F32 or AAMD_SA_F64), on the
+ * device.  lattice is int16 (n_img, dims) on the device: every integer vector v with sum |v_d| <= max_order, last axis
+ * fastest (n_img must be that count).  Per image and axis loc = room (v + 1) - source for odd v, room v + source for even v;
+ * att = prod_d sqrt(1 - absorption_lower)^|floor(v / 2)| sqrt(1 - absorption_upper)^|floor((v + 1) / 2)|; dist = |loc - mic|,
+ * a = att / dist, tau = dist sample_rate / sound_speed.  Geometry, filter argument and sums are float64 for both element
+ * types and a float32 result is rounded once.  A (room, microphone) row with a non-finite a or tau is NaN throughout.  No
+ * atomics, sums in image order: the bits of a sample do not depend on batch, mics or out_len.  dims outside {2, 3}, an even
+ * or short filter: AAMD_EINVAL; filter_len > AAMD_RIR_MAX_FILTER or max_order > AAMD_RIR_MAX_ORDER: AAMD_EUNSUPPORTED.  One
+ * launch. */
+int aamd_simulate_rir(int32_t dtype, const void* room, const void* source, const void* mic, const void* absorption,
+                      const int16_t* lattice, int64_t n_img, void* out, int64_t batch, int64_t mics, int32_t dims,
+                      int32_t max_order, int32_t filter_len, int64_t out_len, double sample_rate, double sound_speed,
+                      void* stream);
 
 #ifdef __cplusplus
 }
