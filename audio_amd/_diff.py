@@ -477,3 +477,77 @@ def fade(x: Tensor, fade_in: Tensor, fade_out: Tensor) -> Tensor:
     fi = torch.cat([fade_in, ones[fade_in.shape[0]:]])
     fo = torch.cat([ones[:n - fade_out.shape[0]], fade_out])
     return (fi * fo) * x
+
+
+# ---- the synthesis ops of prototype.functional: the definitions of csrc/dsp_synth.h as torch compositions on the device -----
+# (the training path: tensor arithmetic that autograd differentiates to any order; not the throughput path)
+
+def oscillator_bank(frequencies: Tensor, amplitudes: Tensor, sample_rate: float, reduction: str) -> Tensor:
+    """(..., T, N) -> (..., T), or (..., T, N) for "none": the phase is summed in float64 and reduced before the sine."""
+    dt = frequencies.dtype
+    ct = torch.float32 if dt in (torch.float16, torch.bfloat16) else dt
+    f, a = frequencies.to(ct), amplitudes.to(ct)
+    two_pi = 2.0 * math.pi
+    dead = f.detach().abs() >= sample_rate / 2.0
+    a = torch.where(dead, torch.zeros((), dtype=ct, device=a.device), a)
+    w = torch.remainder((f * two_pi) / sample_rate, two_pi)
+    phi = torch.cumsum(w.double(), dim=-2)
+    phi = phi - (two_pi * torch.round(phi.detach() / two_pi))
+    y = a * torch.sin(phi.to(ct))
+    if reduction == "sum":
+        y = y.sum(dim=-1)
+    elif reduction == "mean":
+        y = y.mean(dim=-1)
+    return y.to(dt)
+
+
+def filter_waveform(waveform: Tensor, kernels: Tensor) -> Tensor:
+    """waveform (rows, T), kernels (F, L) or (rows, F, L): y[n] = sum_j x[m] h[m // C][j], m = n + (L - 1) // 2 - j."""
+    dt = waveform.dtype
+    ct = torch.float32 if dt in (torch.float16, torch.bfloat16) else dt
+    x, h = waveform.to(ct), kernels.to(ct)
+    T = x.shape[-1]
+    F, L = h.shape[-2:]
+    C, d = T // F, (L - 1) // 2
+    j = torch.arange(L, device=x.device)
+    m = torch.arange(T, device=x.device)[:, None] + d - j[None, :]                  # (T, L)
+    ok = ((m >= 0) & (m < T)).to(ct)
+    mc = m.clamp(0, T - 1)
+    taps = h[..., mc // C, j.expand_as(mc)]                                        # (T, L) or (rows, T, L)
+    return ((x[..., mc] * taps) * ok).sum(dim=-1).to(dt)
+
+
+def sinc_impulse_response(cutoff: Tensor, window_size: int, high_pass: bool) -> Tensor:
+    dt = cutoff.dtype
+    half = window_size // 2
+    i = torch.arange(-half, half + 1, device=cutoff.device, dtype=torch.float64)
+    px = math.pi * (cutoff.double()[..., None] * i)
+    zero = px.detach() == 0
+    s = torch.where(zero, torch.ones_like(px), torch.sin(px) / torch.where(zero, torch.ones_like(px), px))
+    if window_size == 1:
+        win = torch.ones(1, dtype=torch.float64, device=cutoff.device)
+    else:
+        win = 0.54 - 0.46 * torch.cos(2.0 * math.pi * (i + half) / (window_size - 1))
+    g = s * win
+    h = g / g.sum(dim=-1, keepdim=True).abs()
+    if high_pass:
+        centre = torch.zeros(window_size, dtype=torch.float64, device=cutoff.device)
+        centre[half] = 1.0
+        h = centre - h
+    return h.to(dt)
+
+
+def frequency_impulse_response(magnitudes: Tensor) -> Tensor:
+    dt = magnitudes.dtype
+    n = magnitudes.shape[-1]
+    N = 2 * (n - 1)
+    dev = magnitudes.device
+    table = torch.from_numpy(_host.fir_cos_table(n)).to(dev)
+    c = torch.full((n,), 2.0, dtype=torch.float64, device=dev)
+    c[0] = c[-1] = 1.0
+    i = torch.arange(N, device=dev)
+    k = (i + N // 2) % N
+    cosm = table[(k[:, None] * torch.arange(n, device=dev)[None, :]) % N]            # (N, n)
+    ir = torch.matmul(magnitudes.double() * c, cosm.t()) / N
+    win = 0.5 * (1.0 - torch.cos(2.0 * math.pi * i.double() / (N - 1)))
+    return (ir * win).to(dt)

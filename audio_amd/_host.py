@@ -887,3 +887,33 @@ def rir_length(room, source, mic_array, max_order: int, sample_rate: float = 160
     if not np.isfinite(top) or top >= 2.0 ** 31:
         raise ValueError("audio_amd: simulate_rir_ism: the largest delay is not finite (or beyond 2^31 samples); pass output_length")
     return int(np.ceil(top)) + int(delay_filter_length)
+
+
+# ---- synthesis ops (csrc/dsp_synth.h): the ADSR ramp and the cosine table of frequency_impulse_response ----------------------
+def adsr_ramp(num_frames: int, attack: float, hold: float, decay: float, sustain: float, release: float, n_decay: int) -> np.ndarray:
+    """float64 (num_frames,): ``sustain`` everywhere, then the attack, hold, decay and release stretches written over it in
+    that order, each a ``linspace`` that includes both of its ends."""
+    n = int(num_frames) - 1
+    na, nh, nd, nr = int(n * attack), int(n * hold), int(n * decay), int(n * release)
+    out = np.full(int(num_frames), float(sustain), np.float64)
+    if na > 0:
+        out[:na + 1] = np.linspace(0.0, 1.0, na + 1)
+    if nh > 0:
+        out[na:na + nh + 1] = 1.0
+    if nd > 0:
+        out[na + nh:na + nh + nd + 1] = np.linspace(1.0, 0.0, nd + 1) ** n_decay * (1.0 - sustain) + sustain
+    if nr > 0:
+        out[-nr - 1:] = np.linspace(sustain, 0.0, nr + 1)
+    return out
+
+
+def fir_cos_table(n: int) -> np.ndarray:
+    """float64 (N,), N = 2 (n - 1): cos(2 pi q / N), with the entries at the quarter turns exact."""
+    N = 2 * (int(n) - 1)
+    q = np.arange(N, dtype=np.float64)
+    t = np.cos(2.0 * np.pi * q / N)
+    t[0] = 1.0
+    t[N // 2] = -1.0
+    if N % 4 == 0:
+        t[N // 4] = t[3 * N // 4] = 0.0
+    return t

@@ -217,6 +217,14 @@ _SIGS = {
     "aamd_rir_tiles": (C.c_int32, [C.c_int32]),
     "aamd_simulate_rir": (C.c_int, [C.c_int32] + [_P] * 5 + [C.c_int64, _P, C.c_int64, C.c_int64] + [C.c_int32] * 3 +
                           [C.c_int64, C.c_double, C.c_double, _P]),
+    # synthesis ops (additions to ABI 7)
+    "aamd_dsp_tiles": (C.c_int32, [C.c_int32]),
+    "aamd_oscillator_workspace": (C.c_int64, [C.c_int64] * 3),
+    "aamd_oscillator_bank": (C.c_int, [C.c_int32] + [_P] * 4 + [C.c_int64] * 5 + [C.c_double, C.c_int32, _P]),
+    "aamd_filter_waveform": (C.c_int, [C.c_int32] + [_P] * 3 + [C.c_int64] * 4 + [C.c_int32, C.c_int32, _P]),
+    "aamd_sinc_impulse_response": (C.c_int, [C.c_int32, _P, _P, C.c_int64, C.c_int32, C.c_int32, _P]),
+    "aamd_frequency_impulse_response": (C.c_int, [C.c_int32, _P, _P, _P, C.c_int64, C.c_int32, _P]),
+    "aamd_extend_pitch": (C.c_int, [C.c_int32, _P, _P, _P, C.c_int64, C.c_int64, _P]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS)

@@ -42,6 +42,8 @@ __all__ = [
     "linear_fbanks", "spectral_centroid", "spectral_tiles",
     "gain", "contrast", "DB_to_amplitude", "mu_law_encoding", "mu_law_decoding", "pointwise_tiles",
     "simulate_rir_ism", "simulate_rir_ism_batch", "rir_tiles",
+    "oscillator_bank", "filter_waveform", "sinc_impulse_response", "frequency_impulse_response", "adsr_envelope", "extend_pitch",
+    "dsp_tiles",
 ]
 
 # --------------------------------------------------------------------------- #
@@ -4331,6 +4333,317 @@ def simulate_rir_ism(room: Tensor, source: Tensor, mic_array: Tensor, max_order:
                                          mic_array.detach().cpu().numpy(), max_order, sample_rate, sound_speed, delay_filter_length)
     return _rir_launch(what, room, source, mic_array, max_order, absorption, output_length, sound_speed, delay_filter_length,
                        sample_rate, False)
+
+
+# --------------------------------------------------------------------------- #
+# synthesis ops of prototype.functional (csrc/dsp_synth.h)                    #
+# --------------------------------------------------------------------------- #
+DSP_MAX_TAPS = 2049                  # AAMD_DSP_MAX_TAPS: the longest filter of filter_waveform
+DSP_MAX_OSCILLATORS = 256            # AAMD_DSP_MAX_OSCILLATORS: the most oscillators of oscillator_bank
+DSP_MAX_MAGNITUDES = 4097            # AAMD_DSP_MAX_MAGNITUDES: the most magnitudes of frequency_impulse_response
+_DSP_REDUCTIONS = {"sum": 0, "mean": 1, "none": 2}       # AAMD_DSP_SUM ..
+_DSP_WIDE = (torch.float32, torch.float64)
+
+
+def dsp_tiles() -> Tuple[int, int, int, int, int]:
+    """(time steps per chunk of the oscillator scan, outputs per workgroup of filter_waveform, the most taps, the most
+    oscillators, the most magnitudes) of csrc/dsp_synth.h: dsp::kOscChunk, kFwTile, kMaxTaps, kMaxOsc, kMaxMags."""
+    lib = _lib.lib()
+    return tuple(int(lib.aamd_dsp_tiles(i)) for i in range(5))
+
+
+def _dsp_tensor(what: str, name: str, t, dtypes=None) -> None:
+    if not isinstance(t, Tensor):
+        raise TypeError(f"audio_amd: {what}: {name} must be a tensor")
+    if t.dtype not in (dtypes or _WA_FLOATS):
+        names = "float32 or float64" if dtypes else "float16, bfloat16, float32 or float64"
+        raise TypeError(f"audio_amd: {what}: {name} must be {names} (got {t.dtype})")
+
+
+def _dsp_grad(*ts) -> bool:
+    return torch.is_grad_enabled() and any(isinstance(t, Tensor) and t.requires_grad for t in ts)
+
+
+def _dsp_rows3(t: Tensor) -> Tensor:
+    """(..., T, N) as (rows, T, N) whose rows are dense -- strides (any, N, 1) -- without a copy wherever the strides allow it."""
+    T_, N = t.shape[-2:]
+    rows = 1
+    for d in t.shape[:-2]:
+        rows *= d
+    t = t.detach()
+    if not ((N <= 1 or t.stride(-1) == 1) and (T_ <= 1 or t.stride(-2) == N)):
+        t = t.contiguous()
+    if t.dim() != 3:
+        try:
+            t = t.view(rows, T_, N)
+        except RuntimeError:
+            t = t.contiguous().view(rows, T_, N)
+    if rows > 1 and t.stride(0) < 0:
+        t = t.contiguous()
+    return t
+
+
+def oscillator_bank(frequencies: Tensor, amplitudes: Tensor, sample_rate: float, reduction: str = "sum",
+                    dtype: Optional[torch.dtype] = torch.float64) -> Tensor:
+    r"""A bank of sine oscillators (reference: ``torchaudio.prototype.functional.oscillator_bank``): ``frequencies`` and
+    ``amplitudes`` are ``(..., time, N)`` of one shape and dtype; the result is ``(..., time)``, or ``(..., time, N)`` with
+    ``reduction="none"``.
+
+    In the input's type (float32 for the half types) ``w = remainder((f * 2 pi) / sample_rate, 2 pi)``; the phase is the
+    inclusive prefix sum of ``w`` over time; ``y = a' sin(phase)`` with ``a' = 0`` where ``|f| >= sample_rate / 2``;
+    ``"sum"`` and ``"mean"`` reduce the last axis by one fused multiply-add chain in ascending ``n``.  Differences from the
+    reference: the prefix sum is always float64 (``dtype`` takes None, float32 or float64 and changes nothing); the phase is
+    reduced to ``[-pi, pi]`` in float64 before it is rounded, so a float32 result does not lose accuracy with the length;
+    frequencies above Nyquist are silenced without a warning or a synchronisation, so the call can be captured in a graph.
+    Two launches (a chunked scan: :func:`dsp_tiles`), no atomics: a sample's bits depend on neither the batch nor the
+    length.  A NaN or infinite frequency makes its oscillator NaN from that step on.  At most ``DSP_MAX_OSCILLATORS``
+    oscillators.  An input that requires grad takes the differentiable composition (``_diff.oscillator_bank``).  A plain
+    Python entry point through the C ABI (not registered as a dispatcher op)."""
+    what = "oscillator_bank"
+    _dsp_tensor(what, "frequencies", frequencies)
+    _dsp_tensor(what, "amplitudes", amplitudes)
+    if frequencies.dim() < 2:
+        raise ValueError(f"audio_amd: {what}: frequencies must be (..., time, N) (got {frequencies.dim()} dimension(s))")
+    if frequencies.shape != amplitudes.shape:
+        raise ValueError(f"audio_amd: {what}: frequencies and amplitudes must have one shape (got {tuple(frequencies.shape)} and "
+                         f"{tuple(amplitudes.shape)})")
+    if frequencies.dtype != amplitudes.dtype:
+        raise TypeError(f"audio_amd: {what}: frequencies and amplitudes must have one dtype (got {frequencies.dtype} and "
+                        f"{amplitudes.dtype})")
+    if reduction not in _DSP_REDUCTIONS:
+        raise ValueError(f"audio_amd: {what}: reduction must be 'sum', 'mean' or 'none' (got {reduction!r})")
+    if dtype not in (None, torch.float32, torch.float64):
+        raise ValueError(f"audio_amd: {what}: dtype must be None, torch.float32 or torch.float64 (got {dtype!r})")
+    try:                                                  # Python and numpy numbers and 0-d tensors, as the reference takes them
+        rate = float("nan") if isinstance(sample_rate, bool) else float(sample_rate)
+    except (TypeError, ValueError, RuntimeError):
+        rate = float("nan")
+    if not math.isfinite(rate) or not rate > 0:
+        raise ValueError(f"audio_amd: {what}: sample_rate must be a positive finite number (got {sample_rate!r})")
+    sample_rate = rate
+    T_, N = frequencies.shape[-2:]
+    if N > DSP_MAX_OSCILLATORS:
+        raise NotImplementedError(f"audio_amd: {what} serves up to {DSP_MAX_OSCILLATORS} oscillators (got {N})")
+    _wa_require(frequencies, f"{what}: frequencies")
+    _wa_require(amplitudes, f"{what}: amplitudes")
+    if amplitudes.device != frequencies.device:
+        raise ValueError(f"audio_amd: {what}: frequencies and amplitudes must be on one device")
+    if _dsp_grad(frequencies, amplitudes):
+        return _diff.oscillator_bank(frequencies, amplitudes, float(sample_rate), reduction)
+    lead = tuple(frequencies.shape[:-2])
+    out = torch.empty(lead + ((T_, N) if reduction == "none" else (T_,)), dtype=frequencies.dtype, device=frequencies.device)
+    if out.numel() == 0:
+        return out
+    if N == 0:
+        return out.fill_(float("nan") if reduction == "mean" else 0.0)
+    f3, a3 = _dsp_rows3(frequencies), _dsp_rows3(amplitudes)
+    rows = f3.shape[0]
+    lib = _lib.lib()
+    ws = torch.empty((max(int(lib.aamd_oscillator_workspace(rows, T_, N)) // 8, 1),), dtype=torch.float64, device=out.device)
+    with torch.cuda.device(out.device):
+        _lib.check(lib.aamd_oscillator_bank(_SA_DTYPES[out.dtype], f3.data_ptr(), a3.data_ptr(), out.data_ptr(), ws.data_ptr(), rows,
+                                            T_, N, f3.stride(0) if rows > 1 else 0, a3.stride(0) if rows > 1 else 0,
+                                            float(sample_rate), _DSP_REDUCTIONS[reduction], _lib.current_stream(out.device)))
+    return out
+
+
+def filter_waveform(waveform: Tensor, kernels: Tensor) -> Tensor:
+    r"""A time-varying FIR filter (reference: ``torchaudio.prototype.functional.filter_waveform``): ``waveform`` is ``(...,
+    time)``, ``kernels`` is ``(num_filters, L)``, shared by every row, or ``(batch, num_filters, L)`` with ``batch`` the
+    number of rows of ``waveform``; ``time`` must be a multiple of ``num_filters``.
+
+    With ``C = time / num_filters`` and ``d = (L - 1) // 2``: ``y[n] = sum_j x[m] h[m // C][j]``, ``m = n + d - j`` inside
+    the row -- every input sample is filtered by the filter of its own chunk and the filter delay is compensated, which is
+    the reference's unfold, per-chunk convolution, overlap-add and crop as one gather.  One launch, one accumulator per
+    output in ascending ``m`` (float32 fused multiply-adds; double for float64; the half types widen on load and round
+    once): bits depend on neither the batch nor the tile.  ``L`` up to ``DSP_MAX_TAPS``.  Rows are read in place through
+    one row stride.  An input that requires grad takes the differentiable composition (``_diff.filter_waveform``).  A plain
+    Python entry point through the C ABI (not registered as a dispatcher op)."""
+    what = "filter_waveform"
+    _dsp_tensor(what, "waveform", waveform)
+    _dsp_tensor(what, "kernels", kernels)
+    if waveform.dim() < 1:
+        raise ValueError(f"audio_amd: {what}: waveform must be (..., time)")
+    if kernels.dim() not in (2, 3):
+        raise ValueError(f"audio_amd: {what}: kernels must be (num_filters, L) or (batch, num_filters, L) (got {kernels.dim()} "
+                         "dimension(s))")
+    T_ = waveform.shape[-1]
+    F_, L = kernels.shape[-2:]
+    if F_ < 1 or L < 1:
+        raise ValueError(f"audio_amd: {what}: kernels must hold at least one filter of at least one tap (got {tuple(kernels.shape)})")
+    if T_ % F_ != 0:
+        raise ValueError(f"audio_amd: {what}: the length ({T_}) must be a multiple of the number of filters ({F_})")
+    lead = tuple(waveform.shape[:-1])
+    rows = 1
+    for d in lead:
+        rows *= d
+    if kernels.dim() == 3 and kernels.shape[0] != rows:
+        raise ValueError(f"audio_amd: {what}: batched kernels must have one set of filters per row of waveform (got "
+                         f"{kernels.shape[0]} for {rows} row(s))")
+    if waveform.dtype != kernels.dtype:
+        raise TypeError(f"audio_amd: {what}: waveform and kernels must have one dtype (got {waveform.dtype} and {kernels.dtype})")
+    if L > DSP_MAX_TAPS:
+        raise NotImplementedError(f"audio_amd: {what} serves filters up to {DSP_MAX_TAPS} taps (got {L})")
+    _wa_require(waveform, f"{what}: waveform")
+    _wa_require(kernels, f"{what}: kernels")
+    if kernels.device != waveform.device:
+        raise ValueError(f"audio_amd: {what}: waveform and kernels must be on one device")
+    if _dsp_grad(waveform, kernels):
+        return _diff.filter_waveform(waveform.reshape(rows, T_), kernels).reshape(lead + (T_,))
+    out = torch.empty(lead + (T_,), dtype=waveform.dtype, device=waveform.device)
+    if out.numel() == 0:
+        return out
+    x2 = _wa_rows(waveform.detach(), lead, T_)
+    h = kernels.detach().contiguous()
+    with torch.cuda.device(out.device):
+        _lib.check(_lib.lib().aamd_filter_waveform(_SA_DTYPES[out.dtype], x2.data_ptr(), h.data_ptr(), out.data_ptr(), rows, T_,
+                                                   _wa_stride(x2), F_, L, 1 if kernels.dim() == 3 else 0,
+                                                   _lib.current_stream(out.device)))
+    return out
+
+
+def sinc_impulse_response(cutoff: Tensor, window_size: int = 513, high_pass: bool = False) -> Tensor:
+    r"""Windowed-sinc low-pass (or high-pass) filters (reference: ``torchaudio.prototype.functional.sinc_impulse_response``):
+    ``cutoff`` is ``(...)`` with 1 meaning Nyquist, the result ``(..., window_size)``.  With ``half = window_size // 2`` and
+    ``i = -half .. half``: ``g[i] = sinc(cutoff i) hamming(window_size)[i + half]`` (the symmetric window; ``[1]`` for one
+    tap), ``h = g / |sum g|``; ``high_pass`` gives ``-h`` with 1 added to the centre tap.  One launch, evaluated in float64
+    for float32 and float64 alike and rounded once.  An input that requires grad takes the differentiable composition."""
+    what = "sinc_impulse_response"
+    _dsp_tensor(what, "cutoff", cutoff, _DSP_WIDE)
+    if isinstance(window_size, bool) or not isinstance(window_size, int):
+        raise TypeError(f"audio_amd: {what}: window_size must be an int (got {window_size!r})")
+    if window_size <= 0 or window_size % 2 == 0:
+        raise ValueError(f"audio_amd: {what}: window_size must be odd and positive (got {window_size})")
+    if window_size >= 2 ** 31:
+        raise ValueError(f"audio_amd: {what}: window_size is beyond 2^31")
+    _wa_require(cutoff, f"{what}: cutoff")
+    if _dsp_grad(cutoff):
+        return _diff.sinc_impulse_response(cutoff, window_size, bool(high_pass))
+    out = torch.empty(tuple(cutoff.shape) + (window_size,), dtype=cutoff.dtype, device=cutoff.device)
+    if out.numel() == 0:
+        return out
+    c1 = cutoff.detach().contiguous().reshape(-1)
+    with torch.cuda.device(out.device):
+        _lib.check(_lib.lib().aamd_sinc_impulse_response(_SA_DTYPES[out.dtype], c1.data_ptr(), out.data_ptr(), c1.shape[0],
+                                                         window_size, 1 if high_pass else 0, _lib.current_stream(out.device)))
+    return out
+
+
+def frequency_impulse_response(magnitudes: Tensor) -> Tensor:
+    r"""Linear-phase filters from magnitude responses (reference:
+    ``torchaudio.prototype.functional.frequency_impulse_response``): ``magnitudes`` is ``(..., n)`` with ``n >= 2``, the
+    result ``(..., N)`` with ``N = 2 (n - 1)``: the inverse real FFT, ``ir[k] = (m_0 + (-1)^k m_{n-1} + 2 sum_j m_j cos(2 pi
+    j k / N)) / N``, shifted by ``N / 2`` and multiplied by the symmetric Hann window.  One launch: one workgroup per filter,
+    one fused multiply-add chain per tap over a host-built cosine table (cached per ``(n, dtype, device)``: run the call once
+    eagerly before capturing it in a graph).  No check for negative magnitudes (the reference's synchronises).  ``n`` up to
+    ``DSP_MAX_MAGNITUDES``.  An input that requires grad takes the differentiable composition."""
+    what = "frequency_impulse_response"
+    _dsp_tensor(what, "magnitudes", magnitudes, _DSP_WIDE)
+    if magnitudes.dim() < 1 or magnitudes.shape[-1] < 2:
+        raise ValueError(f"audio_amd: {what}: magnitudes must be (..., n) with n >= 2 (got {tuple(magnitudes.shape)})")
+    n = magnitudes.shape[-1]
+    if n > DSP_MAX_MAGNITUDES:
+        raise NotImplementedError(f"audio_amd: {what} serves up to {DSP_MAX_MAGNITUDES} magnitudes (got {n})")
+    _wa_require(magnitudes, f"{what}: magnitudes")
+    if _dsp_grad(magnitudes):
+        return _diff.frequency_impulse_response(magnitudes)
+    out = torch.empty(tuple(magnitudes.shape[:-1]) + (2 * (n - 1),), dtype=magnitudes.dtype, device=magnitudes.device)
+    if out.numel() == 0:
+        return out
+    dt = magnitudes.dtype
+    table = _device_table("cosine table", ("fir_cos", n, str(dt)), out.device, lambda: _host.round_once(_host.fir_cos_table(n), dt))
+    m2 = magnitudes.detach().contiguous().reshape(-1, n)
+    with torch.cuda.device(out.device):
+        _lib.check(_lib.lib().aamd_frequency_impulse_response(_SA_DTYPES[dt], m2.data_ptr(), table.data_ptr(), out.data_ptr(),
+                                                              m2.shape[0], n, _lib.current_stream(out.device)))
+    return out
+
+
+def adsr_envelope(num_frames: int, *, attack: float = 0.0, hold: float = 0.0, decay: float = 0.0, sustain: float = 1.0,
+                  release: float = 0.0, n_decay: int = 2, dtype: Optional[torch.dtype] = None, device=None) -> Tensor:
+    r"""An attack-hold-decay-sustain-release envelope of ``num_frames`` samples (reference:
+    ``torchaudio.prototype.functional.adsr_envelope``).  With ``n = num_frames - 1`` and ``na, nh, nd, nr = int(n attack),
+    int(n hold), int(n decay), int(n release)``: ``sustain`` everywhere, then ``linspace(0, 1, na + 1)`` over the attack, 1
+    over the hold, ``linspace(1, 0, nd + 1)^n_decay (1 - sustain) + sustain`` over the decay and ``linspace(sustain, 0, nr +
+    1)`` at the end.  Built on the host in float64 and rounded once to ``dtype`` (default: torch's default dtype).
+    ``device=None`` is the current ROCm device (the reference defaults to the CPU)."""
+    what = "adsr_envelope"
+    if isinstance(num_frames, bool) or not isinstance(num_frames, int):
+        raise TypeError(f"audio_amd: {what}: num_frames must be an int (got {num_frames!r})")
+    if num_frames < 1:
+        raise ValueError(f"audio_amd: {what}: num_frames must be at least 1 (got {num_frames})")
+    for name, v in (("attack", attack), ("hold", hold), ("decay", decay), ("sustain", sustain), ("release", release)):
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not 0 <= v <= 1:
+            raise ValueError(f"audio_amd: {what}: {name} must lie in [0, 1] (got {v!r})")
+    if attack + hold + decay + release > 1 + 4 * 2.0 ** -52:      # three additions of fractions that sum to 1 on paper
+        raise ValueError(f"audio_amd: {what}: attack + hold + decay + release must not exceed 1 (got "
+                         f"{attack + hold + decay + release})")
+    if isinstance(n_decay, bool) or not isinstance(n_decay, int) or n_decay < 0:
+        raise ValueError(f"audio_amd: {what}: n_decay must be a non-negative int (got {n_decay!r})")
+    dtype = torch.get_default_dtype() if dtype is None else dtype
+    if dtype not in _WA_FLOATS:
+        raise TypeError(f"audio_amd: {what}: dtype must be float16, bfloat16, float32 or float64 (got {dtype})")
+    dev = torch.device(device) if device is not None else (torch.device("cuda", torch.cuda.current_device())
+                                                           if torch.cuda.is_available() else torch.device("cpu"))
+    if dev.type != "cuda":
+        raise RuntimeError(f"audio_amd: {what}: the result must be on an MI355X (ROCm) device, got {dev}. "
+                           "The HIP kernels have no CPU fallback.")
+    return _host.round_once(_host.adsr_ramp(num_frames, attack, hold, decay, sustain, release, n_decay), dtype).to(dev)
+
+
+def extend_pitch(base_frequency: Tensor, pattern: Union[int, List[float], Tensor]) -> Tensor:
+    r"""Harmonics of a fundamental (reference: ``torchaudio.prototype.functional.extend_pitch``): ``base_frequency`` is ``(...,
+    time, 1)``; ``pattern`` is an int ``k`` (the multipliers ``1 .. k``), a list of floats or a 1-D tensor of the same dtype;
+    the result is ``(..., time, N)``, each product rounded once (the half types multiply in float32), in one launch.  A
+    list's multipliers are rounded once to the dtype and cached on the device: run the call once eagerly before capturing it
+    in a graph.  Under grad the result is the broadcast product."""
+    what = "extend_pitch"
+    _dsp_tensor(what, "base_frequency", base_frequency)
+    if base_frequency.dim() < 2 or base_frequency.shape[-1] != 1:
+        raise ValueError(f"audio_amd: {what}: base_frequency must be (..., time, 1) (got {tuple(base_frequency.shape)})")
+    dt = base_frequency.dtype
+    values = None
+    if isinstance(pattern, Tensor):
+        if pattern.dim() != 1:
+            raise ValueError(f"audio_amd: {what}: a tensor pattern must have one dimension (got {pattern.dim()})")
+        if pattern.dtype != dt:
+            raise TypeError(f"audio_amd: {what}: pattern must have the dtype of base_frequency ({dt}; got {pattern.dtype})")
+    elif isinstance(pattern, bool):
+        raise TypeError(f"audio_amd: {what}: pattern must be an int, a list of floats or a tensor (got a bool)")
+    elif isinstance(pattern, int):
+        if pattern < 0:
+            raise ValueError(f"audio_amd: {what}: an int pattern must not be negative (got {pattern})")
+        values = tuple(float(i) for i in range(1, pattern + 1))
+    elif isinstance(pattern, (list, tuple)):
+        if not all(isinstance(v, (int, float)) and not isinstance(v, bool) and math.isfinite(v) for v in pattern):
+            raise TypeError(f"audio_amd: {what}: a list pattern must hold finite numbers")
+        values = tuple(float(v) for v in pattern)
+    else:
+        raise TypeError(f"audio_amd: {what}: pattern must be an int, a list of floats or a tensor (got {type(pattern).__name__})")
+    _wa_require(base_frequency, f"{what}: base_frequency")
+    dev = base_frequency.device
+    if values is None:
+        _wa_require(pattern, f"{what}: pattern")
+        if pattern.device != dev:
+            raise ValueError(f"audio_amd: {what}: base_frequency and pattern must be on one device")
+        pat = pattern
+    elif len(values) == 0:
+        pat = torch.empty((0,), dtype=dt, device=dev)
+    else:
+        pat = _device_table("pitch pattern", ("extend_pitch", values, str(dt)), dev,
+                            lambda: _host.round_once(np.asarray(values, np.float64), dt))
+    if _dsp_grad(base_frequency, pat):
+        return base_frequency * pat
+    N = pat.shape[0]
+    out = torch.empty(tuple(base_frequency.shape[:-1]) + (N,), dtype=dt, device=dev)
+    if out.numel() == 0:
+        return out
+    b1 = base_frequency.detach().contiguous().reshape(-1)
+    p1 = pat.detach().contiguous()
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().aamd_extend_pitch(_SA_DTYPES[dt], b1.data_ptr(), p1.data_ptr(), out.data_ptr(), b1.shape[0], N,
+                                                _lib.current_stream(dev)))
+    return out
 
 
 # --------------------------------------------------------------------------- #

@@ -1,4 +1,7 @@
-"""``torchaudio.prototype.functional``: the room simulation entry points, defined in ``audio_amd.functional``."""
-from ..functional import simulate_rir_ism, simulate_rir_ism_batch  # noqa: F401
+"""``torchaudio.prototype.functional``: the room simulation and the synthesis entry points, defined in
+``audio_amd.functional``."""
+from ..functional import (adsr_envelope, extend_pitch, filter_waveform, frequency_impulse_response,  # noqa: F401
+                          oscillator_bank, simulate_rir_ism, simulate_rir_ism_batch, sinc_impulse_response)
 
-__all__ = ["simulate_rir_ism", "simulate_rir_ism_batch"]
+__all__ = ["simulate_rir_ism", "simulate_rir_ism_batch", "oscillator_bank", "adsr_envelope", "extend_pitch",
+           "sinc_impulse_response", "frequency_impulse_response", "filter_waveform"]

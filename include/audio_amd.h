@@ -66,6 +66,8 @@
  *   aamd_vad_trigger          for all measurements of all rows, one or two for the trigger) -- additions to ABI 7 as well
  *   aamd_simulate_rir         prototype.functional.simulate_rir_ism (the reference's Python image lattice around the CPU-only
  *                             torchaudio::_simulate_rir) and a batch of rooms per call; one launch -- an addition to ABI 7
+ *   aamd_oscillator_bank, aamd_filter_waveform, aamd_sinc_impulse_response, aamd_frequency_impulse_response,
+ *   aamd_extend_pitch         the synthesis ops of prototype.functional -- additions to ABI 7 as well
  *   aamd_detect_pitch_f32     F.detect_pitch_frequency (_compute_nccf + _find_max_per_frame + _median_smoothing in the
  *                             reference; an addition to ABI 7 as well)
  *
@@ -938,6 +940,55 @@ int aamd_simulate_rir(int32_t dtype, const void* room, const void* source, const
                       const int16_t* lattice, int64_t n_img, void* out, int64_t batch, int64_t mics, int32_t dims,
                       int32_t max_order, int32_t filter_len, int64_t out_len, double sample_rate, double sound_speed,
                       void* stream);
+
+/* ---- Synthesis ops (additions to ABI 7; csrc/dsp_synth.h) ------------------------------------------------------------- */
+
+#define AAMD_DSP_MAX_TAPS 2049        /* the longest filter of aamd_filter_waveform */
+#define AAMD_DSP_MAX_OSCILLATORS 256  /* the most oscillators of aamd_oscillator_bank */
+#define AAMD_DSP_MAX_MAGNITUDES 4097  /* the most magnitudes of aamd_frequency_impulse_response */
+enum { AAMD_DSP_SUM = 0, AAMD_DSP_MEAN = 1, AAMD_DSP_NONE = 2 };
+
+/* which = 0: time steps per chunk of the oscillator scan; 1: outputs per workgroup of the filter; 2: AAMD_DSP_MAX_TAPS;
+ * 3: AAMD_DSP_MAX_OSCILLATORS; 4: AAMD_DSP_MAX_MAGNITUDES. */
+int32_t aamd_dsp_tiles(int32_t which);
+
+/* Bytes of workspace aamd_oscillator_bank needs (float64 chunk sums); -1 on a negative size. */
+int64_t aamd_oscillator_workspace(int64_t rows, int64_t time, int64_t n);
+
+/* prototype.functional.oscillator_bank: freq and amp are (rows, time, n) of `dtype` (AAMD_SA_*), dense within a row, rows
+ * `*_row_stride` elements apart.  In the compute type (float32; double for AAMD_SA_F64): w = remainder((f * 2 pi) /
+ * sample_rate, 2 pi), each operation rounded once; phi = the inclusive prefix sum of w over time in float64, reduced to
+ * [-pi, pi] with a two-term 2 pi and rounded once; a' = 0 where |f| >= sample_rate / 2.  AAMD_DSP_NONE writes a' sin(phi) to
+ * out (rows, time, n); AAMD_DSP_SUM / _MEAN write one fused multiply-add chain over ascending n to out (rows, time), the
+ * mean divided once.  Two launches (one where time fits one chunk), no atomics: bits depend on neither rows nor time.
+ * n > AAMD_DSP_MAX_OSCILLATORS: AAMD_EUNSUPPORTED.  With n == 0 nothing is written. */
+int aamd_oscillator_bank(int32_t dtype, const void* freq, const void* amp, void* out, void* workspace, int64_t rows, int64_t time,
+                         int64_t n, int64_t freq_row_stride, int64_t amp_row_stride, double sample_rate, int32_t reduction,
+                         void* stream);
+
+/* prototype.functional.filter_waveform: out[r][i] = sum_j x[r][m] h[m / C][j], m = i + (taps - 1) / 2 - j in [0, time),
+ * C = time / num_filters, one accumulator per output in ascending m (fused multiply-adds in the compute type).  x is
+ * (rows, time) with unit stride along time and rows `row_stride` elements apart, kernels dense (num_filters, taps), or
+ * (rows, num_filters, taps) where `batched`; out dense (rows, time).  taps > AAMD_DSP_MAX_TAPS: AAMD_EUNSUPPORTED. */
+int aamd_filter_waveform(int32_t dtype, const void* x, const void* kernels, void* out, int64_t rows, int64_t time,
+                         int64_t row_stride, int64_t num_filters, int32_t taps, int32_t batched, void* stream);
+
+/* prototype.functional.sinc_impulse_response: cutoff (rows,) -> out (rows, window_size), float32 or float64, evaluated in
+ * float64 and rounded once: g[i] = sinc(cutoff i) hamming(window_size)[i + half], h = g / |sum g|; high_pass negates h and
+ * adds 1 to the centre tap.  One launch. */
+int aamd_sinc_impulse_response(int32_t dtype, const void* cutoff, void* out, int64_t rows, int32_t window_size, int32_t high_pass,
+                               void* stream);
+
+/* prototype.functional.frequency_impulse_response: magnitudes (rows, n) -> out (rows, N), N = 2 (n - 1), float32 or float64:
+ * the inverse real FFT as one fused multiply-add chain over ascending j per tap, shifted by N / 2 and multiplied by the
+ * symmetric Hann window.  table is cos(2 pi q / N), q < N, of `dtype` on the device.  n > AAMD_DSP_MAX_MAGNITUDES:
+ * AAMD_EUNSUPPORTED.  One launch. */
+int aamd_frequency_impulse_response(int32_t dtype, const void* magnitudes, const void* table, void* out, int64_t rows, int32_t n,
+                                    void* stream);
+
+/* prototype.functional.extend_pitch: out[i][k] = base[i] * pattern[k], i < count, k < n, of `dtype`; the half types
+ * multiply in float32 and round once.  One launch. */
+int aamd_extend_pitch(int32_t dtype, const void* base, const void* pattern, void* out, int64_t count, int64_t n, void* stream);
 
 #ifdef __cplusplus
 }
