@@ -889,6 +889,27 @@ def rir_length(room, source, mic_array, max_order: int, sample_rate: float = 160
     return int(np.ceil(top)) + int(delay_filter_length)
 
 
+# ---- ray-traced energy histograms (csrc/ray_trace.h): the two host scalars of a call ------------------------------------------
+RAY_HEADROOM = 64                    # ray::kHeadroom
+
+
+def ray_num_bins(time_thres: float, hist_bin_size: float) -> int:
+    """``ceil(time_thres / hist_bin_size)`` in float64."""
+    return int(math.ceil(float(time_thres) / float(hist_bin_size)))
+
+
+def ray_scale_log2(mic_radius: float, headroom: int = RAY_HEADROOM) -> int:
+    """``k = 62 - ceil(log2(8 headroom / mic_radius^2))``: contributions enter the int64 sums as ``rint(e 2^k)``.  Every one is
+    at most ``4 E0 / R^2 = 8 / (N R^2)``, so ``headroom`` contributions of each of the N rays stay below ``2^62``.  The
+    logarithm is taken from the float64 exponent (exact at powers of two)."""
+    r2 = float(mic_radius) * float(mic_radius)
+    x = 8.0 * headroom / r2 if r2 > 0.0 else math.inf
+    if not (math.isfinite(x) and x >= 2.0 ** -900 and x <= 2.0 ** 900):
+        raise ValueError(f"audio_amd: ray_tracing: mic_radius = {mic_radius!r} leaves no usable fixed-point scale")
+    m, e = math.frexp(x)                                     # x = m 2^e, 0.5 <= m < 1
+    return 62 - (e - 1 if m == 0.5 else e)
+
+
 # ---- synthesis ops (csrc/dsp_synth.h): the ADSR ramp and the cosine table of frequency_impulse_response ----------------------
 def adsr_ramp(num_frames: int, attack: float, hold: float, decay: float, sustain: float, release: float, n_decay: int) -> np.ndarray:
     """float64 (num_frames,): ``sustain`` everywhere, then the attack, hold, decay and release stretches written over it in

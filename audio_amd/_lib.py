@@ -217,6 +217,10 @@ _SIGS = {
     "aamd_rir_tiles": (C.c_int32, [C.c_int32]),
     "aamd_simulate_rir": (C.c_int, [C.c_int32] + [_P] * 5 + [C.c_int64, _P, C.c_int64, C.c_int64] + [C.c_int32] * 3 +
                           [C.c_int64, C.c_double, C.c_double, _P]),
+    # ray-traced energy histograms (additions to ABI 7)
+    "aamd_ray_tiles": (C.c_int32, [C.c_int32]),
+    "aamd_ray_trace": (C.c_int, [C.c_int32] + [_P] * 7 + [C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int64, C.c_int64,
+                                 C.c_int32] + [C.c_double] * 5 + [_P]),
     # synthesis ops (additions to ABI 7)
     "aamd_dsp_tiles": (C.c_int32, [C.c_int32]),
     "aamd_oscillator_workspace": (C.c_int64, [C.c_int64] * 3),

@@ -42,6 +42,7 @@ __all__ = [
     "linear_fbanks", "spectral_centroid", "spectral_tiles",
     "gain", "contrast", "DB_to_amplitude", "mu_law_encoding", "mu_law_decoding", "pointwise_tiles",
     "simulate_rir_ism", "simulate_rir_ism_batch", "rir_tiles",
+    "ray_tracing", "ray_tracing_batch", "ray_tiles",
     "oscillator_bank", "filter_waveform", "sinc_impulse_response", "frequency_impulse_response", "adsr_envelope", "extend_pitch",
     "dsp_tiles",
 ]
@@ -4333,6 +4334,184 @@ def simulate_rir_ism(room: Tensor, source: Tensor, mic_array: Tensor, max_order:
                                          mic_array.detach().cpu().numpy(), max_order, sample_rate, sound_speed, delay_filter_length)
     return _rir_launch(what, room, source, mic_array, max_order, absorption, output_length, sound_speed, delay_filter_length,
                        sample_rate, False)
+
+
+# --------------------------------------------------------------------------- #
+# ray-traced energy histograms of shoebox rooms (csrc/ray_trace.h)            #
+# --------------------------------------------------------------------------- #
+RAY_MAX_BANDS = 8                    # AAMD_RAY_MAX_BANDS
+RAY_MAX_MICS = 16                    # AAMD_RAY_MAX_MICS
+RAY_MAX_RAYS = 1 << 24               # AAMD_RAY_MAX_RAYS
+RAY_MAX_BINS = 65536                 # AAMD_RAY_MAX_BINS
+RAY_MAX_BOUNCES = 4096               # AAMD_RAY_MAX_BOUNCES: a room whose sum_d (floor(S_max / room_d) + 2) exceeds it is NaN
+RAY_HEADROOM = 64                    # AAMD_RAY_HEADROOM: contributions of every ray a (microphone, bin) may take
+
+
+def ray_tiles() -> Tuple[int, int, int, int, int, int, int]:
+    """(rays per workgroup, the most bands, the most microphones, the most rays, the most bins, the cap on a room's bounce
+    bound, the headroom of the fixed-point sums) of csrc/ray_trace.h: ray::kThreads, kMaxBands, kMaxMics, kMaxRays, kMaxBins,
+    kMaxBounces, kHeadroom."""
+    lib = _lib.lib()
+    return tuple(int(lib.aamd_ray_tiles(i)) for i in range(7))
+
+
+def _ray_check(what: str, room, source, mic_array, batched: bool, num_rays, absorption, scattering, mic_radius, sound_speed,
+               energy_thres, time_thres, hist_bin_size) -> Tuple[int, int]:
+    """The checks that need no device, in the order ranks, sizes, dtypes, parameters, limits; returns (num_bands, num_bins)."""
+    lead = 1 if batched else 0
+    for name, t, rank in (("room", room, lead + 1), ("source", source, lead + 1), ("mic_array", mic_array, lead + 2)):
+        if not isinstance(t, Tensor):
+            raise TypeError(f"audio_amd: {what}: {name} must be a tensor")
+        if t.dim() != rank:
+            raise ValueError(f"audio_amd: {what}: {name} must have {rank} dimensions (got {t.dim()})")
+    D = room.shape[-1]
+    if D not in (2, 3):
+        raise ValueError(f"audio_amd: {what}: room must have 2 or 3 coordinates (got {D})")
+    if source.shape[-1] != D or mic_array.shape[-1] != D:
+        raise ValueError(f"audio_amd: {what}: room, source and mic_array must have the same number of coordinates (got {D}, "
+                         f"{source.shape[-1]}, {mic_array.shape[-1]})")
+    if batched and not (room.shape[0] == source.shape[0] == mic_array.shape[0]):
+        raise ValueError(f"audio_amd: {what}: room, source and mic_array must have the same number of rooms (got "
+                         f"{room.shape[0]}, {source.shape[0]}, {mic_array.shape[0]})")
+    B = room.shape[0] if batched else 1
+    bands = []
+    for name, c in (("absorption", absorption), ("scattering", scattering)):
+        if isinstance(c, Tensor):
+            if batched:
+                if c.dim() != 3 or c.shape[0] != B or c.shape[2] != 2 * D:
+                    raise ValueError(f"audio_amd: {what}: {name} must be a float or ({B}, num_bands, {2 * D}) (got {tuple(c.shape)})")
+            elif c.dim() not in (1, 2) or (c.dim() == 2 and c.shape[1] != 2 * D):
+                raise ValueError(f"audio_amd: {what}: {name} must be a float, (num_bands,) or (num_bands, {2 * D}) (got "
+                                 f"{tuple(c.shape)})")
+            bands.append(c.shape[1] if batched else c.shape[0])
+            if bands[-1] < 1:
+                raise ValueError(f"audio_amd: {what}: {name} must have at least one band (got {tuple(c.shape)})")
+        elif isinstance(c, bool) or not isinstance(c, (int, float)):
+            raise TypeError(f"audio_amd: {what}: {name} must be a float or a tensor (got {type(c).__name__})")
+        else:
+            bands.append(1)
+    num_bands = max(bands)
+    if min(bands) not in (1, num_bands):
+        raise ValueError(f"audio_amd: {what}: absorption and scattering must have the same number of bands, or one of them a "
+                         f"single band (got {bands[0]} and {bands[1]})")
+    if room.dtype not in (torch.float32, torch.float64):
+        raise TypeError(f"audio_amd: {what}: room must be float32 or float64 (got {room.dtype})")
+    others = [t for t in (source, mic_array, absorption, scattering) if isinstance(t, Tensor)]
+    if any(t.dtype != room.dtype for t in others):
+        raise TypeError(f"audio_amd: {what}: room, source, mic_array and the coefficient tensors must have one dtype (got "
+                        f"{', '.join(str(t.dtype) for t in [room] + others)})")
+    if isinstance(num_rays, bool) or not isinstance(num_rays, int):
+        raise TypeError(f"audio_amd: {what}: num_rays must be an int (got {num_rays!r})")
+    if num_rays < 1:
+        raise ValueError(f"audio_amd: {what}: num_rays must be at least 1 (got {num_rays})")
+    for name, v in (("mic_radius", mic_radius), ("sound_speed", sound_speed), ("energy_thres", energy_thres),
+                    ("time_thres", time_thres), ("hist_bin_size", hist_bin_size)):
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v) or not v > 0:
+            raise ValueError(f"audio_amd: {what}: {name} must be a positive finite number (got {v!r})")
+    num_bins = _host.ray_num_bins(time_thres, hist_bin_size)
+    if num_bands > RAY_MAX_BANDS:
+        raise NotImplementedError(f"audio_amd: {what} serves up to {RAY_MAX_BANDS} bands (got {num_bands})")
+    if mic_array.shape[-2] > RAY_MAX_MICS:
+        raise NotImplementedError(f"audio_amd: {what} serves up to {RAY_MAX_MICS} microphones (got {mic_array.shape[-2]})")
+    if num_rays > RAY_MAX_RAYS:
+        raise NotImplementedError(f"audio_amd: {what} serves up to {RAY_MAX_RAYS} rays (got {num_rays})")
+    if num_bins > RAY_MAX_BINS:
+        raise NotImplementedError(f"audio_amd: {what} serves up to {RAY_MAX_BINS} bins (got {num_bins} = ceil(time_thres / "
+                                  "hist_bin_size))")
+    return num_bands, num_bins
+
+
+def _ray_coefficients(what: str, name: str, c, B: int, D: int, num_bands: int, like: Tensor, batched: bool) -> Tensor:
+    """Dense (B, num_bands, 2 D) of `like`'s dtype on its device, from a float or a tensor of one of the checked forms."""
+    if not isinstance(c, Tensor):
+        return torch.full((B, num_bands, 2 * D), float(c), dtype=like.dtype, device=like.device)
+    if c.requires_grad and torch.is_grad_enabled():
+        raise RuntimeError(f"audio_amd: {what} is forward-only (no gradient is implemented); wrap the call in "
+                           "torch.no_grad() or detach the inputs.")
+    _wa_require(c, f"{what}: {name}")
+    c = c.detach()
+    if not batched:
+        c = (c[:, None] if c.dim() == 1 else c)[None]
+    return c.expand(B, num_bands, 2 * D).contiguous()
+
+
+def _ray_launch(what: str, room: Tensor, source: Tensor, mic_array: Tensor, num_rays: int, absorption, scattering,
+                mic_radius: float, sound_speed: float, energy_thres: float, time_thres: float, hist_bin_size: float,
+                batched: bool) -> Tensor:
+    num_bands, num_bins = _ray_check(what, room, source, mic_array, batched, num_rays, absorption, scattering, mic_radius,
+                                     sound_speed, energy_thres, time_thres, hist_bin_size)
+    D = room.shape[-1]
+    if torch.is_grad_enabled() and (room.requires_grad or source.requires_grad or mic_array.requires_grad):
+        raise RuntimeError(f"audio_amd: {what} is forward-only (no gradient is implemented); wrap the call in "
+                           "torch.no_grad() or detach the inputs.")
+    for name, t in (("room", room), ("source", source), ("mic_array", mic_array)):
+        _wa_require(t, f"{what}: {name}")
+    if not batched:
+        room, source, mic_array = room.unsqueeze(0), source.unsqueeze(0), mic_array.unsqueeze(0)
+    B, M = mic_array.shape[0], mic_array.shape[1]
+    ab = _ray_coefficients(what, "absorption", absorption, B, D, num_bands, room, batched)
+    sc = _ray_coefficients(what, "scattering", scattering, B, D, num_bands, room, batched)
+    room, source, mic_array = room.detach().contiguous(), source.detach().contiguous(), mic_array.detach().contiguous()
+    out = torch.empty((B, M, num_bands, num_bins), dtype=room.dtype, device=room.device)
+    if out.numel():
+        acc = torch.zeros((B, M, num_bands, num_bins), dtype=torch.int64, device=room.device)
+        with torch.cuda.device(room.device):
+            _lib.check(_lib.lib().aamd_ray_trace(_SA_DTYPES[room.dtype], room.data_ptr(), source.data_ptr(), mic_array.data_ptr(),
+                                                 ab.data_ptr(), sc.data_ptr(), acc.data_ptr(), out.data_ptr(), B, M, D, num_bands,
+                                                 num_rays, num_bins, _host.ray_scale_log2(mic_radius), float(mic_radius),
+                                                 float(sound_speed), float(energy_thres), float(time_thres),
+                                                 float(hist_bin_size), _lib.current_stream(room.device)))
+    return out if batched else out[0]
+
+
+def ray_tracing_batch(room: Tensor, source: Tensor, mic_array: Tensor, num_rays: int, absorption: Union[float, Tensor] = 0.0,
+                      scattering: Union[float, Tensor] = 0.0, mic_radius: float = 0.5, sound_speed: float = 343.0,
+                      energy_thres: float = 1e-7, time_thres: float = 10.0, hist_bin_size: float = 0.004) -> Tensor:
+    r"""Energy histograms of a batch of shoebox rooms by ray tracing (an extension; the reference traces one room per call, on
+    the CPU): ``room (B, D)``, ``source (B, D)``, ``mic_array (B, M, D)`` with ``D`` 2 or 3 give ``(B, M, num_bands,
+    num_bins)``; every row is a room of its own.  ``absorption`` and ``scattering`` are each a float or ``(B, num_bands, 2
+    D)`` (per wall: west, east, south, north, floor, ceiling); one of them may have a single band.  The definition is
+    :func:`ray_tracing`'s.  Two launches and no synchronisation; nothing is cached on the host, so the first call can be
+    captured in a graph.  float32 or float64; geometry and energies are float64 for both and the result is rounded once.  A
+    bad room (see :func:`ray_tracing`) is NaN throughout and the other rooms keep their bits.  Deterministic: the sums are
+    fixed point, so a bin's bits do not depend on ``B``, ``M`` or the order in which the rays arrive.  Forward-only; a plain
+    Python entry point through the C ABI (not registered as a dispatcher op)."""
+    return _ray_launch("ray_tracing_batch", room, source, mic_array, num_rays, absorption, scattering, mic_radius, sound_speed,
+                       energy_thres, time_thres, hist_bin_size, True)
+
+
+def ray_tracing(room: Tensor, source: Tensor, mic_array: Tensor, num_rays: int, absorption: Union[float, Tensor] = 0.0,
+                scattering: Union[float, Tensor] = 0.0, mic_radius: float = 0.5, sound_speed: float = 343.0,
+                energy_thres: float = 1e-7, time_thres: float = 10.0, hist_bin_size: float = 0.004) -> Tensor:
+    r"""Energy histogram of a shoebox room by ray tracing (reference: ``torchaudio.prototype.functional.ray_tracing``): ``room
+    (D,)``, ``source (D,)``, ``mic_array (M, D)`` give ``(M, num_bands, num_bins)`` with ``num_bins = ceil(time_thres /
+    hist_bin_size)``.  ``absorption`` and ``scattering`` are each a float (one band, all walls), ``(num_bands,)`` (every wall
+    alike) or ``(num_bands, 2 D)`` (west, east, south, north, floor, ceiling: wall ``2 d + (upper wall of axis d)``).
+
+    With ``E0 = 2 / num_rays``, ``S_max = time_thres sound_speed``, ``R = mic_radius`` and ``w_bin = sound_speed
+    hist_bin_size``, ray ``i`` of ``N`` leaves the source along ``(rho cos phi, rho sin phi, z)`` with ``z = 1 - (2 i + 1) /
+    N``, ``rho = sqrt(1 - z^2)``, ``phi = i pi (3 - sqrt 5)`` (in 2-D ``(cos phi, sin phi)`` with ``phi = 2 pi (i + 1/2) /
+    N``), carrying ``tr = E0`` in every band, and repeats: (1) the next wall is the first axis that attains ``t = min_d t_d``
+    with ``t_d = (room_d - p_d) / dir_d`` for ``dir_d > 0`` and ``p_d / -dir_d`` for ``dir_d < 0``; (2) every microphone with
+    ``v = mic - p``, ``u = v . dir``, ``0 <= u <= t`` and ``v . v - u^2 < R^2`` gets ``tr / (r2 p_hit)`` at distance ``d =
+    travel + u``, where ``r2 = max(d^2, R^2)`` and ``p_hit = 1 - sqrt(1 - R^2 / r2)``, in bin ``floor(d / w_bin)`` if that is
+    a bin; (3) the ray moves to the wall (the hit coordinate is set to 0 or ``room_d`` exactly) and ``tr *= 1 -
+    absorption``; (4) if the wall scatters in any band, every microphone at ``v = mic - p``, ``h = |v|`` gets ``st / (r2
+    p_hit)`` with ``st = 2 (|v_axis| / h) p_eq tr scattering``, ``p_eq = 1 - sqrt(1 - R^2 / max(h^2, R^2))`` and ``d = travel +
+    h``, if ``d < S_max`` and ``max_band st > energy_thres``; (5) ``tr *= 1 - scattering`` and the ray ends if ``travel >
+    S_max`` or ``max_band tr < energy_thres``; (6) it reflects.  Every contribution ``e`` enters its sum as ``rint(e 2^k)``
+    in int64 with ``k = 62 - ceil(log2(8 H / R^2))``, ``H`` the headroom of :func:`ray_tiles` (64: a step of ``2^-51`` at the
+    default radius), and the result is the sum times ``2^-k`` rounded once.  A bin that took more than ``H`` contributions of
+    every ray can wrap, and then it is NaN.
+
+    This definition governs where the reference differs: ``r2`` is clamped at ``R^2`` in the product too (the reference
+    divides by the unclamped square, which is unbounded for a microphone at the source); geometry and energies are float64
+    for float32 inputs; a bad room -- a dimension that is not finite and positive, a source or a microphone not strictly
+    inside, a coefficient outside ``[0, 1]`` or NaN, or a bounce bound ``sum_d (floor(S_max / room_d) + 2)`` above the cap of
+    :func:`ray_tiles` (4096; the defaults in a 6 x 5 x 3 m room need 2406) -- gives NaN throughout and is not traced.
+    Limits, errors, precision and determinism as :func:`ray_tracing_batch`."""
+    return _ray_launch("ray_tracing", room, source, mic_array, num_rays, absorption, scattering, mic_radius, sound_speed,
+                       energy_thres, time_thres, hist_bin_size, False)
 
 
 # --------------------------------------------------------------------------- #

@@ -66,6 +66,8 @@
  *   aamd_vad_trigger          for all measurements of all rows, one or two for the trigger) -- additions to ABI 7 as well
  *   aamd_simulate_rir         prototype.functional.simulate_rir_ism (the reference's Python image lattice around the CPU-only
  *                             torchaudio::_simulate_rir) and a batch of rooms per call; one launch -- an addition to ABI 7
+ *   aamd_ray_trace            prototype.functional.ray_tracing (the reference's CPU-only loop over the rays of one room) and a
+ *                             batch of rooms per call; fixed-point sums, two launches -- an addition to ABI 7
  *   aamd_oscillator_bank, aamd_filter_waveform, aamd_sinc_impulse_response, aamd_frequency_impulse_response,
  *   aamd_extend_pitch         the synthesis ops of prototype.functional -- additions to ABI 7 as well
  *   aamd_detect_pitch_f32     F.detect_pitch_frequency (_compute_nccf + _find_max_per_frame + _median_smoothing in the
@@ -941,7 +943,38 @@ int aamd_simulate_rir(int32_t dtype, const void* room, const void* source, const
                       int32_t max_order, int32_t filter_len, int64_t out_len, double sample_rate, double sound_speed,
                       void* stream);
 
-/* ---- Synthesis ops (additions to ABI 7; csrc/dsp_synth.h) ------------------------------------------------------------- */
+/* ---- Ray-traced energy histograms of shoebox rooms (additions to ABI 7; csrc/ray_trace.h) ----------------------------- */
+
+#define AAMD_RAY_MAX_BANDS 8         /* frequency bands of the coefficients */
+#define AAMD_RAY_MAX_MICS 16         /* microphones of a room */
+#define AAMD_RAY_MAX_RAYS 16777216   /* 2^24 rays */
+#define AAMD_RAY_MAX_BINS 65536      /* histogram bins */
+#define AAMD_RAY_MAX_BOUNCES 4096    /* the cap on a room's bounce bound sum_d (floor(S_max / room_d) + 2) */
+#define AAMD_RAY_HEADROOM 64         /* contributions of EVERY ray one (microphone, bin) may take before its sum can wrap */
+
+/* which = 0: rays per workgroup; 1: AAMD_RAY_MAX_BANDS; 2: AAMD_RAY_MAX_MICS; 3: AAMD_RAY_MAX_RAYS; 4: AAMD_RAY_MAX_BINS;
+ * 5: AAMD_RAY_MAX_BOUNCES; 6: AAMD_RAY_HEADROOM. */
+int32_t aamd_ray_tiles(int32_t which);
+
+/* F.ray_tracing_batch: out[b][m][band][bin] = the energy that the num_rays rays of room b leave at microphone m (the
+ * definition: the docstring of F.ray_tracing, restated by tests/ray_oracle.py).  room and source are dense (batch, dims), mic
+ * dense (batch, mics, dims), absorption and scattering dense (batch, bands, 2 dims) in the order lower wall, upper wall of
+ * each axis, out dense (batch, mics, bands, num_bins): all of `dtype` (AAMD_SA_F32 or AAMD_SA_F64), on the device.  acc is
+ * an int64 buffer of out's shape that is ZERO on entry: every contribution e is added to it as rint(e 2^scale_log2) with
+ * 64-bit integer atomics, so the sums do not depend on the order of arrival, and out = acc 2^-scale_log2 rounded to the
+ * element type.  The caller forms scale_log2 = 62 - ceil(log2(8 AAMD_RAY_HEADROOM / mic_radius^2)) from mic_radius alone;
+ * an accumulator that wrapped (negative) gives NaN.  Geometry and energies are float64 for both element types.  A bad room
+ * -- a dimension that is not finite and positive, a source or microphone not strictly inside, a coefficient outside [0, 1]
+ * or NaN, a bounce bound above AAMD_RAY_MAX_BOUNCES with S_max = time_thres sound_speed -- is NaN throughout and no ray of
+ * it is traced; the other rooms keep their bits.  The bounce loop of a ray is bounded by the room's bounce bound whatever
+ * the data.  dims outside {2, 3}, a non-positive or non-finite scalar: AAMD_EINVAL; bands, mics, num_rays or num_bins
+ * above the limits: AAMD_EUNSUPPORTED.  Two launches (trace, convert), no synchronisation. */
+int aamd_ray_trace(int32_t dtype, const void* room, const void* source, const void* mic, const void* absorption,
+                   const void* scattering, int64_t* acc, void* out, int64_t batch, int64_t mics, int32_t dims, int32_t bands,
+                   int64_t num_rays, int64_t num_bins, int32_t scale_log2, double mic_radius, double sound_speed,
+                   double energy_thres, double time_thres, double hist_bin_size, void* stream);
+
+/* ---- Synthesis ops (additions to ABI 7; csrc/dsp_synth.h)------------------------------------------------------------- */
 
 #define AAMD_DSP_MAX_TAPS 2049        /* the longest filter of aamd_filter_waveform */
 #define AAMD_DSP_MAX_OSCILLATORS 256  /* the most oscillators of aamd_oscillator_bank */
