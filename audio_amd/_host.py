@@ -802,6 +802,103 @@ def linear_fbanks(n_freqs: int, f_min: float, f_max: float, n_filter: int, sampl
     return torch.max(torch.zeros(1), torch.min(down_slopes, up_slopes))
 
 
+# ---- Bark and chroma filterbanks (prototype.functional), and the dense projection's operand image (csrc/dense_fbank.h) ------
+BARK_SCALES = ("traunmuller", "schroeder", "wang")
+
+
+def _hz_to_bark(freq: float, bark_scale: str = "traunmuller") -> float:
+    if bark_scale not in BARK_SCALES:
+        raise ValueError('bark_scale should be one of "schroeder", "traunmuller" or "wang".')
+    if bark_scale == "wang":
+        return 6.0 * math.asinh(freq / 600.0)
+    if bark_scale == "schroeder":
+        return 7.0 * math.asinh(freq / 650.0)
+    bark = ((26.81 * freq) / (1960.0 + freq)) - 0.53
+    if bark < 2:
+        bark += 0.15 * (2 - bark)
+    elif bark > 20.1:
+        bark += 0.22 * (bark - 20.1)
+    return bark
+
+
+def _bark_to_hz(barks: torch.Tensor, bark_scale: str = "traunmuller") -> torch.Tensor:
+    if bark_scale not in BARK_SCALES:
+        raise ValueError('bark_scale should be one of "schroeder", "traunmuller" or "wang".')
+    if bark_scale == "wang":
+        return 600.0 * torch.sinh(barks / 6.0)
+    if bark_scale == "schroeder":
+        return 650.0 * torch.sinh(barks / 7.0)
+    # the two corrections undone per element (the exact inverse of _hz_to_bark)
+    barks = torch.where(barks < 2, (barks - 0.3) / 0.85, torch.where(barks > 20.1, (barks + 4.422) / 1.22, barks))
+    return 1960.0 * ((barks + 0.53) / (26.28 - barks))
+
+
+def barkscale_fbanks(n_freqs: int, f_min: float, f_max: float, n_barks: int, sample_rate: int,
+                     bark_scale: str = "traunmuller") -> torch.Tensor:
+    """Triangular filterbank on a Bark scale, (n_freqs, n_barks): float32 torch CPU ops, the triangles of
+    ``melscale_fbanks`` between edges equally spaced in Bark (prototype.functional.barkscale_fbanks)."""
+    all_freqs = torch.linspace(0, sample_rate // 2, n_freqs)
+    m_min = _hz_to_bark(f_min, bark_scale=bark_scale)
+    m_max = _hz_to_bark(f_max, bark_scale=bark_scale)
+    f_pts = _bark_to_hz(torch.linspace(m_min, m_max, n_barks + 2), bark_scale=bark_scale)
+    f_diff = f_pts[1:] - f_pts[:-1]                             # (n_barks + 1)
+    slopes = f_pts.unsqueeze(0) - all_freqs.unsqueeze(1)        # (n_freqs, n_barks + 2)
+    down_slopes = (-1.0 * slopes[:, :-2]) / f_diff[:-1]
+    up_slopes = slopes[:, 2:] / f_diff[1:]
+    fb = torch.max(torch.zeros(1), torch.min(down_slopes, up_slopes))
+    if (fb.max(dim=0).values == 0.0).any():
+        warnings.warn(
+            "At least one bark filterbank has all zero values. "
+            f"The value for `n_barks` ({n_barks}) may be set too high. "
+            f"Or, the value for `n_freqs` ({n_freqs}) may be set too low."
+        )
+    return fb
+
+
+def chroma_filterbank(sample_rate: int, n_freqs: int, n_chroma: int, *, tuning: float = 0.0, ctroct: float = 5.0,
+                      octwidth: Optional[float] = 2.0, norm: float = 2, base_c: bool = True) -> torch.Tensor:
+    """Chroma filterbank, (n_freqs, n_chroma): float32 torch CPU ops (prototype.functional.chroma_filterbank, a port of
+    librosa's ``filters.chroma``): a Gaussian bump around every bin's pitch class, each row normalised, weighted by a
+    Gaussian over octaves around ``ctroct``.  Dense: with the defaults nearly every entry is non-zero."""
+    if n_freqs < 2:
+        raise ValueError(f"chroma_filterbank: n_freqs must be at least 2 (got {n_freqs})")
+    if n_chroma < 1:
+        raise ValueError(f"chroma_filterbank: n_chroma must be at least 1 (got {n_chroma})")
+    if not norm > 0:
+        raise ValueError(f"chroma_filterbank: norm must be positive (got {norm})")
+    freqs = torch.linspace(0, sample_rate // 2, n_freqs)[1:]
+    a440 = 440.0 * 2.0 ** (tuning / n_chroma)
+    freq_bins = n_chroma * torch.log2(freqs / (a440 / 16))
+    freq_bins = torch.cat((torch.tensor([freq_bins[0] - 1.5 * n_chroma]), freq_bins))
+    freq_bin_widths = torch.cat((torch.maximum(freq_bins[1:] - freq_bins[:-1], torch.tensor(1.0)), torch.tensor([1.0])))
+    D = freq_bins.unsqueeze(1) - torch.arange(0, n_chroma)      # (n_freqs, n_chroma)
+    n_chroma2 = round(n_chroma / 2)
+    D = torch.remainder(D + n_chroma2, n_chroma) - n_chroma2    # the wrapped distance to every pitch class
+    fb = torch.exp(-0.5 * (2 * D / freq_bin_widths.unsqueeze(1)) ** 2)
+    fb = torch.nn.functional.normalize(fb, p=norm, dim=1)
+    if octwidth is not None:
+        fb = fb * torch.exp(-0.5 * (((freq_bins.unsqueeze(1) / n_chroma - ctroct) / octwidth) ** 2))
+    if base_c:
+        fb = torch.roll(fb, -3 * (n_chroma // 12), dims=1)
+    return fb.contiguous()
+
+
+def dense_fbank_fragments(fb: np.ndarray) -> np.ndarray:
+    """The (n_freqs, n_out) float32 filterbank `fb` as the dense projection kernel reads it (csrc/dense_fbank.h,
+    dfb::w_index): K4 / 4 * NT * 64 floats (K4 = n_freqs rounded up to 4, NT = ceil(n_out / 16)) with element (k, n) at
+    ``((k // 4) * NT + n // 16) * 64 + (k % 4) * 16 + n % 16`` -- the order in which the matrix instruction's A operand is
+    read, so that a tile of bins is a run of consecutive floats.  Bins beyond n_freqs and outputs beyond n_out are zeros."""
+    fb = np.asarray(fb, dtype=np.float32)
+    if fb.ndim != 2 or fb.size == 0:
+        raise ValueError("dense_fbank_fragments expects a non-empty (n_freqs, n_out) filterbank")
+    K, N = fb.shape
+    k4, nt = (K + 3) // 4 * 4, (N + 15) // 16
+    padded = np.zeros((k4, nt * 16), dtype=np.float32)
+    padded[:K, :N] = fb
+    # (k // 4, k % 4, n // 16, n % 16) -> (k // 4, n // 16, k % 4, n % 16)
+    return np.ascontiguousarray(padded.reshape(k4 // 4, 4, nt, 16).transpose(0, 2, 1, 3)).reshape(-1)
+
+
 def centroid_freqs(sample_rate: int, n_fft: int) -> np.ndarray:
     """float32[1 + n_fft // 2]: the reference's ``torch.linspace(0, sample_rate // 2, 1 + n_fft // 2)``."""
     return torch.linspace(0, sample_rate // 2, steps=1 + n_fft // 2).numpy()

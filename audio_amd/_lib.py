@@ -229,6 +229,9 @@ _SIGS = {
     "aamd_sinc_impulse_response": (C.c_int, [C.c_int32, _P, _P, C.c_int64, C.c_int32, C.c_int32, _P]),
     "aamd_frequency_impulse_response": (C.c_int, [C.c_int32, _P, _P, _P, C.c_int64, C.c_int32, _P]),
     "aamd_extend_pitch": (C.c_int, [C.c_int32, _P, _P, _P, C.c_int64, C.c_int64, _P]),
+    # dense filterbank projection (additions to ABI 7)
+    "aamd_dense_fbank_tiles": (C.c_int32, [C.c_int32]),
+    "aamd_dense_fbank": (C.c_int, [C.c_int32, _P, _P, _P] + [C.c_int64] * 5 + [C.c_int32] * 2 + [_P]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS)

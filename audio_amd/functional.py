@@ -26,6 +26,7 @@ from . import _lib
 from . import _shim
 from . import _diff
 from ._host import create_dct, linear_fbanks, melscale_fbanks  # noqa: F401  (re-exported, host-side constants)
+from ._host import barkscale_fbanks, chroma_filterbank  # noqa: F401  (prototype.functional's, re-exported likewise)
 
 __all__ = [
     "spectrogram", "inverse_spectrogram", "griffinlim", "phase_vocoder", "pitch_shift", "speed", "amplitude_to_DB", "melscale_fbanks", "create_dct", "resample",
@@ -45,6 +46,7 @@ __all__ = [
     "ray_tracing", "ray_tracing_batch", "ray_tiles",
     "oscillator_bank", "filter_waveform", "sinc_impulse_response", "frequency_impulse_response", "adsr_envelope", "extend_pitch",
     "dsp_tiles",
+    "barkscale_fbanks", "chroma_filterbank", "dense_fbank_scale", "dense_fbank_tiles",
 ]
 
 # --------------------------------------------------------------------------- #
@@ -3663,6 +3665,82 @@ def inverse_mel_scale(melspec: Tensor, fb: Tensor, log_input: bool = False) -> T
         _lib.check(_lib.lib().aamd_inverse_mel(_SA_DTYPES[x3.dtype], x3.data_ptr(), P.data_ptr(), out.data_ptr(), x3.shape[0],
                                                T_, sr, sm, st, n_stft, n_mels, int(bool(log_input)),
                                                _lib.current_stream(melspec.device)))
+    return out.transpose(-1, -2)
+
+
+# --------------------------------------------------------------------------- #
+# Dense filterbank projection (csrc/dense_fbank.h): ChromaScale               #
+# --------------------------------------------------------------------------- #
+_DFB_PINNED: dict = {}               # id(W) -> W: operand images a captured graph reads, kept for the life of the process
+
+
+def dense_fbank_tiles() -> Tuple[int, int, int, int]:
+    """(frames of one row per workgroup, bins of n_freqs per LDS tile, the most outputs, the most frequency bins the kernel
+    serves) of csrc/dense_fbank.h (dfb::kFrames, dfb::kTileK, dfb::kMaxN, dfb::kMaxK)."""
+    lib = _lib.lib()
+    return tuple(int(lib.aamd_dense_fbank_tiles(i)) for i in range(4))
+
+
+def _dense_fbank_image(fb: Tensor, device) -> Tensor:
+    """The float32 values of `fb` on `device` in the order the kernel's A operand is read (`_host.dense_fbank_fragments`),
+    padded with zeros to a multiple of 16 outputs and of 4 bins.  Cached per buffer like every constant derived from one
+    (identity, in-place version, storage).  Building it copies `fb` to the host, which a graph capture cannot do: the first
+    call must run eagerly."""
+    def make():
+        if fb.is_cuda and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("audio_amd: the operand image of this filterbank is not on the device yet and cannot be built "
+                               "inside a graph capture (it needs the filterbank on the host); run the call once eagerly "
+                               "before capturing it")
+        w = _host.dense_fbank_fragments(fb.detach().to(torch.float32).cpu().numpy())
+        return torch.from_numpy(w).to(device)
+    w = _tensor_cached(fb, ("dense_fbank", str(device)), make)
+    if w.is_cuda and torch.cuda.is_current_stream_capturing():
+        with _CACHE_LOCK:
+            _DFB_PINNED[id(w)] = w            # (an id is not reused while its tensor is held here)
+    return w
+
+
+def dense_fbank_scale(specgram: Tensor, fb: Tensor) -> Tensor:
+    r"""EXTENSION (as ``mel_scale`` is): the projection of a spectrogram onto a DENSE filterbank ``fb`` of shape
+    ``(n_freqs, n_out)`` -- ``ChromaScale.forward``: ``(..., n_freqs, time) -> (..., n_out, time)``,
+    ``matmul(specgram^T, fb)^T`` per row.
+
+    One launch (csrc/dense_fbank.h) on the float32 matrix instructions: FMA chains in ascending frequency, one accumulator
+    per output, so the bits do not depend on layout, alignment, batch or tiling.  float32, float16 and bfloat16 are read in
+    place (unit stride along freq -- the frame-major view every ``Spectrogram`` here returns -- or along time; anything else
+    is gathered first), computed in float32 and rounded once.  The result is frame-major, returned as the
+    ``(..., n_out, time)`` view, ``MelScale``'s convention.  ``n_out`` up to 128 and ``n_freqs`` up to 4097
+    (``NotImplementedError`` beyond).  float64 input, or an input or ``fb`` that requires grad under grad mode, takes
+    ``torch.matmul`` (the precision / training path; gradients reach ``fb``).  The first call for a filterbank lays it out on
+    the host and cannot run inside a graph capture; later calls can.  A plain Python entry point through the C ABI (not a
+    dispatcher op)."""
+    if not isinstance(specgram, Tensor) or not isinstance(fb, Tensor):
+        raise TypeError("audio_amd: dense_fbank_scale: specgram and fb must be tensors")
+    if specgram.dtype not in _WA_FLOATS:
+        raise TypeError(f"audio_amd: dense_fbank_scale: specgram must be float16, bfloat16, float32 or float64 (got {specgram.dtype})")
+    if fb.dim() != 2 or not fb.is_floating_point():
+        raise ValueError(f"audio_amd: dense_fbank_scale: fb must be a floating-point (n_freqs, n_out) matrix (got {tuple(fb.shape)})")
+    n_freqs, n_out = int(fb.shape[0]), int(fb.shape[1])
+    if specgram.dim() < 2 or specgram.shape[-2] != n_freqs:
+        raise ValueError("audio_amd: dense_fbank_scale: expected an input with {} frequency bins, the filterbank's. Found: {}".format(
+            n_freqs, specgram.shape[-2] if specgram.dim() >= 2 else tuple(specgram.shape)))
+    _wa_require(specgram, "dense_fbank_scale: specgram")
+    if specgram.dtype == torch.float64 or (torch.is_grad_enabled() and (specgram.requires_grad or fb.requires_grad)):
+        return torch.matmul(specgram.transpose(-1, -2), fb.to(device=specgram.device, dtype=specgram.dtype)).transpose(-1, -2)
+    _, _, max_out, max_freqs = dense_fbank_tiles()
+    if n_out > max_out:
+        raise NotImplementedError(f"audio_amd: dense_fbank_scale serves up to {max_out} outputs (got {n_out})")
+    if n_freqs > max_freqs:
+        raise NotImplementedError(f"audio_amd: dense_fbank_scale serves up to {max_freqs} frequency bins (got {n_freqs})")
+    lead, T_ = tuple(specgram.shape[:-2]), int(specgram.shape[-1])
+    out = torch.empty(lead + (T_, n_out), dtype=specgram.dtype, device=specgram.device)
+    if out.numel() == 0 or n_freqs == 0:
+        return out.zero_().transpose(-1, -2)
+    x3, sr, sk, st = _imel_rows(specgram.detach())
+    W = _dense_fbank_image(fb, specgram.device)
+    with torch.cuda.device(specgram.device):
+        _lib.check(_lib.lib().aamd_dense_fbank(_SA_DTYPES[x3.dtype], x3.data_ptr(), W.data_ptr(), out.data_ptr(), x3.shape[0],
+                                               T_, sr, sk, st, n_freqs, n_out, _lib.current_stream(specgram.device)))
     return out.transpose(-1, -2)
 
 

@@ -1,7 +1,8 @@
 """Drop-in replacements for the hot-path modules of ``torchaudio.transforms``:
 Spectrogram, MelScale, MelSpectrogram, AmplitudeToDB, MFCC, Resample, FFTConvolve, ComputeDeltas, SlidingWindowCmn,
 FrequencyMasking, TimeMasking, SpecAugment, AddNoise, Preemphasis, Deemphasis, Convolve, PSD, MVDR, SoudenMVDR, RTFMVDR,
-RNNTLoss, Vad, LFCC, SpectralCentroid, MuLawEncoding, MuLawDecoding, Fade, Vol.
+RNNTLoss, Vad, LFCC, SpectralCentroid, MuLawEncoding, MuLawDecoding, Fade, Vol, and of ``torchaudio.prototype.transforms``:
+BarkScale, InverseBarkScale, BarkSpectrogram, ChromaScale, ChromaSpectrogram.
 
 Constructor / forward signatures, registered buffer names (``window``, ``fb``, ``dct_mat``,
 ``kernel``), shapes, strides, warnings and error messages follow
@@ -36,7 +37,7 @@ __all__ = ["Spectrogram", "InverseSpectrogram", "GriffinLim", "TimeStretch", "Pi
            "MelScale", "InverseMelScale", "MelSpectrogram", "AmplitudeToDB", "MFCC", "Resample", "FFTConvolve", "ComputeDeltas",
            "SlidingWindowCmn", "FrequencyMasking", "TimeMasking", "SpecAugment", "AddNoise", "Preemphasis", "Deemphasis",
            "Convolve", "PSD", "MVDR", "SoudenMVDR", "RTFMVDR", "RNNTLoss", "Vad", "LFCC", "SpectralCentroid", "MuLawEncoding",
-           "MuLawDecoding", "Fade", "Vol"]
+           "MuLawDecoding", "Fade", "Vol", "BarkScale", "InverseBarkScale", "BarkSpectrogram", "ChromaScale", "ChromaSpectrogram"]
 
 
 class Spectrogram(torch.nn.Module):
@@ -559,6 +560,214 @@ class MelSpectrogram(torch.nn.Module):
         # operator above is the same function), with this module's own launch plans
         return F._melspectrogram_module(waveform, sp.window, self.mel_scale.fb, sp.pad, sp.n_fft, sp.hop_length, sp.win_length,
                                         sp.power, sp.normalized, sp.center, sp.pad_mode, self._plans)
+
+
+class BarkScale(torch.nn.Module):
+    r"""STFT bins -> Bark bins with triangular filters (reference: prototype.transforms.BarkScale):
+    ``(..., n_stft, time) -> (..., n_barks, time)``.  The filterbank is banded, so ``forward`` is ``F.mel_scale`` on it: the
+    banded kernel ``MelScale`` runs."""
+    __constants__ = ["n_barks", "sample_rate", "f_min", "f_max"]
+
+    def __init__(
+        self,
+        n_barks: int = 128,
+        sample_rate: int = 16000,
+        f_min: float = 0.0,
+        f_max: Optional[float] = None,
+        n_stft: int = 201,
+        bark_scale: str = "traunmuller",
+    ) -> None:
+        super().__init__()
+        self.n_barks = n_barks
+        self.sample_rate = sample_rate
+        self.f_max = f_max if f_max is not None else float(sample_rate // 2)
+        self.f_min = f_min
+        self.bark_scale = bark_scale
+        if f_min > self.f_max:
+            raise ValueError("Require f_min: {} <= f_max: {}".format(f_min, self.f_max))
+        fb = F.barkscale_fbanks(n_stft, self.f_min, self.f_max, self.n_barks, self.sample_rate, self.bark_scale)
+        self.register_buffer("fb", fb)
+
+    def forward(self, specgram: Tensor) -> Tensor:
+        return F.mel_scale(specgram, self.fb)
+
+
+class InverseBarkScale(torch.nn.Module):
+    r"""Bark bins -> STFT bins (reference: prototype.transforms.InverseBarkScale):
+    ``(..., n_barks, time) -> (..., n_stft, time)``.
+
+    STATED DIFFERENCE: the reference minimises ``|barkspec - fb^T x|`` by SGD from a random start.  Here the result is the
+    ``InverseMelScale`` definition on the Bark filterbank -- ``relu(P @ barkspec)`` with ``P`` the float64 pseudo-inverse of
+    ``fb^T`` cut at float32's rank, the minimum-norm least-squares solution, one launch (``F.inverse_mel_scale``) --
+    deterministic and what the iteration converges towards.  ``max_iter``, ``tolerance_loss``, ``tolerance_change`` and
+    ``sgdargs`` are stored and unused."""
+    __constants__ = ["n_stft", "n_barks", "sample_rate", "f_min", "f_max", "max_iter", "tolerance_loss", "tolerance_change"]
+
+    def __init__(
+        self,
+        n_stft: int,
+        n_barks: int = 128,
+        sample_rate: int = 16000,
+        f_min: float = 0.0,
+        f_max: Optional[float] = None,
+        max_iter: int = 100000,
+        tolerance_loss: float = 1e-5,
+        tolerance_change: float = 1e-8,
+        sgdargs: Optional[dict] = None,
+        bark_scale: str = "traunmuller",
+    ) -> None:
+        super().__init__()
+        self.n_barks = n_barks
+        self.sample_rate = sample_rate
+        self.f_max = f_max if f_max is not None else float(sample_rate // 2)
+        self.f_min = f_min
+        self.n_stft = n_stft
+        self.max_iter = max_iter
+        self.tolerance_loss = tolerance_loss
+        self.tolerance_change = tolerance_change
+        self.sgdargs = sgdargs or {"lr": 0.1, "momentum": 0.9}
+        self.bark_scale = bark_scale
+        if f_min > self.f_max:
+            raise ValueError("Require f_min: {} <= f_max: {}".format(f_min, self.f_max))
+        fb = F.barkscale_fbanks(n_stft, self.f_min, self.f_max, self.n_barks, self.sample_rate, self.bark_scale)
+        self.register_buffer("fb", fb)
+
+    def forward(self, barkspec: Tensor) -> Tensor:
+        return F.inverse_mel_scale(barkspec, self.fb)
+
+
+class BarkSpectrogram(torch.nn.Module):
+    r"""Bark spectrogram of ``(..., time)`` audio (reference: prototype.transforms.BarkSpectrogram).  ``forward`` is
+    ``MelSpectrogram``'s eager route with the Bark filterbank: the same ONE fused launch, dtypes and gradient routes."""
+    __constants__ = ["sample_rate", "n_fft", "win_length", "hop_length", "pad", "n_barks", "f_min"]
+
+    def __init__(
+        self,
+        sample_rate: int = 16000,
+        n_fft: int = 400,
+        win_length: Optional[int] = None,
+        hop_length: Optional[int] = None,
+        f_min: float = 0.0,
+        f_max: Optional[float] = None,
+        pad: int = 0,
+        n_barks: int = 128,
+        window_fn: Callable[..., Tensor] = torch.hann_window,
+        power: float = 2.0,
+        normalized: bool = False,
+        wkwargs: Optional[dict] = None,
+        center: bool = True,
+        pad_mode: str = "reflect",
+        bark_scale: str = "traunmuller",
+    ) -> None:
+        super().__init__()
+        self.sample_rate = sample_rate
+        self.n_fft = n_fft
+        self.win_length = win_length if win_length is not None else n_fft
+        self.hop_length = hop_length if hop_length is not None else self.win_length // 2
+        self.pad = pad
+        self.power = power
+        self.normalized = normalized
+        self.n_barks = n_barks
+        self.f_max = f_max
+        self.f_min = f_min
+        self.spectrogram = Spectrogram(
+            n_fft=self.n_fft, win_length=self.win_length, hop_length=self.hop_length, pad=self.pad,
+            window_fn=window_fn, power=self.power, normalized=self.normalized, wkwargs=wkwargs,
+            center=center, pad_mode=pad_mode, onesided=True,
+        )
+        self.bark_scale = BarkScale(self.n_barks, self.sample_rate, self.f_min, self.f_max, self.n_fft // 2 + 1, bark_scale)
+        self._plans: dict = {}      # per-(shape, device, buffer version) launch plans of the inference path
+
+    def __getstate__(self):
+        state = self.__dict__.copy()
+        state["_plans"] = {}            # launch plans hold op handles and device tensors: rebuilt on first use
+        return state
+
+    def forward(self, waveform: Tensor) -> Tensor:
+        sp = self.spectrogram
+        return F._melspectrogram_module(waveform, sp.window, self.bark_scale.fb, sp.pad, sp.n_fft, sp.hop_length, sp.win_length,
+                                        sp.power, sp.normalized, sp.center, sp.pad_mode, self._plans)
+
+
+class ChromaScale(torch.nn.Module):
+    r"""STFT bins -> chroma (pitch class) bins (reference: prototype.transforms.ChromaScale):
+    ``(..., n_freqs, time) -> (..., n_chroma, time)``.  The chroma filterbank is dense, so ``forward`` is
+    ``F.dense_fbank_scale``: one launch of the dense projection kernel (csrc/dense_fbank.h); a plain Python entry point, so
+    the module is not scriptable as one op."""
+    __constants__ = ["sample_rate", "n_freqs", "n_chroma"]
+
+    def __init__(
+        self,
+        sample_rate: int,
+        n_freqs: int,
+        *,
+        n_chroma: int = 12,
+        tuning: float = 0.0,
+        ctroct: float = 5.0,
+        octwidth: Optional[float] = 2.0,
+        norm: int = 2,
+        base_c: bool = True,
+    ) -> None:
+        super().__init__()
+        self.sample_rate = sample_rate
+        self.n_freqs = n_freqs
+        self.n_chroma = n_chroma
+        fb = F.chroma_filterbank(sample_rate, n_freqs, n_chroma, tuning=tuning, ctroct=ctroct, octwidth=octwidth, norm=norm,
+                                 base_c=base_c)
+        self.register_buffer("fb", fb)
+
+    def forward(self, specgram: Tensor) -> Tensor:
+        return F.dense_fbank_scale(specgram, self.fb)
+
+
+class ChromaSpectrogram(torch.nn.Module):
+    r"""Chromagram of ``(..., time)`` audio (reference: prototype.transforms.ChromaSpectrogram): ``(..., n_chroma, time)``.
+    Two launches and no layout copy: the spectrogram of whichever STFT family serves ``n_fft``, then the dense projection
+    over its frame-major memory.  ``power=None`` (a complex spectrogram) raises ``ValueError`` here, at construction; the
+    reference fails later, inside ``matmul``."""
+    __constants__ = ["sample_rate", "n_fft", "win_length", "hop_length", "pad", "n_chroma"]
+
+    def __init__(
+        self,
+        sample_rate: int,
+        n_fft: int,
+        *,
+        win_length: Optional[int] = None,
+        hop_length: Optional[int] = None,
+        pad: int = 0,
+        window_fn: Callable[..., Tensor] = torch.hann_window,
+        power: float = 2.0,
+        normalized: bool = False,
+        wkwargs: Optional[dict] = None,
+        center: bool = True,
+        pad_mode: str = "reflect",
+        n_chroma: int = 12,
+        tuning: float = 0.0,
+        ctroct: float = 5.0,
+        octwidth: Optional[float] = 2.0,
+        norm: int = 2,
+        base_c: bool = True,
+    ) -> None:
+        super().__init__()
+        if power is None:
+            raise ValueError("audio_amd: ChromaSpectrogram needs a real power (got None): the chroma filterbank is applied "
+                             "to a power or magnitude spectrogram")
+        self.sample_rate = sample_rate
+        self.n_fft = n_fft
+        self.win_length = win_length if win_length is not None else n_fft
+        self.hop_length = hop_length if hop_length is not None else self.win_length // 2
+        self.pad = pad
+        self.n_chroma = n_chroma
+        self.spectrogram = Spectrogram(
+            n_fft=self.n_fft, win_length=self.win_length, hop_length=self.hop_length, pad=self.pad,
+            window_fn=window_fn, power=power, normalized=normalized, wkwargs=wkwargs,
+            center=center, pad_mode=pad_mode, onesided=True,
+        )
+        self.chroma_scale = ChromaScale(sample_rate, n_fft // 2 + 1, n_chroma=n_chroma, tuning=tuning, ctroct=ctroct,
+                                        octwidth=octwidth, norm=norm, base_c=base_c)
+
+    def forward(self, waveform: Tensor) -> Tensor:
+        return self.chroma_scale(self.spectrogram(waveform))
 
 
 class MFCC(torch.nn.Module):

@@ -70,6 +70,8 @@
  *                             batch of rooms per call; fixed-point sums, two launches -- an addition to ABI 7
  *   aamd_oscillator_bank, aamd_filter_waveform, aamd_sinc_impulse_response, aamd_frequency_impulse_response,
  *   aamd_extend_pitch         the synthesis ops of prototype.functional -- additions to ABI 7 as well
+ *   aamd_dense_fbank          F.dense_fbank_scale / prototype.transforms.ChromaScale (a matmul with a dense (n_freqs, n_chroma)
+ *                             filterbank in the reference); one launch -- an addition to ABI 7 as well
  *   aamd_detect_pitch_f32     F.detect_pitch_frequency (_compute_nccf + _find_max_per_frame + _median_smoothing in the
  *                             reference; an addition to ABI 7 as well)
  *
@@ -1022,6 +1024,28 @@ int aamd_frequency_impulse_response(int32_t dtype, const void* magnitudes, const
 /* prototype.functional.extend_pitch: out[i][k] = base[i] * pattern[k], i < count, k < n, of `dtype`; the half types
  * multiply in float32 and round once.  One launch. */
 int aamd_extend_pitch(int32_t dtype, const void* base, const void* pattern, void* out, int64_t count, int64_t n, void* stream);
+
+/* ---- Dense filterbank projection (additions to ABI 7; csrc/dense_fbank.h) -------------------------------------------- */
+
+#define AAMD_DENSE_FBANK_MAX_OUT 128    /* the most outputs (filters) the kernel serves: 8 accumulators per wave */
+#define AAMD_DENSE_FBANK_MAX_FREQS 4097 /* the most frequency bins: n_fft = 8192 */
+
+/* which = 0: frames of one row per workgroup; 1: bins of n_freqs per LDS tile; 2: the most outputs; 3: the most bins (the
+ * defines above). */
+int32_t aamd_dense_fbank_tiles(int32_t which);
+
+/* F.dense_fbank_scale / T.ChromaScale: out[r][t][n] = sum_k x[r][k][t] * w[k][n].  x is (rows, n_freqs, frames) of `dtype`
+ * (AAMD_SA_F32 / F16 / BF16) read in place through its strides in elements: unit stride along freq (stride_freq == 1:
+ * frame-major) or along time (stride_frame == 1); anything else is AAMD_EINVAL (gather first).  w is the (n_freqs, n_out)
+ * float32 filterbank on the device, 16-byte aligned, in the order the kernel reads it: K4 / 4 * NT * 64 floats (K4 = n_freqs
+ * rounded up to 4, NT = ceil(n_out / 16)), element (k, n) at ((k / 4) * NT + n / 16) * 64 + (k % 4) * 16 + n % 16, zeros
+ * beyond n_freqs and n_out (_host.dense_fbank_fragments).  out is dense (rows, frames, n_out) of `dtype`.  float32 FMA
+ * chains in ascending k on the matrix cores, one accumulator per output, rounded once to `dtype`: the result does not
+ * depend on the layout, the alignment, the number of rows or the tiling of k.  n_out > AAMD_DENSE_FBANK_MAX_OUT or
+ * n_freqs > AAMD_DENSE_FBANK_MAX_FREQS: AAMD_EUNSUPPORTED.  One launch. */
+int aamd_dense_fbank(int32_t dtype, const void* x, const float* w, void* out, int64_t rows, int64_t frames,
+                     int64_t stride_row, int64_t stride_freq, int64_t stride_frame, int32_t n_freqs, int32_t n_out,
+                     void* stream);
 
 #ifdef __cplusplus
 }

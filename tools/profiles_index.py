@@ -6,7 +6,8 @@ import re
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DESC = [
     (r'r0\d_.*fuzz_generic_census.*', "pytest tests/test_gpu_fuzz_generic.py -s on an MI355X: per case the kernel instantiation, radix plan, pairs per block, blocks, LDS layout and the achieved fraction of its per-row bar (Kaldi: of `kaldi_fuzz_cases.judge`'s tolerance), the worst fraction per instantiation, 168 passed in 4.1 s", 'DESIGN 2 (generic-kernel census)'),
-    (r'r0\d_.*bench_dsp.*', "tools/bench_dsp.py: F.oscillator_bank on (16, 64000, 64) and (256, 16000, 1) and F.filter_waveform on (64, 160000) with 1000 filters of 513 and of 65 taps and on (4, 16000) with 16000 filters of 65 taps, float32, rotating over three draws of the inputs, beside the reference's compositions restated in torch on the same device (remainder, float64 cumsum cast back unreduced, sin, sum; unfold, per-chunk FFT convolution, overlap-add, crop), both by one protocol in alternating rounds, with the bytes and multiply-adds of each call as rates", 'DESIGN 4.23, README kernel table'),
+    (r'r0\d_.*bench_bark_chroma.*', "tools/bench_bark_chroma.py: T.ChromaScale (the dense projection of csrc/dense_fbank.h, 12 chroma) on the frame-major spectrogram of (256, 160000) at n_fft 400 / hop 200 and of (32, 441000) at n_fft 2048 / hop 512, float32, inputs rotating over more than twice the Infinity Cache, beside matmul(spec^T, fb) restated in torch on the same tensors, both by one protocol in alternating rounds, with the spectrogram's bytes at 8 TB/s as the roofline; T.ChromaSpectrogram end to end beside Spectrogram + the restated matmul; T.BarkSpectrogram beside T.MelSpectrogram of the same shape", 'DESIGN 4.25, README kernel table'),
+    (r'r0\d_.*bench_dsp.*',"tools/bench_dsp.py: F.oscillator_bank on (16, 64000, 64) and (256, 16000, 1) and F.filter_waveform on (64, 160000) with 1000 filters of 513 and of 65 taps and on (4, 16000) with 16000 filters of 65 taps, float32, rotating over three draws of the inputs, beside the reference's compositions restated in torch on the same device (remainder, float64 cumsum cast back unreduced, sin, sum; unfold, per-chunk FFT convolution, overlap-add, crop), both by one protocol in alternating rounds, with the bytes and multiply-adds of each call as rates", 'DESIGN 4.23, README kernel table'),
     (r'r0\d_.*bench_ray.*', "tools/bench_ray.py: F.ray_tracing_batch on 256 rooms x 4 microphones x 10 000 rays, one band, time_thres 1.0, with scattering 0 and 0.2, and on 1 room x 8 microphones x 100 000 rays x 7 bands, float32, rotating over two draws of rooms, beside the definition restated in torch on the same device (all rays in lockstep under masks, index_add_, float64; 8 rooms scaled to 256), both by one protocol in alternating rounds, with the number of 8-byte atomic adds and their rate", 'DESIGN 4.24, README kernel table'),
     (r'r0\d_.*bench_rir.*', "tools/bench_rir.py: F.simulate_rir_ism_batch on 256 rooms x 4 microphones at order 17 with 8192 samples and on 1 room x 8 microphones at order 10 with 4096 samples, float32, rotating over three draws of rooms, beside the reference's scatter form restated in torch on the same device (4 rooms scaled to 256), both by one protocol in alternating rounds, with the number of taps inside the output", 'DESIGN 4.22, README kernel table'),
     (r'r0\d_.*bench_spectral_pointwise.*', "tools/bench_spectral_pointwise.py: F.gain, T.Vol, F.contrast, F.DB_to_amplitude, the mu-law pair, T.Fade, F.spectral_centroid (whole and per launch, n_fft 400 / 512 / 480) and T.LFCC on (256, 160000) float32 (float16 for two rows), inputs rotating over more than twice the Infinity Cache, beside the reference's compositions restated in torch and torch.clone of the same tensors, alternating rounds", 'DESIGN 4.20, 4.21, README kernel table'),
