@@ -232,6 +232,12 @@ _SIGS = {
     # dense filterbank projection (additions to ABI 7)
     "aamd_dense_fbank_tiles": (C.c_int32, [C.c_int32]),
     "aamd_dense_fbank": (C.c_int, [C.c_int32, _P, _P, _P] + [C.c_int64] * 5 + [C.c_int32] * 2 + [_P]),
+    # batched edit distance (additions to ABI 7)
+    "aamd_edit_distance_states_per_lane": (C.c_int32, [C.c_int64]),
+    "aamd_edit_distance_threads": (C.c_int32, [C.c_int64]),
+    "aamd_edit_distance_max_ref": (C.c_int32, []),
+    "aamd_edit_distance_max_hyp": (C.c_int32, []),
+    "aamd_edit_distance": (C.c_int, [_P, C.c_int32] * 4 + [C.c_int64] * 4 + [C.c_int32, _P, _P]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS)

@@ -47,6 +47,7 @@ __all__ = [
     "oscillator_bank", "filter_waveform", "sinc_impulse_response", "frequency_impulse_response", "adsr_envelope", "extend_pitch",
     "dsp_tiles",
     "barkscale_fbanks", "chroma_filterbank", "dense_fbank_scale", "dense_fbank_tiles",
+    "edit_distance", "edit_distance_batch", "edit_distance_tiles",
 ]
 
 # --------------------------------------------------------------------------- #
@@ -5037,6 +5038,111 @@ def merge_tokens(tokens: Tensor, scores: Tensor, blank: int = 0) -> List[TokenSp
     edges = [0] + (np.flatnonzero(tok[1:] != tok[:-1]) + 1).tolist() + [n]
     return [TokenSpan(token=int(tok[s]), start=s, end=e, score=float(sc[s:e].mean()))
             for s, e in zip(edges[:-1], edges[1:]) if tok[s] != blank]
+
+
+# --------------------------------------------------------------------------- #
+# batched edit distance (csrc/edit_distance.h)                                #
+# --------------------------------------------------------------------------- #
+EDIT_MAX_REF = 4096                  # AAMD_EDIT_DISTANCE_MAX_REF: the widest reference axis the kernel serves
+EDIT_MAX_HYP = 32767                 # AAMD_EDIT_DISTANCE_MAX_HYP: the widest hypothesis axis
+
+
+def edit_distance_tiles() -> Tuple[Tuple[Tuple[int, int, int], ...], int, int]:
+    """(((largest reference width M, rows per lane, lanes per workgroup) of every configuration, by M), largest M, largest
+    hypothesis width N) of csrc/edit_distance.h."""
+    lib = _lib.lib()
+    configs, prev = [], None
+    for M in range(EDIT_MAX_REF + 1):
+        cur = (int(lib.aamd_edit_distance_states_per_lane(M)), int(lib.aamd_edit_distance_threads(M)))
+        if cur != prev and prev is not None:
+            configs.append((M - 1,) + prev)
+        prev = cur
+    configs.append((EDIT_MAX_REF,) + prev)
+    return tuple(configs), int(lib.aamd_edit_distance_max_ref()), int(lib.aamd_edit_distance_max_hyp())
+
+
+def _edit_distance_check(hyps: Tensor, refs: Tensor, hyp_lengths: Optional[Tensor], ref_lengths: Optional[Tensor]) -> None:
+    """The host-side checks of F.edit_distance_batch.  Nothing is read from the device."""
+    if hyps.dim() < 1 or refs.dim() < 1:
+        raise ValueError(f"hyps and refs need a token axis, got {tuple(hyps.shape)} and {tuple(refs.shape)}")
+    lead, rlead = tuple(hyps.shape[:-1]), tuple(refs.shape[:-1])
+    if len(rlead) > len(lead) or lead[:len(rlead)] != rlead:
+        raise ValueError(f"the leading axes of refs {rlead} must be a prefix of those of hyps {lead}")
+    for t, what, want in ((hyp_lengths, "hyp_lengths", lead), (ref_lengths, "ref_lengths", rlead)):
+        if t is not None and tuple(t.shape) != want:
+            raise ValueError(f"{what} must have the shape {want}, got {tuple(t.shape)}")
+    tensors = [(hyps, "hyps"), (refs, "refs")] + [(t, what) for t, what in ((hyp_lengths, "hyp_lengths"),
+                                                                             (ref_lengths, "ref_lengths")) if t is not None]
+    for t, what in tensors:
+        if t.dtype not in _ALIGN_INTS:
+            raise TypeError(f"{what} must be int32 or int64 (got {t.dtype})")
+    for t, what in tensors:
+        if not t.is_contiguous():
+            raise ValueError(f"{what} must be contiguous")
+    if refs.shape[-1] > EDIT_MAX_REF or hyps.shape[-1] > EDIT_MAX_HYP:
+        raise NotImplementedError(f"audio_amd: edit_distance serves references up to M = {EDIT_MAX_REF} tokens and hypotheses up "
+                                  f"to N = {EDIT_MAX_HYP} (got M = {refs.shape[-1]}, N = {hyps.shape[-1]}): the reference of one "
+                                  "pair lies across the registers of one workgroup; the distance is symmetric, so the arguments "
+                                  "may be swapped (which swaps deletions and insertions)")
+    for t, what in tensors:
+        if not t.is_cuda:
+            raise RuntimeError(f"audio_amd: {what} must be on an MI355X (ROCm) device, got {t.device}. "
+                               "The HIP kernels have no CPU fallback.")
+        if t.device != hyps.device:
+            raise RuntimeError(f"audio_amd: {what} must be on the hyps' device")
+
+
+def edit_distance_batch(hyps: Tensor, refs: Tensor, hyp_lengths: Optional[Tensor] = None, ref_lengths: Optional[Tensor] = None,
+                        return_ops: bool = False) -> Tensor:
+    r"""Levenshtein distance of every hypothesis ``hyps`` ``(*lead, N)`` to its reference ``refs`` ``(*rlead, M)``, ``rlead`` a
+    prefix of ``lead``: a reference serves the whole block of hypotheses beneath it, so the ``(B, nbest, N)`` tokens of
+    ``ctc_beam_search`` go against ``(B, M)`` transcripts as they are.  Tokens are int32 or int64 (the two tensors may differ;
+    they are compared as integers), lengths int32 or int64 of the shapes ``lead`` / ``rlead`` (``None``: the full width).
+    Returns int32 ``lead``: the distance; with ``return_ops`` int32 ``(*lead, 4)``: (distance, substitutions, deletions,
+    insertions) of one fixed optimal alignment -- every cell takes the first of diagonal, deletion (a reference token without a
+    partner), insertion whose cost is smallest -- so ``distance == S + D + I`` and ``N_p == M_p - D + I``.  A pair whose length
+    lies outside ``[0, N]`` / ``[0, M]`` (the ``-1`` of a hypothesis the beam did not hold) gets ``-1`` in every field, and no
+    token of it is read.  One launch, lengths read on the device, no synchronisation, nothing cached: the first call can be
+    captured in a graph.  Integers only: two calls give the same bits, and row p of a batch equals the pair alone.  No
+    gradient.  References beyond ``EDIT_MAX_REF`` or hypotheses beyond ``EDIT_MAX_HYP`` tokens raise NotImplementedError.  A
+    plain Python entry point through the C ABI: not registered as a dispatcher op."""
+    _edit_distance_check(hyps, refs, hyp_lengths, ref_lengths)
+    lead = tuple(hyps.shape[:-1])
+    pairs, rows = math.prod(lead), math.prod(refs.shape[:-1])
+    out = torch.empty(lead + ((4,) if return_ops else ()), dtype=torch.int32, device=hyps.device)
+    if pairs:
+        is64 = lambda t: int(t is not None and t.dtype == torch.int64)   # noqa: E731
+        p = lambda t: (_lib.ptr(t) or None) if t is not None else None   # noqa: E731
+        with torch.cuda.device(hyps.device):
+            _lib.check(_lib.lib().aamd_edit_distance(p(hyps), is64(hyps), p(refs), is64(refs), p(hyp_lengths), is64(hyp_lengths),
+                                                     p(ref_lengths), is64(ref_lengths), pairs, pairs // rows, hyps.shape[-1],
+                                                     refs.shape[-1], int(bool(return_ops)), out.data_ptr(),
+                                                     _lib.current_stream(hyps.device)))
+    return out
+
+
+def edit_distance(seq1, seq2) -> int:
+    r"""Levenshtein distance of two sequences (reference: F.edit_distance, a Python loop over the cells on the host), ``seq1``
+    taken as the reference of ``edit_distance_batch``.  Two 1-D integer tensors on the device go to the kernel as one pair;
+    any other pair of Python sequences (strings, lists of words) is interned to ids with a dict on the host, uploaded to the
+    current ROCm device and goes the same way.  The Python ``int`` costs one small device-to-host copy, so this entry point
+    synchronises and cannot be captured in a graph; ``edit_distance_batch`` can."""
+    t1, t2 = isinstance(seq1, Tensor), isinstance(seq2, Tensor)
+    if t1 != t2:
+        raise TypeError("edit_distance takes two tensors or two Python sequences, not one of each")
+    if t1:
+        if seq1.dim() != 1 or seq2.dim() != 1:
+            raise ValueError(f"seq1 and seq2 must be 1-D, got {tuple(seq1.shape)} and {tuple(seq2.shape)}")
+        return int(edit_distance_batch(seq2, seq1).item())
+    if not torch.cuda.is_available():
+        raise RuntimeError("audio_amd: edit_distance must run on an MI355X (ROCm) device and none is available. "
+                           "The HIP kernels have no CPU fallback.")
+    ids: dict = {}
+    a = [ids.setdefault(x, len(ids)) for x in seq1]
+    b = [ids.setdefault(x, len(ids)) for x in seq2]
+    dev = torch.device("cuda", torch.cuda.current_device())
+    both = torch.tensor(a + b, dtype=torch.int32).to(dev)
+    return int(edit_distance_batch(both[len(a):], both[:len(a)]).item())
 
 
 @_reduced_precision_io

@@ -72,6 +72,8 @@
  *   aamd_extend_pitch         the synthesis ops of prototype.functional -- additions to ABI 7 as well
  *   aamd_dense_fbank          F.dense_fbank_scale / prototype.transforms.ChromaScale (a matmul with a dense (n_freqs, n_chroma)
  *                             filterbank in the reference); one launch -- an addition to ABI 7 as well
+ *   aamd_edit_distance        F.edit_distance / F.edit_distance_batch (the reference's Python loop over the cells of one pair on
+ *                             the host); every pair of a batch in one launch, with the error counts -- an addition to ABI 7
  *   aamd_detect_pitch_f32     F.detect_pitch_frequency (_compute_nccf + _find_max_per_frame + _median_smoothing in the
  *                             reference; an addition to ABI 7 as well)
  *
@@ -1046,6 +1048,31 @@ int32_t aamd_dense_fbank_tiles(int32_t which);
 int aamd_dense_fbank(int32_t dtype, const void* x, const float* w, void* out, int64_t rows, int64_t frames,
                      int64_t stride_row, int64_t stride_freq, int64_t stride_frame, int32_t n_freqs, int32_t n_out,
                      void* stream);
+
+/* ---- Batched edit distance (additions to ABI 7; csrc/edit_distance.h) ------------------------------------------------ */
+
+#define AAMD_EDIT_DISTANCE_MAX_REF 4096  /* the widest reference axis: 256 lanes x 16 rows of one workgroup */
+#define AAMD_EDIT_DISTANCE_MAX_HYP 32767 /* the widest hypothesis axis: the fields of a cell are 16 bits */
+
+/* What the launcher picks for a reference axis of max_m tokens: consecutive rows per lane (4 or 16) and lanes per workgroup
+ * (64 or 256); the two limits (the defines above). */
+int32_t aamd_edit_distance_states_per_lane(int64_t max_m);
+int32_t aamd_edit_distance_threads(int64_t max_m);
+int32_t aamd_edit_distance_max_ref(void);
+int32_t aamd_edit_distance_max_hyp(void);
+
+/* F.edit_distance_batch.  hyps dense (pairs, max_n) and refs dense (pairs / pairs_per_ref, max_m), int32 or int64 each
+ * (hyps_int64, refs_int64; compared as integers); pair p scores hypothesis p against reference p / pairs_per_ref.
+ * hyp_lengths (pairs,) and ref_lengths (pairs / pairs_per_ref,), int32 or int64 each, or null for the full width.  All on
+ * the device and read there: no synchronisation, no workspace.  out is int32 (pairs,): the Levenshtein distance; with
+ * return_ops (pairs, 4): (distance, substitutions, deletions, insertions) of the alignment that takes, cell by cell, the
+ * first of diagonal, deletion (a reference token without a partner), insertion whose cost is smallest.  A pair with a
+ * hypothesis length outside [0, max_n] or a reference length outside [0, max_m] gets -1 in every field, and nothing is
+ * indexed with those values.  max_m > AAMD_EDIT_DISTANCE_MAX_REF or max_n > AAMD_EDIT_DISTANCE_MAX_HYP:
+ * AAMD_EUNSUPPORTED.  One launch, integers only. */
+int aamd_edit_distance(const void* hyps, int32_t hyps_int64, const void* refs, int32_t refs_int64, const void* hyp_lengths,
+                       int32_t hyp_lengths_int64, const void* ref_lengths, int32_t ref_lengths_int64, int64_t pairs,
+                       int64_t pairs_per_ref, int64_t max_n, int64_t max_m, int32_t return_ops, int32_t* out, void* stream);
 
 #ifdef __cplusplus
 }

@@ -5,6 +5,7 @@ import re
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DESC = [
+    (r'r0\d_.*bench_edit_distance.*', "tools/bench_edit_distance.py: F.edit_distance_batch, with and without the error counts, on (32, 10, 1500) int32 hypotheses of 100-300 tokens against (32, 300) references, (256, 1, 400) against (256, 400) and (8, 1, 4000) against (8, 4096), time per call and per DP cell, beside the row recurrence restated in torch on the same device (arange + cummin), both by one protocol in alternating rounds, and the reference's Python loop on the host scaled from two pairs", 'DESIGN 4.26, README kernel table'),
     (r'r0\d_.*fuzz_generic_census.*', "pytest tests/test_gpu_fuzz_generic.py -s on an MI355X: per case the kernel instantiation, radix plan, pairs per block, blocks, LDS layout and the achieved fraction of its per-row bar (Kaldi: of `kaldi_fuzz_cases.judge`'s tolerance), the worst fraction per instantiation, 168 passed in 4.1 s", 'DESIGN 2 (generic-kernel census)'),
     (r'r0\d_.*bench_bark_chroma.*', "tools/bench_bark_chroma.py: T.ChromaScale (the dense projection of csrc/dense_fbank.h, 12 chroma) on the frame-major spectrogram of (256, 160000) at n_fft 400 / hop 200 and of (32, 441000) at n_fft 2048 / hop 512, float32, inputs rotating over more than twice the Infinity Cache, beside matmul(spec^T, fb) restated in torch on the same tensors, both by one protocol in alternating rounds, with the spectrogram's bytes at 8 TB/s as the roofline; T.ChromaSpectrogram end to end beside Spectrogram + the restated matmul; T.BarkSpectrogram beside T.MelSpectrogram of the same shape", 'DESIGN 4.25, README kernel table'),
     (r'r0\d_.*bench_dsp.*',"tools/bench_dsp.py: F.oscillator_bank on (16, 64000, 64) and (256, 16000, 1) and F.filter_waveform on (64, 160000) with 1000 filters of 513 and of 65 taps and on (4, 16000) with 16000 filters of 65 taps, float32, rotating over three draws of the inputs, beside the reference's compositions restated in torch on the same device (remainder, float64 cumsum cast back unreduced, sin, sum; unfold, per-chunk FFT convolution, overlap-add, crop), both by one protocol in alternating rounds, with the bytes and multiply-adds of each call as rates", 'DESIGN 4.23, README kernel table'),
