@@ -226,6 +226,11 @@ _SIGS = {
     "aamd_oscillator_workspace": (C.c_int64, [C.c_int64] * 3),
     "aamd_oscillator_bank": (C.c_int, [C.c_int32] + [_P] * 4 + [C.c_int64] * 5 + [C.c_double, C.c_int32, _P]),
     "aamd_filter_waveform": (C.c_int, [C.c_int32] + [_P] * 3 + [C.c_int64] * 4 + [C.c_int32, C.c_int32, _P]),
+    "aamd_dsp_grad_tiles": (C.c_int32, [C.c_int32]),
+    "aamd_oscillator_grad_workspace": (C.c_int64, [C.c_int64] * 3),
+    "aamd_oscillator_bank_grad": (C.c_int, [C.c_int32] + [_P] * 6 + [C.c_int64] * 5 + [C.c_double, C.c_int32, _P]),
+    "aamd_filter_waveform_grad_workspace": (C.c_int64, [C.c_int64] * 3 + [C.c_int32, C.c_int32]),
+    "aamd_filter_waveform_grad": (C.c_int, [C.c_int32] + [_P] * 6 + [C.c_int64] * 4 + [C.c_int32, C.c_int32, _P]),
     "aamd_sinc_impulse_response": (C.c_int, [C.c_int32, _P, _P, C.c_int64, C.c_int32, C.c_int32, _P]),
     "aamd_frequency_impulse_response": (C.c_int, [C.c_int32, _P, _P, _P, C.c_int64, C.c_int32, _P]),
     "aamd_extend_pitch": (C.c_int, [C.c_int32, _P, _P, _P, C.c_int64, C.c_int64, _P]),

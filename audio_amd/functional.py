@@ -45,7 +45,7 @@ __all__ = [
     "simulate_rir_ism", "simulate_rir_ism_batch", "rir_tiles",
     "ray_tracing", "ray_tracing_batch", "ray_tiles",
     "oscillator_bank", "filter_waveform", "sinc_impulse_response", "frequency_impulse_response", "adsr_envelope", "extend_pitch",
-    "dsp_tiles",
+    "dsp_tiles", "dsp_grad_tiles",
     "barkscale_fbanks", "chroma_filterbank", "dense_fbank_scale", "dense_fbank_tiles",
     "edit_distance", "edit_distance_batch", "edit_distance_tiles",
 ]
@@ -4655,8 +4655,12 @@ def oscillator_bank(frequencies: Tensor, amplitudes: Tensor, sample_rate: float,
     frequencies above Nyquist are silenced without a warning or a synchronisation, so the call can be captured in a graph.
     Two launches (a chunked scan: :func:`dsp_tiles`), no atomics: a sample's bits depend on neither the batch nor the
     length.  A NaN or infinite frequency makes its oscillator NaN from that step on.  At most ``DSP_MAX_OSCILLATORS``
-    oscillators.  An input that requires grad takes the differentiable composition (``_diff.oscillator_bank``).  A plain
-    Python entry point through the C ABI (not registered as a dispatcher op)."""
+    oscillators.  With an input that requires grad the forward is the same two launches (the same bits) and the
+    first-order backward is HIP as well (``csrc/dsp_synth_grad.h``: the forward's phase, ``g sin(phi)`` for the amplitudes
+    and a float64 suffix sum of ``g a' cos(phi)`` in a fixed order for the frequencies; two or three launches, only the
+    gradients that are needed); under ``create_graph=True`` the backward takes the differentiable composition
+    (``_diff.oscillator_bank``), which differentiates to any order.  A plain Python entry point through the C ABI (not
+    registered as a dispatcher op)."""
     what = "oscillator_bank"
     _dsp_tensor(what, "frequencies", frequencies)
     _dsp_tensor(what, "amplitudes", amplitudes)
@@ -4687,7 +4691,14 @@ def oscillator_bank(frequencies: Tensor, amplitudes: Tensor, sample_rate: float,
     if amplitudes.device != frequencies.device:
         raise ValueError(f"audio_amd: {what}: frequencies and amplitudes must be on one device")
     if _dsp_grad(frequencies, amplitudes):
-        return _diff.oscillator_bank(frequencies, amplitudes, float(sample_rate), reduction)
+        if frequencies.numel() == 0:                      # nothing to launch: the composition carries the (empty) graph
+            return _diff.oscillator_bank(frequencies, amplitudes, float(sample_rate), reduction)
+        return _OscillatorBankFunction.apply(frequencies, amplitudes, float(sample_rate), reduction)
+    return _oscillator_bank_launch(frequencies, amplitudes, float(sample_rate), reduction)
+
+
+def _oscillator_bank_launch(frequencies: Tensor, amplitudes: Tensor, sample_rate: float, reduction: str) -> Tensor:
+    T_, N = frequencies.shape[-2:]
     lead = tuple(frequencies.shape[:-2])
     out = torch.empty(lead + ((T_, N) if reduction == "none" else (T_,)), dtype=frequencies.dtype, device=frequencies.device)
     if out.numel() == 0:
@@ -4715,8 +4726,12 @@ def filter_waveform(waveform: Tensor, kernels: Tensor) -> Tensor:
     the reference's unfold, per-chunk convolution, overlap-add and crop as one gather.  One launch, one accumulator per
     output in ascending ``m`` (float32 fused multiply-adds; double for float64; the half types widen on load and round
     once): bits depend on neither the batch nor the tile.  ``L`` up to ``DSP_MAX_TAPS``.  Rows are read in place through
-    one row stride.  An input that requires grad takes the differentiable composition (``_diff.filter_waveform``).  A plain
-    Python entry point through the C ABI (not registered as a dispatcher op)."""
+    one row stride.  With an input that requires grad the forward is the same launch (the same bits) and the first-order
+    backward is HIP as well (``csrc/dsp_synth_grad.h``: the gradient of ``waveform`` in one launch shaped like the forward,
+    the gradient of ``kernels`` as a float64 reduction in a fixed order without atomics; only the gradients that are
+    needed, and no ``(rows, time, L)`` temporary); under ``create_graph=True`` the backward takes the differentiable
+    composition (``_diff.filter_waveform``), which differentiates to any order.  A plain Python entry point through the C
+    ABI (not registered as a dispatcher op)."""
     what = "filter_waveform"
     _dsp_tensor(what, "waveform", waveform)
     _dsp_tensor(what, "kernels", kernels)
@@ -4747,7 +4762,19 @@ def filter_waveform(waveform: Tensor, kernels: Tensor) -> Tensor:
     if kernels.device != waveform.device:
         raise ValueError(f"audio_amd: {what}: waveform and kernels must be on one device")
     if _dsp_grad(waveform, kernels):
-        return _diff.filter_waveform(waveform.reshape(rows, T_), kernels).reshape(lead + (T_,))
+        if waveform.numel() == 0:                         # nothing to launch: the composition carries the (empty) graph
+            return _diff.filter_waveform(waveform.reshape(rows, T_), kernels).reshape(lead + (T_,))
+        return _FilterWaveformFunction.apply(waveform, kernels)
+    return _filter_waveform_launch(waveform, kernels)
+
+
+def _filter_waveform_launch(waveform: Tensor, kernels: Tensor) -> Tensor:
+    T_ = waveform.shape[-1]
+    F_, L = kernels.shape[-2:]
+    lead = tuple(waveform.shape[:-1])
+    rows = 1
+    for d in lead:
+        rows *= d
     out = torch.empty(lead + (T_,), dtype=waveform.dtype, device=waveform.device)
     if out.numel() == 0:
         return out
@@ -4758,6 +4785,100 @@ def filter_waveform(waveform: Tensor, kernels: Tensor) -> Tensor:
                                                    _wa_stride(x2), F_, L, 1 if kernels.dim() == 3 else 0,
                                                    _lib.current_stream(out.device)))
     return out
+
+
+class _OscillatorBankFunction(torch.autograd.Function):
+    """oscillator_bank in training mode: forward = the two launches of the inference path (the same bits); backward =
+    aamd_oscillator_bank_grad (csrc/dsp_synth_grad.h): the forward's phase, grad_amplitudes = g sin(phi) and grad_frequencies =
+    the float64 suffix sum of g a' cos(phi), only for the inputs that need one.  All HIP kernels."""
+
+    @staticmethod
+    def forward(ctx, frequencies, amplitudes, sample_rate, reduction):
+        ctx.save_for_backward(frequencies, amplitudes)
+        ctx.args = (sample_rate, reduction)
+        return _oscillator_bank_launch(frequencies.detach(), amplitudes.detach(), sample_rate, reduction)
+
+    @staticmethod
+    def backward(ctx, dy):
+        frequencies, amplitudes = ctx.saved_tensors
+        sample_rate, reduction = ctx.args
+        need_f, need_a = ctx.needs_input_grad[:2]
+        if torch.is_grad_enabled():
+            # create_graph=True: differentiate the differentiable composition instead (see _MelSpectrogramFunction)
+            with torch.enable_grad():
+                y = _diff.oscillator_bank(frequencies, amplitudes, sample_rate, reduction)
+                wanted = [t for t, need in ((frequencies, need_f), (amplitudes, need_a)) if need]
+                grads = list(torch.autograd.grad(y, wanted, dy, create_graph=True))
+            return grads.pop(0) if need_f else None, grads.pop(0) if need_a else None, None, None
+        T_, N = frequencies.shape[-2:]
+        f3, a3 = _dsp_rows3(frequencies), _dsp_rows3(amplitudes)
+        rows = f3.shape[0]
+        g = dy.detach().contiguous()
+        dev = f3.device
+        gf = torch.empty((rows, T_, N), dtype=f3.dtype, device=dev) if need_f else None
+        ga = torch.empty((rows, T_, N), dtype=f3.dtype, device=dev) if need_a else None
+        lib = _lib.lib()
+        ws = torch.empty((max(int(lib.aamd_oscillator_grad_workspace(rows, T_, N)) // 8, 1),), dtype=torch.float64, device=dev)
+        with torch.cuda.device(dev):
+            _lib.check(lib.aamd_oscillator_bank_grad(_SA_DTYPES[f3.dtype], f3.data_ptr(), a3.data_ptr(), g.data_ptr(),
+                                                     gf.data_ptr() if need_f else None, ga.data_ptr() if need_a else None,
+                                                     ws.data_ptr(), rows, T_, N, f3.stride(0) if rows > 1 else 0,
+                                                     a3.stride(0) if rows > 1 else 0, float(sample_rate), _DSP_REDUCTIONS[reduction],
+                                                     _lib.current_stream(dev)))
+        return (gf.reshape(frequencies.shape) if need_f else None, ga.reshape(amplitudes.shape) if need_a else None, None, None)
+
+
+class _FilterWaveformFunction(torch.autograd.Function):
+    """filter_waveform in training mode: forward = the launch of the inference path (the same bits); backward =
+    aamd_filter_waveform_grad (csrc/dsp_synth_grad.h): grad_waveform in one launch shaped like the forward, grad_kernels as a
+    float64 reduction in a fixed order (one or two launches), only for the inputs that need one.  All HIP kernels; nothing of
+    (rows, time, L) is ever allocated."""
+
+    @staticmethod
+    def forward(ctx, waveform, kernels):
+        ctx.save_for_backward(waveform, kernels)
+        return _filter_waveform_launch(waveform.detach(), kernels.detach())
+
+    @staticmethod
+    def backward(ctx, dy):
+        waveform, kernels = ctx.saved_tensors
+        need_x, need_h = ctx.needs_input_grad[:2]
+        T_ = waveform.shape[-1]
+        F_, L = kernels.shape[-2:]
+        lead = tuple(waveform.shape[:-1])
+        rows = 1
+        for d in lead:
+            rows *= d
+        if torch.is_grad_enabled():
+            # create_graph=True: differentiate the differentiable composition instead (see _MelSpectrogramFunction)
+            with torch.enable_grad():
+                y = _diff.filter_waveform(waveform.reshape(rows, T_), kernels).reshape(lead + (T_,))
+                wanted = [t for t, need in ((waveform, need_x), (kernels, need_h)) if need]
+                grads = list(torch.autograd.grad(y, wanted, dy, create_graph=True))
+            return grads.pop(0) if need_x else None, grads.pop(0) if need_h else None
+        dev = waveform.device
+        batched = 1 if kernels.dim() == 3 else 0
+        x2 = _wa_rows(waveform.detach(), lead, T_)
+        h = kernels.detach().contiguous()
+        g = dy.detach().reshape(rows, T_).contiguous()
+        gx = torch.empty((rows, T_), dtype=x2.dtype, device=dev) if need_x else None
+        gh = torch.empty(tuple(kernels.shape), dtype=x2.dtype, device=dev) if need_h else None
+        lib = _lib.lib()
+        nbytes = int(lib.aamd_filter_waveform_grad_workspace(rows, T_, F_, L, batched)) if need_h else 0
+        ws = torch.empty((max(nbytes // 8, 1),), dtype=torch.float64, device=dev)
+        with torch.cuda.device(dev):
+            _lib.check(lib.aamd_filter_waveform_grad(_SA_DTYPES[x2.dtype], x2.data_ptr(), h.data_ptr(), g.data_ptr(),
+                                                     gx.data_ptr() if need_x else None, gh.data_ptr() if need_h else None,
+                                                     ws.data_ptr(), rows, T_, _wa_stride(x2), F_, L, batched,
+                                                     _lib.current_stream(dev)))
+        return gx.reshape(waveform.shape) if need_x else None, gh
+
+
+def dsp_grad_tiles() -> Tuple[int, int]:
+    """(samples per unit of time, lags per workgroup) of the filter-gradient reduction of csrc/dsp_synth_grad.h: dsp::kGhPiece,
+    kGhLags."""
+    lib = _lib.lib()
+    return tuple(int(lib.aamd_dsp_grad_tiles(i)) for i in range(2))
 
 
 def sinc_impulse_response(cutoff: Tensor, window_size: int = 513, high_pass: bool = False) -> Tensor:

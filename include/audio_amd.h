@@ -70,6 +70,8 @@
  *                             batch of rooms per call; fixed-point sums, two launches -- an addition to ABI 7
  *   aamd_oscillator_bank, aamd_filter_waveform, aamd_sinc_impulse_response, aamd_frequency_impulse_response,
  *   aamd_extend_pitch         the synthesis ops of prototype.functional -- additions to ABI 7 as well
+ *   aamd_oscillator_bank_grad, aamd_filter_waveform_grad: their first-order gradients (autograd composes a dozen launches over
+ *                             (rows, time, taps) gathers in the reference) -- additions to ABI 7 as well
  *   aamd_dense_fbank          F.dense_fbank_scale / prototype.transforms.ChromaScale (a matmul with a dense (n_freqs, n_chroma)
  *                             filterbank in the reference); one launch -- an addition to ABI 7 as well
  *   aamd_edit_distance        F.edit_distance / F.edit_distance_batch (the reference's Python loop over the cells of one pair on
@@ -1009,6 +1011,35 @@ int aamd_oscillator_bank(int32_t dtype, const void* freq, const void* amp, void*
  * (rows, num_filters, taps) where `batched`; out dense (rows, time).  taps > AAMD_DSP_MAX_TAPS: AAMD_EUNSUPPORTED. */
 int aamd_filter_waveform(int32_t dtype, const void* x, const void* kernels, void* out, int64_t rows, int64_t time,
                          int64_t row_stride, int64_t num_filters, int32_t taps, int32_t batched, void* stream);
+
+/* First-order adjoints of the two ops above (csrc/dsp_synth_grad.h); additions to ABI 7 as well.
+ * which = 0: samples per unit of time of the filter-gradient reduction; 1: lags per workgroup of it. */
+int32_t aamd_dsp_grad_tiles(int32_t which);
+
+/* Bytes of workspace aamd_oscillator_bank_grad needs (float64 chunk sums of w and chunk totals); -1 on a negative size. */
+int64_t aamd_oscillator_grad_workspace(int64_t rows, int64_t time, int64_t n);
+
+/* The gradient of aamd_oscillator_bank: grad_out is dense (rows, time), or (rows, time, n) for AAMD_DSP_NONE (AAMD_DSP_MEAN
+ * divides it by n in the compute type); grad_freq and grad_amp are dense (rows, time, n), and a null one is not computed.
+ * The phase is the forward's, bit for bit.  grad_amp = g sin(phi) where the oscillator is live, (g sin(phi)) * 0 where
+ * |f| >= sample_rate / 2; grad_freq = (2 pi / sample_rate) sum_{s >= t} g a' cos(phi): a float64 suffix sum in a fixed order
+ * (slices of a chunk, then chunks through the workspace), rounded once.  Two or three launches, no atomics. */
+int aamd_oscillator_bank_grad(int32_t dtype, const void* freq, const void* amp, const void* grad_out, void* grad_freq, void* grad_amp,
+                              void* workspace, int64_t rows, int64_t time, int64_t n, int64_t freq_row_stride, int64_t amp_row_stride,
+                              double sample_rate, int32_t reduction, void* stream);
+
+/* Bytes of workspace aamd_filter_waveform_grad needs for grad_kernels (float64 partial sums; 0 where every sum is formed by
+ * one workgroup); -1 on sizes the op refuses. */
+int64_t aamd_filter_waveform_grad_workspace(int64_t rows, int64_t time, int64_t num_filters, int32_t taps, int32_t batched);
+
+/* The gradient of aamd_filter_waveform: grad_out dense (rows, time); grad_x dense (rows, time), grad_kernels dense in the
+ * shape of kernels; a null one is not computed (kernels may then be null for grad_kernels alone, x for grad_x alone).
+ * grad_x[m] = sum_j h[m / C][j] g[m - d + j], one fused multiply-add chain in ascending j in the compute type;
+ * grad_kernels[c][j] = sum over the m of chunk c (and over the rows where the filters are shared) of x[m] g[m - d + j],
+ * accumulated in float64 in a fixed order (time, then rows) and rounded once.  No atomics. */
+int aamd_filter_waveform_grad(int32_t dtype, const void* x, const void* kernels, const void* grad_out, void* grad_x, void* grad_kernels,
+                              void* workspace, int64_t rows, int64_t time, int64_t row_stride, int64_t num_filters, int32_t taps,
+                              int32_t batched, void* stream);
 
 /* prototype.functional.sinc_impulse_response: cutoff (rows,) -> out (rows, window_size), float32 or float64, evaluated in
  * float64 and rounded once: g[i] = sinc(cutoff i) hamming(window_size)[i + half], h = g / |sum g|; high_pass negates h and

@@ -8,6 +8,7 @@ DESC = [
     (r'r0\d_.*bench_edit_distance.*', "tools/bench_edit_distance.py: F.edit_distance_batch, with and without the error counts, on (32, 10, 1500) int32 hypotheses of 100-300 tokens against (32, 300) references, (256, 1, 400) against (256, 400) and (8, 1, 4000) against (8, 4096), time per call and per DP cell, beside the row recurrence restated in torch on the same device (arange + cummin), both by one protocol in alternating rounds, and the reference's Python loop on the host scaled from two pairs", 'DESIGN 4.26, README kernel table'),
     (r'r0\d_.*fuzz_generic_census.*', "pytest tests/test_gpu_fuzz_generic.py -s on an MI355X: per case the kernel instantiation, radix plan, pairs per block, blocks, LDS layout and the achieved fraction of its per-row bar (Kaldi: of `kaldi_fuzz_cases.judge`'s tolerance), the worst fraction per instantiation, 168 passed in 4.1 s", 'DESIGN 2 (generic-kernel census)'),
     (r'r0\d_.*bench_bark_chroma.*', "tools/bench_bark_chroma.py: T.ChromaScale (the dense projection of csrc/dense_fbank.h, 12 chroma) on the frame-major spectrogram of (256, 160000) at n_fft 400 / hop 200 and of (32, 441000) at n_fft 2048 / hop 512, float32, inputs rotating over more than twice the Infinity Cache, beside matmul(spec^T, fb) restated in torch on the same tensors, both by one protocol in alternating rounds, with the spectrogram's bytes at 8 TB/s as the roofline; T.ChromaSpectrogram end to end beside Spectrogram + the restated matmul; T.BarkSpectrogram beside T.MelSpectrogram of the same shape", 'DESIGN 4.25, README kernel table'),
+    (r'r0\d_.*bench_dsp_grad.*', "tools/bench_dsp_grad.py: forward + backward (every input requiring grad) of F.oscillator_bank on (16, 64000, 64) and (256, 16000, 1) and of F.filter_waveform on (64, 160000) with 1000 filters of 513 and of 65 taps and on (4, 16000) with 16000 filters of 65 taps, float32, rotating over two draws of the inputs, beside the differentiable torch compositions of audio_amd._diff on the same device, both by one protocol in alternating rounds, with the allocator's peak of one call of each side and the largest relative difference of their gradients; a composition that cannot allocate is recorded as that", 'DESIGN 4.23.1, README kernel table'),
     (r'r0\d_.*bench_dsp.*',"tools/bench_dsp.py: F.oscillator_bank on (16, 64000, 64) and (256, 16000, 1) and F.filter_waveform on (64, 160000) with 1000 filters of 513 and of 65 taps and on (4, 16000) with 16000 filters of 65 taps, float32, rotating over three draws of the inputs, beside the reference's compositions restated in torch on the same device (remainder, float64 cumsum cast back unreduced, sin, sum; unfold, per-chunk FFT convolution, overlap-add, crop), both by one protocol in alternating rounds, with the bytes and multiply-adds of each call as rates", 'DESIGN 4.23, README kernel table'),
     (r'r0\d_.*bench_ray.*', "tools/bench_ray.py: F.ray_tracing_batch on 256 rooms x 4 microphones x 10 000 rays, one band, time_thres 1.0, with scattering 0 and 0.2, and on 1 room x 8 microphones x 100 000 rays x 7 bands, float32, rotating over two draws of rooms, beside the definition restated in torch on the same device (all rays in lockstep under masks, index_add_, float64; 8 rooms scaled to 256), both by one protocol in alternating rounds, with the number of 8-byte atomic adds and their rate", 'DESIGN 4.24, README kernel table'),
     (r'r0\d_.*bench_rir.*', "tools/bench_rir.py: F.simulate_rir_ism_batch on 256 rooms x 4 microphones at order 17 with 8192 samples and on 1 room x 8 microphones at order 10 with 4096 samples, float32, rotating over three draws of rooms, beside the reference's scatter form restated in torch on the same device (4 rooms scaled to 256), both by one protocol in alternating rounds, with the number of taps inside the output", 'DESIGN 4.22, README kernel table'),
