@@ -30,7 +30,7 @@ SOURCES = ["api_common.hip", "api_stft.hip", "api_mel400_lowp.hip", "api_istft.h
            "api_specdomain.hip", "api_resample.hip", "api_lfilter.hip", "api_fftconv.hip", "api_post.hip", "api_rnnt.hip",
            "api_align.hip", "api_effects.hip", "api_decoder.hip", "api_inverse_mel.hip", "api_vad.hip", "api_spectral.hip",
            "api_pointwise.hip", "api_rir.hip", "api_ray.hip", "api_dsp.hip", "api_dense_fbank.hip",
-           "api_edit.hip"]
+           "api_edit.hip", "api_stoi.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=fast",
          # a packed fp32 VALU op takes 1.6-1.7 x a scalar one on gfx950: 0.78-0.85 of the scalar cost per operation in isolation (fma 0.85,
          # add 0.78, mul 0.79 at 3 waves per SIMD), but the compiler's pairs cost v_mov / v_xor shuffles and hand-packed phases of the

@@ -243,6 +243,10 @@ _SIGS = {
     "aamd_edit_distance_max_ref": (C.c_int32, []),
     "aamd_edit_distance_max_hyp": (C.c_int32, []),
     "aamd_edit_distance": (C.c_int, [_P, C.c_int32] * 4 + [C.c_int64] * 4 + [C.c_int32, _P, _P]),
+    # STOI / ESTOI (additions to ABI 7)
+    "aamd_stoi_tiles": (C.c_int32, [C.c_int32]),
+    "aamd_stoi_workspace": (C.c_int64, [C.c_int32, C.c_int64, C.c_int64]),
+    "aamd_stoi": (C.c_int, [C.c_int32, _P, _P] + [C.c_int64] * 4 + [_P, C.c_int32, C.c_int32, _P, _P, _P]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS)

@@ -48,6 +48,7 @@ __all__ = [
     "dsp_tiles", "dsp_grad_tiles",
     "barkscale_fbanks", "chroma_filterbank", "dense_fbank_scale", "dense_fbank_tiles",
     "edit_distance", "edit_distance_batch", "edit_distance_tiles",
+    "stoi", "stoi_tiles",
 ]
 
 # --------------------------------------------------------------------------- #
@@ -5264,6 +5265,109 @@ def edit_distance(seq1, seq2) -> int:
     dev = torch.device("cuda", torch.cuda.current_device())
     both = torch.tensor(a + b, dtype=torch.int32).to(dev)
     return int(edit_distance_batch(both[len(a):], both[:len(a)]).item())
+
+
+# --------------------------------------------------------------------------- #
+# STOI / ESTOI speech intelligibility (csrc/stoi.h)                           #
+# --------------------------------------------------------------------------- #
+STOI_SAMPLE_RATE = 10000             # the rate the measure is defined at; other rates go through F.resample first
+
+
+def stoi_tiles() -> Tuple[int, int, int, int, int]:
+    """(threads per workgroup, frames per workgroup of the energy kernel, output frames per workgroup of the band kernel,
+    segments per workgroup of the segment kernel, threads per row of the finishing kernel) of csrc/stoi.h: stoi::kThreads,
+    kEnergyFrames, kTobFrames, kSegTile, kFinishThreads."""
+    lib = _lib.lib()
+    return tuple(int(lib.aamd_stoi_tiles(i)) for i in range(5))
+
+
+def _stoi_check(preds: Tensor, target: Tensor, sample_rate: int, lengths: Optional[Tensor]) -> None:
+    """The host-side checks of F.stoi, in the order shapes, parameters, dtypes, gradient, device.  Nothing is read from the
+    device."""
+    if not isinstance(preds, Tensor) or not isinstance(target, Tensor):
+        raise TypeError("audio_amd: stoi: preds and target must be tensors")
+    if preds.dim() < 1 or target.dim() < 1:
+        raise ValueError(f"audio_amd: stoi expects (..., time), got {tuple(preds.shape)} and {tuple(target.shape)}")
+    if preds.shape != target.shape:
+        raise ValueError(f"audio_amd: stoi: preds and target must have the same shape, got {tuple(preds.shape)} and "
+                         f"{tuple(target.shape)}")
+    if isinstance(sample_rate, bool) or not isinstance(sample_rate, int) or sample_rate <= 0:
+        raise ValueError(f"audio_amd: stoi: sample_rate must be a positive integer (got {sample_rate!r})")
+    if lengths is not None and (not isinstance(lengths, Tensor) or tuple(lengths.shape) != tuple(preds.shape[:-1])):
+        raise ValueError(f"audio_amd: stoi: lengths must have the shape {tuple(preds.shape[:-1])}, got "
+                         f"{tuple(lengths.shape) if isinstance(lengths, Tensor) else type(lengths).__name__}")
+    if preds.dtype not in _WA_FLOATS or target.dtype not in _WA_FLOATS:
+        raise TypeError(f"audio_amd: stoi: preds and target must be float16, bfloat16, float32 or float64 (got {preds.dtype} "
+                        f"and {target.dtype})")
+    if preds.dtype != target.dtype:
+        raise TypeError(f"audio_amd: stoi: preds and target must share a dtype (got {preds.dtype} and {target.dtype})")
+    if lengths is not None and lengths.dtype not in _ALIGN_INTS:
+        raise TypeError(f"audio_amd: stoi: lengths must be int32 or int64 (got {lengths.dtype})")
+    if torch.is_grad_enabled() and (preds.requires_grad or target.requires_grad):
+        raise RuntimeError("audio_amd: stoi is forward-only (no gradient is implemented); wrap the call in torch.no_grad() or "
+                           "detach the waveforms.")
+    for t, what in ((preds, "preds"), (target, "target"), (lengths, "lengths")):
+        if t is not None and not t.is_cuda:
+            raise RuntimeError(f"audio_amd: stoi: {what} must be on an MI355X (ROCm) device, got {t.device}. "
+                               "The HIP kernels have no CPU fallback.")
+        if t is not None and t.device != preds.device:
+            raise RuntimeError(f"audio_amd: stoi: {what} must be on the preds' device")
+
+
+def stoi(preds: Tensor, target: Tensor, sample_rate: int, extended: bool = False, lengths: Optional[Tensor] = None) -> Tensor:
+    r"""Short-time objective intelligibility of the processed ``preds`` against the clean ``target``, both ``(..., time)``
+    (the argument order and names of torchmetrics' ``short_time_objective_intelligibility``, which loops pystoi over one
+    utterance at a time in float64 numpy on the host): every row is scored on its own, the result has the shape
+    ``preds.shape[:-1]`` and stays on the device.  ``extended=True`` gives ESTOI.  ``lengths`` (``preds.shape[:-1]``, int32 or
+    int64, on the device) ends row b at sample ``lengths[b]``; nothing at or beyond it is read.
+
+    The measure (Taal et al. 2011; Jensen & Taal 2016) at 10 kHz: 256-sample Hann frames (``hanning(258)[1:-1]``) at hop 128;
+    the frames of the clean signal within 40 dB of its loudest frame are kept and both signals are rebuilt from them by
+    overlap-add; 512-point spectra of the rebuilt signals' frames (all but the last), 15 third-octave band magnitudes from
+    150 Hz; over every run of 30 frames the band-wise correlation of the clean and the normalised, clipped processed
+    magnitudes (STOI), or the correlation of the row- and column-normalised 15 x 30 blocks (ESTOI), averaged.  Fewer than 30
+    such frames score ``1e-5`` (without pystoi's warning).  Any other ``sample_rate`` goes through this package's
+    ``F.resample(., sample_rate, 10000)`` with its defaults first (pystoi uses an Octave-compatible polyphase filter, so
+    scores differ there), and ``lengths`` becomes ``ceil(lengths * 10000 / sample_rate)``.
+
+    float32 is the kernel path; float16 / bfloat16 are widened on load and return float32; float64 runs the same kernels on
+    double and returns float64.  The frame energies and the 40 dB decision are float64 for every dtype, the segment statistic
+    too.  Five launches, no atomics, no host read-back: two calls give the same bits, row b of a batch equals the call on row
+    b, and a row with ``lengths[b]`` equals the call on ``row[:lengths[b]]``.  The window and the twiddles are computed in the
+    kernels, nothing is cached, so the first call can be captured in a graph (at ``sample_rate != 10000`` the resampler's
+    cached kernel is needed: run that call once eagerly).  A row with a non-finite sample below its length, or a length
+    outside ``[0, time]``, scores NaN; other rows keep their bits.  ``ValueError`` for different shapes, 0-dimensional input,
+    ``sample_rate <= 0`` or ``lengths`` of another shape; ``TypeError`` for non-floating or mixed dtypes; no gradient.  A
+    plain Python entry point through the C ABI: not registered as a dispatcher op."""
+    _stoi_check(preds, target, sample_rate, lengths)
+    lead = tuple(preds.shape[:-1])
+    preds, target = preds.detach(), target.detach()
+    if sample_rate != STOI_SAMPLE_RATE:
+        if lengths is not None:
+            # ceil(lengths * 10000 / sample_rate) as F.speed does, in integers (exact at every length); a length outside
+            # [0, time] stays outside
+            scaled = torch.div(lengths.to(torch.int64) * STOI_SAMPLE_RATE + (sample_rate - 1), sample_rate, rounding_mode="floor")
+            lengths = torch.where((lengths < 0) | (lengths > preds.shape[-1]), -1, scaled).to(lengths.dtype)
+        preds = resample(preds, sample_rate, STOI_SAMPLE_RATE)
+        target = resample(target, sample_rate, STOI_SAMPLE_RATE)
+    T_ = preds.shape[-1]
+    p2, t2 = _wa_rows(preds, lead, T_), _wa_rows(target, lead, T_)
+    rows = p2.shape[0]
+    if rows > 1 and p2.stride(0) < T_:             # expanded rows: the launcher takes rows that do not overlap
+        p2 = p2.contiguous()
+    if rows > 1 and t2.stride(0) < T_:
+        t2 = t2.contiguous()
+    out = torch.empty((rows,), dtype=torch.float64 if preds.dtype == torch.float64 else torch.float32, device=preds.device)
+    if rows:
+        lib = _lib.lib()
+        dt = _SA_DTYPES[p2.dtype]
+        ws = torch.empty((max(int(lib.aamd_stoi_workspace(dt, rows, T_)) // 8, 1),), dtype=torch.float64, device=preds.device)
+        len1 = lengths.reshape(-1).contiguous() if lengths is not None else None
+        with torch.cuda.device(preds.device):
+            _lib.check(lib.aamd_stoi(dt, _lib.ptr(p2) or None, _lib.ptr(t2) or None, rows, T_, _wa_stride(p2), _wa_stride(t2),
+                                     len1.data_ptr() if len1 is not None else None, int(len1 is not None and len1.dtype == torch.int64),
+                                     int(bool(extended)), ws.data_ptr(), out.data_ptr(), _lib.current_stream(preds.device)))
+    return out.view(lead)
 
 
 @_reduced_precision_io

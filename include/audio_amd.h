@@ -76,6 +76,8 @@
  *                             filterbank in the reference); one launch -- an addition to ABI 7 as well
  *   aamd_edit_distance        F.edit_distance / F.edit_distance_batch (the reference's Python loop over the cells of one pair on
  *                             the host); every pair of a batch in one launch, with the error counts -- an addition to ABI 7
+ *   aamd_stoi                 F.stoi: STOI / ESTOI of every row of a batch (pystoi's float64 numpy loop over one utterance on
+ *                             the host, through torchmetrics); five launches, no read-back -- an addition to ABI 7
  *   aamd_detect_pitch_f32     F.detect_pitch_frequency (_compute_nccf + _find_max_per_frame + _median_smoothing in the
  *                             reference; an addition to ABI 7 as well)
  *
@@ -1104,6 +1106,25 @@ int32_t aamd_edit_distance_max_hyp(void);
 int aamd_edit_distance(const void* hyps, int32_t hyps_int64, const void* refs, int32_t refs_int64, const void* hyp_lengths,
                        int32_t hyp_lengths_int64, const void* ref_lengths, int32_t ref_lengths_int64, int64_t pairs,
                        int64_t pairs_per_ref, int64_t max_n, int64_t max_m, int32_t return_ops, int32_t* out, void* stream);
+
+/* ---- STOI / ESTOI speech intelligibility (additions to ABI 7; csrc/stoi.h) ------------------------------------------- */
+
+/* which: 0 threads per workgroup, 1 frames per workgroup of the energy kernel, 2 output frames per workgroup of the band
+ * kernel, 3 segments per workgroup of the segment kernel, 4 threads per row of the finishing kernel. */
+int32_t aamd_stoi_tiles(int32_t which);
+
+/* Bytes of workspace for `rows` rows of `length` samples of `dtype` (AAMD_SA_*); 0 for no rows. */
+int64_t aamd_stoi_workspace(int32_t dtype, int64_t rows, int64_t length);
+
+/* F.stoi at 10 kHz.  preds (processed) and target (clean): (rows, length) of `dtype` (AAMD_SA_F32 / F64 / F16 / BF16), unit
+ * sample stride, row strides in elements.  lengths: (rows,) int32 or int64 (lengths_int64) or null for the full width; row b
+ * ends at lengths[b] and nothing at or beyond it is read; a length outside [0, length] scores NaN, as does a row with a
+ * non-finite sample below its length.  extended: ESTOI.  workspace: aamd_stoi_workspace bytes, 8-byte aligned.  out: (rows,)
+ * float32, or float64 for AAMD_SA_F64.  Rows with fewer than 30 output frames score 1e-5.  All on the device and read
+ * there: five launches, no synchronisation, no atomics, no cached table. */
+int aamd_stoi(int32_t dtype, const void* preds, const void* target, int64_t rows, int64_t length, int64_t preds_stride,
+              int64_t target_stride, const void* lengths, int32_t lengths_int64, int32_t extended, void* workspace, void* out,
+              void* stream);
 
 #ifdef __cplusplus
 }

@@ -5,6 +5,8 @@ import re
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DESC = [
+    (r'r0\d_.*stoi_kernel_stats.*', "rocprofv3 --kernel-trace --stats of 10 STOI and 10 ESTOI calls of F.stoi on (256, 100000) float32 white noise at 10 kHz (every frame kept, the most work a row can have): calls, total and mean time of the five kernels of csrc/stoi.h; the segment kernel's mean is over both modes, its minimum is STOI and its maximum ESTOI", "DESIGN 4.27"),
+    (r'r0\d_.*bench_stoi.*', "tools/bench_stoi.py: F.stoi, STOI and ESTOI, on (256, 160000) at 16 kHz, (32, 40000) at 10 kHz and (8, 441000) at 44.1 kHz, float32: the measure at 10 kHz, both F.resample calls on their own and the whole call, time per call and per frame, beside the definition restated in torch on the same device (unfold, argsort, rfft, band matrix), both by one protocol in alternating rounds, and the float64 numpy definition on the host scaled from two rows", "DESIGN 4.27, README kernel table"),
     (r'r0\d_.*bench_edit_distance.*', "tools/bench_edit_distance.py: F.edit_distance_batch, with and without the error counts, on (32, 10, 1500) int32 hypotheses of 100-300 tokens against (32, 300) references, (256, 1, 400) against (256, 400) and (8, 1, 4000) against (8, 4096), time per call and per DP cell, beside the row recurrence restated in torch on the same device (arange + cummin), both by one protocol in alternating rounds, and the reference's Python loop on the host scaled from two pairs", 'DESIGN 4.26, README kernel table'),
     (r'r0\d_.*fuzz_generic_census.*', "pytest tests/test_gpu_fuzz_generic.py -s on an MI355X: per case the kernel instantiation, radix plan, pairs per block, blocks, LDS layout and the achieved fraction of its per-row bar (Kaldi: of `kaldi_fuzz_cases.judge`'s tolerance), the worst fraction per instantiation, 168 passed in 4.1 s", 'DESIGN 2 (generic-kernel census)'),
     (r'r0\d_.*bench_bark_chroma.*', "tools/bench_bark_chroma.py: T.ChromaScale (the dense projection of csrc/dense_fbank.h, 12 chroma) on the frame-major spectrogram of (256, 160000) at n_fft 400 / hop 200 and of (32, 441000) at n_fft 2048 / hop 512, float32, inputs rotating over more than twice the Infinity Cache, beside matmul(spec^T, fb) restated in torch on the same tensors, both by one protocol in alternating rounds, with the spectrogram's bytes at 8 TB/s as the roofline; T.ChromaSpectrogram end to end beside Spectrogram + the restated matmul; T.BarkSpectrogram beside T.MelSpectrogram of the same shape", 'DESIGN 4.25, README kernel table'),
