@@ -247,6 +247,12 @@ _SIGS = {
     "aamd_stoi_tiles": (C.c_int32, [C.c_int32]),
     "aamd_stoi_workspace": (C.c_int64, [C.c_int32, C.c_int64, C.c_int64]),
     "aamd_stoi": (C.c_int, [C.c_int32, _P, _P] + [C.c_int64] * 4 + [_P, C.c_int32, C.c_int32, _P, _P, _P]),
+    "aamd_sdr_tiles": (C.c_int32, [C.c_int32]),
+    "aamd_sdr_workspace": (C.c_int64, [C.c_int32, C.c_int64, C.c_int64, C.c_int64]),
+    "aamd_sdr": (C.c_int, [C.c_int32, _P, _P] + [C.c_int64] * 4 + [_P, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_double,
+                           _P, _P, _P]),
+    "aamd_si_sdr": (C.c_int, [C.c_int32, C.c_int32, _P, _P] + [C.c_int64] * 4 + [_P, C.c_int32, C.c_int32, _P, _P, _P, _P]),
+    "aamd_si_sdr_grad": (C.c_int, [C.c_int32, C.c_int32, _P, _P] + [C.c_int64] * 4 + [_P, C.c_int32, _P, _P, _P, _P, _P]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS)

@@ -49,6 +49,8 @@ __all__ = [
     "barkscale_fbanks", "chroma_filterbank", "dense_fbank_scale", "dense_fbank_tiles",
     "edit_distance", "edit_distance_batch", "edit_distance_tiles",
     "stoi", "stoi_tiles",
+    "signal_distortion_ratio", "scale_invariant_signal_distortion_ratio", "scale_invariant_signal_noise_ratio",
+    "signal_noise_ratio", "sdr_tiles",
 ]
 
 # --------------------------------------------------------------------------- #
@@ -5368,6 +5370,202 @@ def stoi(preds: Tensor, target: Tensor, sample_rate: int, extended: bool = False
                                      len1.data_ptr() if len1 is not None else None, int(len1 is not None and len1.dtype == torch.int64),
                                      int(bool(extended)), ws.data_ptr(), out.data_ptr(), _lib.current_stream(preds.device)))
     return out.view(lead)
+
+
+# --------------------------------------------------------------------------- #
+# SDR, SI-SDR / SI-SNR, SNR (csrc/sdr.h)                                      #
+# --------------------------------------------------------------------------- #
+SDR_MAX_FILTER_LENGTH = 512          # lags the correlation and Levinson kernels hold
+
+
+def sdr_tiles() -> Tuple[int, int, int, int, int, int]:
+    """(threads per workgroup, samples per workgroup of the streaming kernels = chunk, samples of a staged piece of the
+    correlation kernel, samples per workgroup of the correlation kernel = span, most lags of the small instantiation, most
+    lags served) of csrc/sdr.h: sdr::kThreads, kChunk, kStage, kSpan, kLagsSmall, kLagsMax."""
+    lib = _lib.lib()
+    return tuple(int(lib.aamd_sdr_tiles(i)) for i in range(6))
+
+
+def _sdr_check(name: str, preds: Tensor, target: Tensor, lengths: Optional[Tensor], forward_only: bool) -> None:
+    """The host-side checks of the separation metrics, in the order shapes, dtypes, gradient, device.  Nothing is read from
+    the device."""
+    if not isinstance(preds, Tensor) or not isinstance(target, Tensor):
+        raise TypeError(f"audio_amd: {name}: preds and target must be tensors")
+    if preds.dim() < 1 or target.dim() < 1:
+        raise ValueError(f"audio_amd: {name} expects (..., time), got {tuple(preds.shape)} and {tuple(target.shape)}")
+    if preds.shape != target.shape:
+        raise ValueError(f"audio_amd: {name}: preds and target must have the same shape, got {tuple(preds.shape)} and "
+                         f"{tuple(target.shape)}")
+    if lengths is not None and (not isinstance(lengths, Tensor) or tuple(lengths.shape) != tuple(preds.shape[:-1])):
+        raise ValueError(f"audio_amd: {name}: lengths must have the shape {tuple(preds.shape[:-1])}, got "
+                         f"{tuple(lengths.shape) if isinstance(lengths, Tensor) else type(lengths).__name__}")
+    if preds.dtype not in _WA_FLOATS or target.dtype not in _WA_FLOATS:
+        raise TypeError(f"audio_amd: {name}: preds and target must be float16, bfloat16, float32 or float64 (got {preds.dtype} "
+                        f"and {target.dtype})")
+    if preds.dtype != target.dtype:
+        raise TypeError(f"audio_amd: {name}: preds and target must share a dtype (got {preds.dtype} and {target.dtype})")
+    if lengths is not None and lengths.dtype not in _ALIGN_INTS:
+        raise TypeError(f"audio_amd: {name}: lengths must be int32 or int64 (got {lengths.dtype})")
+    if forward_only and torch.is_grad_enabled() and (preds.requires_grad or target.requires_grad):
+        raise RuntimeError(f"audio_amd: {name} is forward-only (no gradient is implemented); wrap the call in torch.no_grad() "
+                           "or detach the waveforms.")
+    for t, what in ((preds, "preds"), (target, "target"), (lengths, "lengths")):
+        if t is not None and not t.is_cuda:
+            raise RuntimeError(f"audio_amd: {name}: {what} must be on an MI355X (ROCm) device, got {t.device}. "
+                               "The HIP kernels have no CPU fallback.")
+        if t is not None and t.device != preds.device:
+            raise RuntimeError(f"audio_amd: {name}: {what} must be on the preds' device")
+
+
+def _sdr_rows(preds: Tensor, target: Tensor, lengths: Optional[Tensor]):
+    """(preds, target) as (rows, time) operands read in place through one row stride, lengths as (rows,) or None."""
+    lead, T_ = tuple(preds.shape[:-1]), preds.shape[-1]
+    p2, t2 = _wa_rows(preds, lead, T_), _wa_rows(target, lead, T_)
+    if p2.shape[0] > 1 and p2.stride(0) < T_:      # expanded rows: the launcher takes rows that do not overlap
+        p2 = p2.contiguous()
+    if t2.shape[0] > 1 and t2.stride(0) < T_:
+        t2 = t2.contiguous()
+    return p2, t2, (lengths.reshape(-1).contiguous() if lengths is not None else None)
+
+
+def _sdr_len_args(len1: Optional[Tensor]):
+    return (len1.data_ptr() if len1 is not None else None, int(len1 is not None and len1.dtype == torch.int64))
+
+
+def signal_distortion_ratio(preds: Tensor, target: Tensor, use_cg_iter: Optional[int] = None, filter_length: int = 512,
+                            zero_mean: bool = False, load_diag: Optional[float] = None,
+                            lengths: Optional[Tensor] = None) -> Tensor:
+    r"""BSS-eval signal-to-distortion ratio in dB of ``preds`` against ``target``, both ``(..., time)`` (the argument order and
+    names of torchmetrics' ``signal_distortion_ratio``): every row is scored on its own, the result has the shape
+    ``preds.shape[:-1]`` and stays on the device.  ``lengths`` (``preds.shape[:-1]``, int32 or int64, on the device) ends row
+    b at sample ``lengths[b]``; nothing at or beyond it is read.
+
+    The definition (tests/sdr_oracle.py), in float64 for every input dtype: rows are centred when ``zero_mean`` and scaled by
+    ``1 / max(norm, 1e-6)``; ``r[k] = sum_n t[n] t[n + k]`` and ``b[k] = sum_n t[n] p[n + k]`` for ``k < filter_length`` are
+    linear correlations (terms beyond the row's end are zero); ``r[0] += load_diag`` when given; ``Toeplitz(r) h = b``;
+    ``coh = b . h``; the score is ``10 log10(coh / (1 - coh))``.  The correlations are direct sums on the float64 matrix
+    cores (a Gram product) where the reference takes four zero-padded FFTs; the system is solved by the
+    Levinson recursion where the reference calls a dense solver.  ``use_cg_iter`` is accepted and ignored: the exact solve is
+    what torchmetrics itself falls back to without fast-bss-eval.  ``filter_length`` from 1 to 512; above that
+    ``NotImplementedError``.
+
+    float64 input returns float64, every other dtype float32 (half types are widened on load).  Three launches, no atomics,
+    no host read-back, nothing cached: two calls give the same bits, row b of a batch equals the call on row b, a row with
+    ``lengths[b]`` equals the call on ``row[:lengths[b]]``, and a first call can be captured in a graph.  A row with a
+    non-finite sample below its length, a length outside ``[0, time]``, or a recursion step whose prediction error is not
+    finite and positive (a singular system: a silent or empty target) scores NaN; other rows keep their bits.
+    ``ValueError`` for different shapes, 0-dimensional input, ``filter_length < 1`` or ``lengths`` of another shape;
+    ``TypeError`` for non-floating or mixed dtypes; forward-only.  A plain Python entry point through the C ABI."""
+    if isinstance(filter_length, bool) or not isinstance(filter_length, int) or filter_length < 1:
+        raise ValueError(f"audio_amd: signal_distortion_ratio: filter_length must be a positive integer (got {filter_length!r})")
+    if filter_length > SDR_MAX_FILTER_LENGTH:
+        raise NotImplementedError(f"audio_amd: signal_distortion_ratio: filter_length above {SDR_MAX_FILTER_LENGTH} is not "
+                                  f"implemented (got {filter_length})")
+    _sdr_check("signal_distortion_ratio", preds, target, lengths, True)
+    lead = tuple(preds.shape[:-1])
+    p2, t2, len1 = _sdr_rows(preds.detach(), target.detach(), lengths)
+    rows, T_ = p2.shape
+    out = torch.empty((rows,), dtype=torch.float64 if preds.dtype == torch.float64 else torch.float32, device=preds.device)
+    if rows:
+        lib = _lib.lib()
+        ws = torch.empty((max(int(lib.aamd_sdr_workspace(0, rows, T_, filter_length)) // 8, 1),), dtype=torch.float64,
+                         device=preds.device)
+        with torch.cuda.device(preds.device):
+            _lib.check(lib.aamd_sdr(_SA_DTYPES[p2.dtype], _lib.ptr(p2) or None, _lib.ptr(t2) or None, rows, T_, _wa_stride(p2),
+                                    _wa_stride(t2), *_sdr_len_args(len1), filter_length, int(bool(zero_mean)),
+                                    int(load_diag is not None), float(load_diag or 0.0), ws.data_ptr(), out.data_ptr(),
+                                    _lib.current_stream(preds.device)))
+    return out.view(lead)
+
+
+def _si_sdr_launch(mode: int, p2: Tensor, t2: Tensor, len1: Optional[Tensor], zero_mean: bool):
+    """The three forward launches over (rows, time) operands: (scores (rows,), the rows' (rows, 8) float64 statistics)."""
+    rows, T_ = p2.shape
+    out = torch.empty((rows,), dtype=torch.float64 if p2.dtype == torch.float64 else torch.float32, device=p2.device)
+    stat = torch.empty((rows, 8), dtype=torch.float64, device=p2.device)
+    if rows:
+        lib = _lib.lib()
+        ws = torch.empty((max(int(lib.aamd_sdr_workspace(mode, rows, T_, 1)) // 8, 1),), dtype=torch.float64, device=p2.device)
+        with torch.cuda.device(p2.device):
+            _lib.check(lib.aamd_si_sdr(_SA_DTYPES[p2.dtype], mode, _lib.ptr(p2) or None, _lib.ptr(t2) or None, rows, T_,
+                                       _wa_stride(p2), _wa_stride(t2), *_sdr_len_args(len1), int(bool(zero_mean)), ws.data_ptr(),
+                                       stat.data_ptr(), out.data_ptr(), _lib.current_stream(p2.device)))
+    return out, stat
+
+
+class _SiSdrFunction(torch.autograd.Function):
+    """Scores preds.shape[:-1].  What is kept for backward is the two waveforms and eight float64 statistics per row; the
+    gradient is one launch, formed once: a second derivative raises."""
+
+    @staticmethod
+    def forward(ctx, preds, target, lengths, mode, zero_mean):
+        p2, t2, len1 = _sdr_rows(preds.detach(), target.detach(), lengths)
+        out, stat = _si_sdr_launch(mode, p2, t2, len1, zero_mean)
+        ctx.save_for_backward(p2, t2, len1, stat)
+        ctx.sdr = (mode, tuple(preds.shape))
+        return out.view(tuple(preds.shape[:-1]))
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        p2, t2, len1, stat = ctx.saved_tensors
+        mode, shape = ctx.sdr
+        rows, T_ = p2.shape
+        cot = grad_out.reshape(-1).to(torch.float64).contiguous()
+        grads = [torch.empty((rows, T_), dtype=p2.dtype, device=p2.device) if need else None for need in ctx.needs_input_grad[:2]]
+        if rows and T_:
+            lib = _lib.lib()
+            with torch.cuda.device(p2.device):
+                _lib.check(lib.aamd_si_sdr_grad(_SA_DTYPES[p2.dtype], mode, _lib.ptr(p2), _lib.ptr(t2), rows, T_, _wa_stride(p2),
+                                                _wa_stride(t2), *_sdr_len_args(len1), stat.data_ptr(), cot.data_ptr(),
+                                                grads[0].data_ptr() if grads[0] is not None else None,
+                                                grads[1].data_ptr() if grads[1] is not None else None,
+                                                _lib.current_stream(p2.device)))
+        return tuple(g.view(shape) if g is not None else None for g in grads) + (None, None, None)
+
+
+def _si_family(name: str, mode: int, preds: Tensor, target: Tensor, zero_mean: bool, lengths: Optional[Tensor]) -> Tensor:
+    _sdr_check(name, preds, target, lengths, False)
+    if torch.is_grad_enabled() and (preds.requires_grad or target.requires_grad):
+        return _SiSdrFunction.apply(preds, target, lengths, mode, bool(zero_mean))
+    p2, t2, len1 = _sdr_rows(preds.detach(), target.detach(), lengths)
+    return _si_sdr_launch(mode, p2, t2, len1, zero_mean)[0].view(tuple(preds.shape[:-1]))
+
+
+def scale_invariant_signal_distortion_ratio(preds: Tensor, target: Tensor, zero_mean: bool = False,
+                                            lengths: Optional[Tensor] = None) -> Tensor:
+    r"""SI-SDR in dB of ``preds`` against ``target``, both ``(..., time)`` (the argument order and names of torchmetrics'
+    ``scale_invariant_signal_distortion_ratio``); the result has the shape ``preds.shape[:-1]`` and stays on the device.
+    With ``eps = finfo(dtype).eps`` (float32's for the half types) and the rows centred when ``zero_mean``:
+    ``alpha = (sum p t + eps) / (sum t t + eps)`` and the score is
+    ``10 log10((sum (alpha t)^2 + eps) / (sum (alpha t - p)^2 + eps))``.  ``lengths`` ends row b at ``lengths[b]``; nothing at
+    or beyond it is read.
+
+    All sums are float64 for every dtype and the residual is summed directly, not from the moments; float64 input returns
+    float64, every other dtype float32.  Three launches where the reference chains five or six full-size temporaries; no
+    atomics, no read-back, nothing cached: two calls give the same bits, row b of a batch equals the call on row b, a row
+    with ``lengths[b]`` equals the call on ``row[:lengths[b]]``, and a first call can be captured in a graph.  A row with a
+    non-finite sample below its length or a length outside ``[0, time]`` scores NaN; other rows keep their bits.
+
+    Differentiable once in ``preds`` and ``target``: the backward is one launch, ``c1 p + c2 t + c3`` with per-row float64
+    coefficients, exactly zero at or beyond ``lengths[b]`` (a length outside ``[0, time]`` gives a zero row, a non-finite
+    row NaN); a second derivative raises.  ``ValueError`` for different shapes, 0-dimensional input or ``lengths`` of
+    another shape; ``TypeError`` for non-floating or mixed dtypes.  A plain Python entry point through the C ABI."""
+    return _si_family("scale_invariant_signal_distortion_ratio", 1, preds, target, zero_mean, lengths)
+
+
+def scale_invariant_signal_noise_ratio(preds: Tensor, target: Tensor, lengths: Optional[Tensor] = None) -> Tensor:
+    r"""SI-SNR in dB: ``scale_invariant_signal_distortion_ratio(preds, target, zero_mean=True, lengths=lengths)``, as in
+    torchmetrics."""
+    return _si_family("scale_invariant_signal_noise_ratio", 1, preds, target, True, lengths)
+
+
+def signal_noise_ratio(preds: Tensor, target: Tensor, zero_mean: bool = False, lengths: Optional[Tensor] = None) -> Tensor:
+    r"""SNR in dB of ``preds`` against ``target``: ``10 log10((sum t^2 + eps) / (sum (t - p)^2 + eps))`` after the optional
+    mean removal (the argument order and names of torchmetrics' ``signal_noise_ratio``).  Sums, dtypes, ``lengths``, the
+    bit-for-bit guarantees, the once-differentiable one-launch backward and the errors are those of
+    ``scale_invariant_signal_distortion_ratio``."""
+    return _si_family("signal_noise_ratio", 2, preds, target, zero_mean, lengths)
 
 
 @_reduced_precision_io

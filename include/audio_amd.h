@@ -78,6 +78,10 @@
  *                             the host); every pair of a batch in one launch, with the error counts -- an addition to ABI 7
  *   aamd_stoi                 F.stoi: STOI / ESTOI of every row of a batch (pystoi's float64 numpy loop over one utterance on
  *                             the host, through torchmetrics); five launches, no read-back -- an addition to ABI 7
+ *   aamd_sdr, aamd_si_sdr,
+ *   aamd_si_sdr_grad          F.signal_distortion_ratio, F.scale_invariant_signal_distortion_ratio, F.signal_noise_ratio
+ *                             (torchmetrics' float64 FFT correlations and dense solve; a chain of full-size temporaries and
+ *                             its autograd graph); three launches each, no read-back -- additions to ABI 7
  *   aamd_detect_pitch_f32     F.detect_pitch_frequency (_compute_nccf + _find_max_per_frame + _median_smoothing in the
  *                             reference; an addition to ABI 7 as well)
  *
@@ -1125,6 +1129,44 @@ int64_t aamd_stoi_workspace(int32_t dtype, int64_t rows, int64_t length);
 int aamd_stoi(int32_t dtype, const void* preds, const void* target, int64_t rows, int64_t length, int64_t preds_stride,
               int64_t target_stride, const void* lengths, int32_t lengths_int64, int32_t extended, void* workspace, void* out,
               void* stream);
+
+/* ---- SDR, SI-SDR / SI-SNR, SNR (additions to ABI 7; csrc/sdr.h) -------------------------------------------------------- */
+
+/* which: 0 threads per workgroup, 1 samples per workgroup of the streaming kernels, 2 samples of a staged piece of the
+ * correlation kernel, 3 samples per workgroup of the correlation kernel, 4 the most lags of the small instantiation, 5 the
+ * most lags served. */
+int32_t aamd_sdr_tiles(int32_t which);
+
+/* Bytes of the float64 workspace for `rows` rows of `length` samples; mode 0: aamd_sdr at filter_length, 1 / 2: aamd_si_sdr
+ * (filter_length is ignored but must lie in [1, 512]); 0 for no rows. */
+int64_t aamd_sdr_workspace(int32_t mode, int64_t rows, int64_t length, int64_t filter_length);
+
+/* F.signal_distortion_ratio.  preds and target: (rows, length) of `dtype` (AAMD_SA_*), unit sample stride, row strides in
+ * elements.  lengths: (rows,) int32 or int64 (lengths_int64) or null; row b ends at lengths[b], nothing at or beyond it is
+ * read; a length outside [0, length] scores NaN, as does a row with a non-finite sample below its length or one whose
+ * Levinson recursion meets a prediction error that is not finite and positive.  Rows are centred when zero_mean, scaled by
+ * 1 / max(norm, 1e-6); r[k] and b[k] for k < filter_length (1 ... 512; above: AAMD_EUNSUPPORTED) are linear correlations
+ * in float64 on the matrix cores; r[0] += load_diag when has_load_diag; Toeplitz(r) h = b; coh = b . h;
+ * out = 10 log10(coh / (1 - coh)): (rows,) float32, or float64 for AAMD_SA_F64.  workspace: aamd_sdr_workspace(0, ...)
+ * bytes, 8-byte aligned.  Three launches, no synchronisation, no atomics, no cached table. */
+int aamd_sdr(int32_t dtype, const void* preds, const void* target, int64_t rows, int64_t length, int64_t preds_stride,
+             int64_t target_stride, const void* lengths, int32_t lengths_int64, int64_t filter_length, int32_t zero_mean,
+             int32_t has_load_diag, double load_diag, void* workspace, void* out, void* stream);
+
+/* mode 1: F.scale_invariant_signal_distortion_ratio, 10 log10((sum (alpha t)^2 + eps) / (sum (alpha t - p)^2 + eps)) with
+ * alpha = (sum p t + eps) / (sum t t + eps); mode 2: F.signal_noise_ratio, alpha = 1.  eps is float32's for every dtype
+ * but AAMD_SA_F64; sums are float64, the residual is summed directly.  stat: (rows, 8) float64, written here and read by
+ * aamd_si_sdr_grad.  Other arguments as aamd_sdr; workspace: aamd_sdr_workspace(mode, ...) bytes.  Three launches. */
+int aamd_si_sdr(int32_t dtype, int32_t mode, const void* preds, const void* target, int64_t rows, int64_t length,
+                int64_t preds_stride, int64_t target_stride, const void* lengths, int32_t lengths_int64, int32_t zero_mean,
+                void* workspace, double* stat, void* out, void* stream);
+
+/* The gradient of aamd_si_sdr's scores: grad_preds and / or grad_target (either may be null), dense (rows, length) of
+ * `dtype`, = cotangent[row] (c1 p + c2 t + c3) with float64 coefficients from stat; half types are rounded once; elements
+ * at or beyond lengths[row] are exactly zero (a length outside [0, length] counts as 0).  One launch. */
+int aamd_si_sdr_grad(int32_t dtype, int32_t mode, const void* preds, const void* target, int64_t rows, int64_t length,
+                     int64_t preds_stride, int64_t target_stride, const void* lengths, int32_t lengths_int64,
+                     const double* stat, const double* cotangent, void* grad_preds, void* grad_target, void* stream);
 
 #ifdef __cplusplus
 }
