@@ -253,6 +253,13 @@ _SIGS = {
                            _P, _P, _P]),
     "aamd_si_sdr": (C.c_int, [C.c_int32, C.c_int32, _P, _P] + [C.c_int64] * 4 + [_P, C.c_int32, C.c_int32, _P, _P, _P, _P]),
     "aamd_si_sdr_grad": (C.c_int, [C.c_int32, C.c_int32, _P, _P] + [C.c_int64] * 4 + [_P, C.c_int32, _P, _P, _P, _P, _P]),
+    # permutation-invariant training (additions to ABI 7)
+    "aamd_pit_tiles": (C.c_int32, [C.c_int32]),
+    "aamd_pit_workspace": (C.c_int64, [C.c_int64] * 3),
+    "aamd_pit_forward": (C.c_int, [C.c_int32, C.c_int32, _P, _P] + [C.c_int64] * 7 + [_P, C.c_int32, C.c_int32, C.c_int32] + [_P] * 6),
+    "aamd_pit_assign": (C.c_int, [C.c_int32, _P, C.c_int64, C.c_int64, C.c_int32, _P, _P, _P]),
+    "aamd_pit_grad": (C.c_int, [C.c_int32, C.c_int32, _P, _P] + [C.c_int64] * 7 + [_P, C.c_int32] + [_P] * 6),
+    "aamd_pit_permutate": (C.c_int, [C.c_int32, _P, _P] + [C.c_int64] * 5 + [C.c_uint64, _P, _P]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS)

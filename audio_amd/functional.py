@@ -51,6 +51,7 @@ __all__ = [
     "stoi", "stoi_tiles",
     "signal_distortion_ratio", "scale_invariant_signal_distortion_ratio", "scale_invariant_signal_noise_ratio",
     "signal_noise_ratio", "sdr_tiles",
+    "permutation_invariant_training", "pit_metric_matrix", "pit_assignment", "pit_permutate", "pit_tiles",
 ]
 
 # --------------------------------------------------------------------------- #
@@ -5566,6 +5567,309 @@ def signal_noise_ratio(preds: Tensor, target: Tensor, zero_mean: bool = False, l
     bit-for-bit guarantees, the once-differentiable one-launch backward and the errors are those of
     ``scale_invariant_signal_distortion_ratio``."""
     return _si_family("signal_noise_ratio", 2, preds, target, zero_mean, lengths)
+
+
+# --------------------------------------------------------------------------- #
+# permutation-invariant training (csrc/pit.h)                                 #
+# --------------------------------------------------------------------------- #
+PIT_MAX_SOURCES = 8                  # one lane per subset of targets: 2^8 lanes
+
+
+def pit_tiles() -> Tuple[int, int, int, int]:
+    """(threads per workgroup, samples per workgroup of the Gram kernel, samples per workgroup of the pairwise residual
+    kernel, most sources served) of csrc/pit.h: pit::kThreads, kGramSpan, kResChunk, kMaxS."""
+    lib = _lib.lib()
+    return tuple(int(lib.aamd_pit_tiles(i)) for i in range(4))
+
+
+def _pit_fused(metric_func, kwargs):
+    """(name, mode, zero_mean) where ``metric_func`` is one of the metrics the pairwise kernels compute, else None."""
+    table = {"scale_invariant_signal_distortion_ratio": (scale_invariant_signal_distortion_ratio, 1, None),
+             "scale_invariant_signal_noise_ratio": (scale_invariant_signal_noise_ratio, 1, True),
+             "signal_noise_ratio": (signal_noise_ratio, 2, None)}
+    for name, (fn, mode, fixed) in table.items():
+        if metric_func is fn or metric_func == name:
+            extra = sorted(set(kwargs) - (set() if fixed is not None else {"zero_mean"}))
+            if extra:
+                raise TypeError(f"audio_amd: permutation_invariant_training: {name} takes no argument {extra[0]!r} here")
+            return name, mode, bool(kwargs.get("zero_mean", False)) if fixed is None else fixed
+    if isinstance(metric_func, str):
+        raise ValueError(f"audio_amd: permutation_invariant_training: unknown metric {metric_func!r}; the names served are "
+                         f"{', '.join(table)}")
+    if not callable(metric_func):
+        raise TypeError("audio_amd: permutation_invariant_training: metric_func must be a callable or a metric's name")
+    return None
+
+
+def _pit_check(name: str, preds: Tensor, target: Tensor, lengths: Optional[Tensor], fused: bool) -> None:
+    """The host-side checks, in the order shapes, dtypes, device; the dtype, device and lengths errors are _sdr_check's.
+    Nothing is read from the device."""
+    if not isinstance(preds, Tensor) or not isinstance(target, Tensor):
+        raise TypeError(f"audio_amd: {name}: preds and target must be tensors")
+    if preds.dim() != 3 or target.dim() != 3:
+        raise ValueError(f"audio_amd: {name} expects (batch, sources, time), got {tuple(preds.shape)} and {tuple(target.shape)}")
+    if preds.shape != target.shape:
+        raise ValueError(f"audio_amd: {name}: preds and target must have the same shape, got {tuple(preds.shape)} and "
+                         f"{tuple(target.shape)}")
+    if preds.shape[1] == 0:
+        raise ValueError(f"audio_amd: {name}: at least one source is needed, got {tuple(preds.shape)}")
+    if preds.shape[1] > PIT_MAX_SOURCES:
+        raise NotImplementedError(f"audio_amd: {name}: more than PIT_MAX_SOURCES = {PIT_MAX_SOURCES} sources are not implemented "
+                                  f"(got {preds.shape[1]})")
+    if not fused:
+        if lengths is not None:
+            raise ValueError(f"audio_amd: {name}: lengths is served for the fused metrics only; a callable's own signature is "
+                             "not known")
+        return
+    if lengths is not None and (not isinstance(lengths, Tensor) or tuple(lengths.shape) != (preds.shape[0],)):
+        raise ValueError(f"audio_amd: {name}: lengths must have the shape {(preds.shape[0],)}, got "
+                         f"{tuple(lengths.shape) if isinstance(lengths, Tensor) else type(lengths).__name__}")
+    if preds.dtype not in _WA_FLOATS or target.dtype not in _WA_FLOATS:
+        raise TypeError(f"audio_amd: {name}: preds and target must be float16, bfloat16, float32 or float64 (got {preds.dtype} "
+                        f"and {target.dtype})")
+    if preds.dtype != target.dtype:
+        raise TypeError(f"audio_amd: {name}: preds and target must share a dtype (got {preds.dtype} and {target.dtype})")
+    if lengths is not None and lengths.dtype not in _ALIGN_INTS:
+        raise TypeError(f"audio_amd: {name}: lengths must be int32 or int64 (got {lengths.dtype})")
+    for t, what in ((preds, "preds"), (target, "target"), (lengths, "lengths")):
+        if t is not None and not t.is_cuda:
+            raise RuntimeError(f"audio_amd: {name}: {what} must be on an MI355X (ROCm) device, got {t.device}. "
+                               "The HIP kernels have no CPU fallback.")
+        if t is not None and t.device != preds.device:
+            raise RuntimeError(f"audio_amd: {name}: {what} must be on the preds' device")
+
+
+def _pit_rows(x: Tensor) -> Tensor:
+    """(batch, sources, time) read in place through its batch and source strides; only the samples must be adjacent."""
+    return x.contiguous() if x.shape[-1] > 1 and x.stride(-1) != 1 else x
+
+
+def _pit_launch(mode: int, zero_mean: bool, p3: Tensor, t3: Tensor, len1: Optional[Tensor], minimize: bool,
+                want_matrix: bool, want_best: bool):
+    """The four forward launches: (matrix (B, S, S) or None, best_metric (B,), best_perm (B, S), the chosen pairs' (B, S, 8)
+    float64 statistics -- the last three None unless ``want_best``)."""
+    B, S, T_ = p3.shape
+    odt = torch.float64 if p3.dtype == torch.float64 else torch.float32
+    matrix = torch.empty((B, S, S), dtype=odt, device=p3.device) if want_matrix else None
+    best = torch.empty((B,), dtype=odt, device=p3.device) if want_best else None
+    perm = torch.empty((B, S), dtype=torch.int64, device=p3.device) if want_best else None
+    stat = torch.empty((B, S, 8), dtype=torch.float64, device=p3.device) if want_best else None
+    if B:
+        lib = _lib.lib()
+        ws = torch.empty((max(int(lib.aamd_pit_workspace(B, S, T_)) // 8, 1),), dtype=torch.float64, device=p3.device)
+        with torch.cuda.device(p3.device):
+            _lib.check(lib.aamd_pit_forward(_SA_DTYPES[p3.dtype], mode, _lib.ptr(p3) or None, _lib.ptr(t3) or None, B, S, T_,
+                                            p3.stride(0), p3.stride(1), t3.stride(0), t3.stride(1), *_sdr_len_args(len1),
+                                            int(bool(zero_mean)), int(bool(minimize)), ws.data_ptr(),
+                                            *(x.data_ptr() if x is not None else None for x in (matrix, best, perm, stat)),
+                                            _lib.current_stream(p3.device)))
+    return matrix, best, perm, stat
+
+
+class _PitFunction(torch.autograd.Function):
+    """(best_metric, best_perm).  What is kept for backward is the two waveforms, the permutation and eight float64
+    statistics per chosen pair; the gradient is one launch, formed once: a second derivative raises."""
+
+    @staticmethod
+    def forward(ctx, preds, target, lengths, mode, zero_mean, minimize):
+        p3, t3 = _pit_rows(preds.detach()), _pit_rows(target.detach())
+        len1 = lengths.contiguous() if lengths is not None else None
+        _, best, perm, stat = _pit_launch(mode, zero_mean, p3, t3, len1, minimize, False, True)
+        ctx.save_for_backward(p3, t3, len1, stat, perm)
+        ctx.pit_mode = mode
+        ctx.mark_non_differentiable(perm)
+        return best, perm
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_best, _grad_perm):
+        p3, t3, len1, stat, perm = ctx.saved_tensors
+        B, S, T_ = p3.shape
+        cot = grad_best.reshape(-1).to(torch.float64).contiguous()
+        grads = [torch.empty((B, S, T_), dtype=p3.dtype, device=p3.device) if need else None for need in ctx.needs_input_grad[:2]]
+        if B and T_:
+            lib = _lib.lib()
+            with torch.cuda.device(p3.device):
+                _lib.check(lib.aamd_pit_grad(_SA_DTYPES[p3.dtype], ctx.pit_mode, _lib.ptr(p3), _lib.ptr(t3), B, S, T_, p3.stride(0),
+                                             p3.stride(1), t3.stride(0), t3.stride(1), *_sdr_len_args(len1), stat.data_ptr(),
+                                             perm.data_ptr(), cot.data_ptr(),
+                                             grads[0].data_ptr() if grads[0] is not None else None,
+                                             grads[1].data_ptr() if grads[1] is not None else None,
+                                             _lib.current_stream(p3.device)))
+        return tuple(grads) + (None, None, None, None)
+
+
+def _pit_eval(name: str, eval_func: str) -> bool:
+    if eval_func not in ("max", "min"):
+        raise ValueError(f"audio_amd: {name}: eval_func must be 'max' or 'min' (got {eval_func!r})")
+    return eval_func == "min"
+
+
+def _pit_generic_matrix(name: str, preds: Tensor, target: Tensor, metric_func, kwargs) -> Tensor:
+    B, S, T_ = preds.shape
+    m = metric_func(preds[:, :, None].expand(B, S, S, T_), target[:, None, :].expand(B, S, S, T_), **kwargs)
+    if not isinstance(m, Tensor) or tuple(m.shape) != (B, S, S):
+        raise ValueError(f"audio_amd: {name}: metric_func must return a tensor of shape {(B, S, S)} for inputs of shape "
+                         f"{(B, S, S, T_)}, got {tuple(m.shape) if isinstance(m, Tensor) else type(m).__name__}")
+    return m
+
+
+def pit_metric_matrix(preds: Tensor, target: Tensor, metric_func, lengths: Optional[Tensor] = None, **kwargs) -> Tensor:
+    r"""``(batch, sources, sources)``: ``matrix[b, i, j]`` is the metric of ``preds[b, i]`` against ``target[b, j]``, for
+    ``preds`` and ``target`` of shape ``(batch, sources, time)``.  ``metric_func`` and ``lengths`` as in
+    ``permutation_invariant_training``: the three fused metrics are computed by the pairwise kernels (four launches, each
+    waveform read twice, no expanded copies; forward-only here), any other callable is called once on the broadcast
+    ``(batch, sources, sources, time)`` views and its result is returned."""
+    name = "pit_metric_matrix"
+    fused = _pit_fused(metric_func, kwargs)
+    _pit_check(name, preds, target, lengths, fused is not None)
+    if fused is None:
+        return _pit_generic_matrix(name, preds, target, metric_func, kwargs)
+    if torch.is_grad_enabled() and (preds.requires_grad or target.requires_grad):
+        raise RuntimeError(f"audio_amd: {name} is forward-only for the fused metrics (the gradient implemented is that of "
+                           "permutation_invariant_training's best_metric); wrap the call in torch.no_grad() or detach the "
+                           "waveforms.")
+    len1 = lengths.contiguous() if lengths is not None else None
+    return _pit_launch(fused[1], fused[2], _pit_rows(preds.detach()), _pit_rows(target.detach()), len1, False, True, False)[0]
+
+
+def pit_assignment(matrix: Tensor, eval_func: str = "max") -> Tuple[Tensor, Tensor]:
+    r"""The best assignment of estimates to references for any ``(batch, sources, sources)`` float32 / float64 score matrix
+    on the device, ``sources <= 8``: ``(best_metric (batch,), best_perm (batch, sources) int64)`` with
+    ``best_perm[b, i] = j`` assigning row ``i`` to column ``j`` and ``best_metric[b]`` the mean of the chosen entries.  An
+    on-device replacement for the host's ``linear_sum_assignment``: one launch, one workgroup per example, a subset DP with
+    one lane per subset of columns; nothing is read back and the call can be captured in a graph.
+
+    Totals are right-nested float64 sums ``M[0][p0] + (M[1][p1] + ...)``; among permutations of equal total the
+    lexicographically smallest wins, for ``"max"`` and ``"min"`` alike.  An example whose matrix holds a NaN gets a NaN
+    metric and the identity; infinities are compared as IEEE compares them.  Forward-only."""
+    name = "pit_assignment"
+    minimize = _pit_eval(name, eval_func)
+    if not isinstance(matrix, Tensor):
+        raise TypeError(f"audio_amd: {name}: matrix must be a tensor")
+    if matrix.dim() != 3 or matrix.shape[1] != matrix.shape[2] or matrix.shape[1] == 0:
+        raise ValueError(f"audio_amd: {name} expects (batch, sources, sources) with at least one source, got {tuple(matrix.shape)}")
+    if matrix.shape[1] > PIT_MAX_SOURCES:
+        raise NotImplementedError(f"audio_amd: {name}: more than PIT_MAX_SOURCES = {PIT_MAX_SOURCES} sources are not implemented "
+                                  f"(got {matrix.shape[1]})")
+    if matrix.dtype not in (torch.float32, torch.float64):
+        raise TypeError(f"audio_amd: {name}: matrix must be float32 or float64 (got {matrix.dtype})")
+    if not matrix.is_cuda:
+        raise RuntimeError(f"audio_amd: {name}: matrix must be on an MI355X (ROCm) device, got {matrix.device}. "
+                           "The HIP kernels have no CPU fallback.")
+    m = matrix.detach().contiguous()
+    B, S = m.shape[:2]
+    best = torch.empty((B,), dtype=m.dtype, device=m.device)
+    perm = torch.empty((B, S), dtype=torch.int64, device=m.device)
+    if B:
+        with torch.cuda.device(m.device):
+            _lib.check(_lib.lib().aamd_pit_assign(_SA_DTYPES[m.dtype], m.data_ptr(), B, S, int(minimize), best.data_ptr(),
+                                                  perm.data_ptr(), _lib.current_stream(m.device)))
+    return best, perm
+
+
+_PIT_NAN_BITS = {torch.float16: 0x7E00, torch.bfloat16: 0x7FC0, torch.float32: 0x7FC00000, torch.float64: 0x7FF8000000000000}
+
+
+def pit_permutate(preds: Tensor, perm: Tensor) -> Tensor:
+    r"""``out[b, i] = preds[b, perm[b, i]]`` for ``preds`` of shape ``(batch, sources, ...)`` and ``perm`` of shape
+    ``(batch, sources)`` (torchmetrics' ``pit_permutate``): the estimates reordered to line up with the references under
+    ``best_perm``'s convention.  One streaming row-gather launch with 16-byte accesses; ``perm`` is read on the device.  An
+    index outside ``[0, sources)`` is not used as one: its row is NaN for floating dtypes and zero for integers.
+    Forward-only."""
+    name = "pit_permutate"
+    if not isinstance(preds, Tensor) or not isinstance(perm, Tensor):
+        raise TypeError(f"audio_amd: {name}: preds and perm must be tensors")
+    if preds.dim() < 2 or tuple(perm.shape) != tuple(preds.shape[:2]):
+        raise ValueError(f"audio_amd: {name} expects preds (batch, sources, ...) and perm (batch, sources), got "
+                         f"{tuple(preds.shape)} and {tuple(perm.shape)}")
+    if perm.dtype not in (torch.int32, torch.int64):
+        raise TypeError(f"audio_amd: {name}: perm must be int32 or int64 (got {perm.dtype})")
+    if preds.is_complex() or preds.element_size() not in (1, 2, 4, 8):
+        raise TypeError(f"audio_amd: {name}: preds must be a real tensor (got {preds.dtype})")
+    if torch.is_grad_enabled() and preds.requires_grad:
+        raise RuntimeError(f"audio_amd: {name} is forward-only (no gradient is implemented); wrap the call in torch.no_grad() "
+                           "or detach preds.")
+    for t, what in ((preds, "preds"), (perm, "perm")):
+        if not t.is_cuda:
+            raise RuntimeError(f"audio_amd: {name}: {what} must be on an MI355X (ROCm) device, got {t.device}. "
+                               "The HIP kernels have no CPU fallback.")
+        if t.device != preds.device:
+            raise RuntimeError(f"audio_amd: {name}: {what} must be on the preds' device")
+    B, S = preds.shape[:2]
+    out = torch.empty(preds.shape, dtype=preds.dtype, device=preds.device)
+    src = preds.detach().reshape(B, S, -1) if B and S else preds.detach().reshape(B, S, 0)
+    R = src.shape[2]
+    if R > 1 and src.stride(2) != 1:
+        src = src.contiguous()
+    if B and S and R:
+        idx = perm.to(torch.int64).contiguous()
+        with torch.cuda.device(preds.device):
+            _lib.check(_lib.lib().aamd_pit_permutate(preds.element_size(), src.data_ptr(), idx.data_ptr(), B, S, R, src.stride(0),
+                                                     src.stride(1), _PIT_NAN_BITS.get(preds.dtype, 0), out.data_ptr(),
+                                                     _lib.current_stream(preds.device)))
+    return out
+
+
+def permutation_invariant_training(preds: Tensor, target: Tensor, metric_func, mode: str = "speaker-wise",
+                                   eval_func: str = "max", lengths: Optional[Tensor] = None,
+                                   **kwargs) -> Tuple[Tensor, Tensor]:
+    r"""Permutation-invariant training (the argument order, names and meaning of torchmetrics'
+    ``permutation_invariant_training``): for ``preds`` and ``target`` of shape ``(batch, sources, time)`` the best assignment
+    of the ``sources`` estimates to the references under ``metric_func``.  Returns ``(best_metric (batch,), best_perm
+    (batch, sources) int64)``: ``best_perm[b, i] = j`` assigns estimate ``i`` to reference ``j`` and ``best_metric[b]`` is the
+    mean over ``i`` of ``matrix[b, i, best_perm[b, i]]``; ``eval_func`` ``"max"`` or ``"min"`` picks the largest or the
+    smallest total.  ``pit_permutate(preds, best_perm)`` lines the estimates up.  Up to ``PIT_MAX_SOURCES = 8`` sources.
+
+    The fused route: ``metric_func`` is ``scale_invariant_signal_distortion_ratio`` (honours ``zero_mean=``),
+    ``scale_invariant_signal_noise_ratio`` or ``signal_noise_ratio`` (honours ``zero_mean=``) of this module, or the name
+    as a string; any other keyword raises ``TypeError``.  Everything the ``sources^2`` scores need but the residual is in
+    the Gram matrix of an example's ``2 sources`` rows, taken on the float64 matrix cores in one read of the waveforms; the
+    residuals of all pairs are summed directly in a second read; the assignment is a subset DP in one workgroup per
+    example.  Four launches where the reference calls the metric on ``sources^2`` expanded pairs and, from
+    three sources on, copies the matrix to the host for ``scipy.optimize.linear_sum_assignment``.  All sums are float64 for
+    every dtype (float16, bfloat16, float32, float64; half types are widened on load); ``best_metric`` is float64 for
+    float64 input, otherwise float32.  ``lengths`` (``(batch,)``, int32 or int64, on the device) ends all rows of example b
+    at ``lengths[b]``; nothing at or beyond it is read.  No atomics, no read-back, nothing cached: two calls give the same
+    bits, example b of a batch equals the call on example b, an example with ``lengths[b]`` equals the call on
+    ``[..., :lengths[b]]``, and a first call can be captured in a graph.  Among permutations of equal total (a
+    right-nested float64 sum of the scores as returned) the lexicographically smallest wins.  An example with a non-finite
+    sample below its length or a length outside ``[0, time]`` has NaN scores: its metric is NaN and its permutation the
+    identity; other examples keep their bits.  Differentiable once in ``preds`` and ``target``: one launch writes
+    ``grad_preds[b, i]`` and ``grad_target[b, best_perm[b, i]]`` from the chosen pair, exactly zero at or beyond
+    ``lengths[b]``; ``best_perm`` carries no gradient; a second derivative raises.
+
+    The generic route: any other callable is called ONCE on the broadcast views ``preds[:, :, None]`` and
+    ``target[:, None, :]`` expanded to ``(batch, sources, sources, time)``, with ``**kwargs``, and must return
+    ``(batch, sources, sources)``; the same search kernel follows and ``best_metric`` is a ``torch.gather`` of the callable's
+    result, so gradients are whatever the callable supports.  This keeps ``signal_distortion_ratio`` and ``stoi`` usable;
+    the temporaries such a callable makes of the expanded views are its own business.  ``lengths`` with a generic callable
+    raises ``ValueError``.
+
+    ``ValueError`` for an unknown ``eval_func`` or ``mode``, inputs that are not 3-D, different shapes or no sources;
+    ``NotImplementedError`` for ``mode="permutation-wise"`` and for more than 8 sources; dtype, device and ``lengths``
+    errors as the separation metrics raise them.  A plain Python entry point through the C ABI."""
+    name = "permutation_invariant_training"
+    if mode == "permutation-wise":
+        raise NotImplementedError(f"audio_amd: {name}: mode 'permutation-wise' is not implemented; metrics that score a whole "
+                                  "permutation at once have no pairwise matrix")
+    if mode != "speaker-wise":
+        raise ValueError(f"audio_amd: {name}: mode must be 'speaker-wise' or 'permutation-wise' (got {mode!r})")
+    minimize = _pit_eval(name, eval_func)
+    fused = _pit_fused(metric_func, kwargs)
+    _pit_check(name, preds, target, lengths, fused is not None)
+    if fused is None:
+        m = _pit_generic_matrix(name, preds, target, metric_func, kwargs)
+        md = m.detach()
+        _, perm = pit_assignment(md if md.dtype in (torch.float32, torch.float64) else md.float(), eval_func)
+        return torch.gather(m, 2, perm.unsqueeze(-1)).squeeze(-1).mean(-1), perm
+    _, mode_, zero_mean = fused
+    if torch.is_grad_enabled() and (preds.requires_grad or target.requires_grad):
+        return _PitFunction.apply(preds, target, lengths, mode_, zero_mean, minimize)
+    len1 = lengths.contiguous() if lengths is not None else None
+    _, best, perm, _ = _pit_launch(mode_, zero_mean, _pit_rows(preds.detach()), _pit_rows(target.detach()), len1, minimize,
+                                   False, True)
+    return best, perm
 
 
 @_reduced_precision_io

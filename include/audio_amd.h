@@ -82,6 +82,10 @@
  *   aamd_si_sdr_grad          F.signal_distortion_ratio, F.scale_invariant_signal_distortion_ratio, F.signal_noise_ratio
  *                             (torchmetrics' float64 FFT correlations and dense solve; a chain of full-size temporaries and
  *                             its autograd graph); three launches each, no read-back -- additions to ABI 7
+ *   aamd_pit_forward, aamd_pit_assign, aamd_pit_grad,
+ *   aamd_pit_permutate        F.permutation_invariant_training, F.pit_assignment, F.pit_permutate (torchmetrics' metric call on
+ *                             S^2 expanded pairs and scipy's linear_sum_assignment on the host); four launches forward, one
+ *                             backward, no read-back -- additions to ABI 7
  *   aamd_detect_pitch_f32     F.detect_pitch_frequency (_compute_nccf + _find_max_per_frame + _median_smoothing in the
  *                             reference; an addition to ABI 7 as well)
  *
@@ -1167,6 +1171,52 @@ int aamd_si_sdr(int32_t dtype, int32_t mode, const void* preds, const void* targ
 int aamd_si_sdr_grad(int32_t dtype, int32_t mode, const void* preds, const void* target, int64_t rows, int64_t length,
                      int64_t preds_stride, int64_t target_stride, const void* lengths, int32_t lengths_int64,
                      const double* stat, const double* cotangent, void* grad_preds, void* grad_target, void* stream);
+
+/* ---- Permutation-invariant training (additions to ABI 7; csrc/pit.h) --------------------------------------------------- */
+
+/* which: 0 threads per workgroup, 1 samples per workgroup of the Gram kernel, 2 samples per workgroup of the pairwise
+ * residual kernel, 3 the most sources served. */
+int32_t aamd_pit_tiles(int32_t which);
+
+/* Bytes of the float64 workspace of aamd_pit_forward for `batch` examples of `sources` (1 ... 8) rows of `length` samples;
+ * 0 for no examples or sources outside that range. */
+int64_t aamd_pit_workspace(int64_t batch, int64_t sources, int64_t length);
+
+/* F.permutation_invariant_training / F.pit_metric_matrix with a fused metric.  preds and target: (batch, sources, length)
+ * of `dtype` (AAMD_SA_*), unit sample stride, batch and source strides in elements.  mode, zero_mean and eps as aamd_si_sdr.
+ * lengths: (batch,) int32 or int64 or null; all rows of example b end at lengths[b] and nothing at or beyond it is read.
+ * matrix[b][i][j]: the score of preds[b][i] against target[b][j]; best_perm[b][i] = j assigns estimate i to reference j, the
+ * assignment of the largest (minimize: smallest) total, the lexicographically smallest among equal totals; best_metric[b]:
+ * its mean; stat: (batch, sources, 8) float64 of the chosen pairs, read by aamd_pit_grad.  matrix and best_metric are
+ * float32, or float64 for AAMD_SA_F64; each of the four outputs may be null.  An example whose matrix holds a NaN gets a
+ * NaN metric and the identity.  sources above 8: AAMD_EUNSUPPORTED.  workspace: aamd_pit_workspace bytes, 8-byte aligned.
+ * Four launches, no synchronisation, no atomics, no cached table. */
+int aamd_pit_forward(int32_t dtype, int32_t mode, const void* preds, const void* target, int64_t batch, int64_t sources,
+                     int64_t length, int64_t preds_batch_stride, int64_t preds_source_stride, int64_t target_batch_stride,
+                     int64_t target_source_stride, const void* lengths, int32_t lengths_int64, int32_t zero_mean,
+                     int32_t minimize, void* workspace, void* matrix, void* best_metric, int64_t* best_perm, double* stat,
+                     void* stream);
+
+/* F.pit_assignment: the search of aamd_pit_forward on a ready dense (batch, sources, sources) matrix of AAMD_SA_F32 or
+ * AAMD_SA_F64; best_metric has the matrix's type.  One launch. */
+int aamd_pit_assign(int32_t dtype, const void* matrix, int64_t batch, int64_t sources, int32_t minimize, void* best_metric,
+                    int64_t* best_perm, void* stream);
+
+/* The gradient of aamd_pit_forward's best_metric: grad_preds[b][i] and grad_target[b][perm[b][i]] (either buffer may be
+ * null), dense (batch, sources, length) of `dtype`, from preds[b][i], target[b][perm[b][i]], stat[b][i] and
+ * cotangent[b] / sources, formed as aamd_si_sdr_grad forms them; elements at or beyond lengths[b] are exactly zero.  perm
+ * must be a permutation per example (an entry outside [0, sources) is read as the identity's).  One launch. */
+int aamd_pit_grad(int32_t dtype, int32_t mode, const void* preds, const void* target, int64_t batch, int64_t sources,
+                  int64_t length, int64_t preds_batch_stride, int64_t preds_source_stride, int64_t target_batch_stride,
+                  int64_t target_source_stride, const void* lengths, int32_t lengths_int64, const double* stat,
+                  const int64_t* perm, const double* cotangent, void* grad_preds, void* grad_target, void* stream);
+
+/* F.pit_permutate: out[b][i][:] = src[b][perm[b][i]][:] for rows of row_elems elements of elem_bytes (1, 2, 4 or 8) bytes,
+ * unit element stride, batch and source strides in elements; out is dense.  An entry of perm outside [0, sources) is not
+ * used as an index: its row is filled with the low elem_bytes bytes of `fill`.  One launch. */
+int aamd_pit_permutate(int32_t elem_bytes, const void* src, const int64_t* perm, int64_t batch, int64_t sources,
+                       int64_t row_elems, int64_t src_batch_stride, int64_t src_source_stride, uint64_t fill, void* out,
+                       void* stream);
 
 #ifdef __cplusplus
 }
