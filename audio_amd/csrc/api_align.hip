@@ -51,9 +51,8 @@ int aamd_forced_align(int32_t dtype, const void* log_probs, const void* targets,
   if (batch == 0) return AAMD_OK;
   AAMD_CHECK_ARG(log_probs && input_lengths && target_lengths && workspace && paths && scores && (targets || max_l == 0),
                  "null buffer");
-  const int es = dtype == AAMD_SA_F64 ? 8 : (dtype == AAMD_SA_F32 ? 4 : 2);
   AAMD_CHECK_ARG(((uintptr_t)workspace & 15) == 0, "forced_align: workspace must be 16-byte aligned");
-  AAMD_CHECK_ARG((((uintptr_t)log_probs | (uintptr_t)scores) & (uintptr_t)(es - 1)) == 0,
+  AAMD_CHECK_ARG((((uintptr_t)log_probs | (uintptr_t)scores) & (uintptr_t)(elem_size(dtype) - 1)) == 0,
                  "forced_align: log_probs or scores is not aligned to its element");
   fa::Args a{};
   a.lp = log_probs; a.targets = targets; a.in_len = input_lengths; a.tg_len = target_lengths;
@@ -62,14 +61,7 @@ int aamd_forced_align(int32_t dtype, const void* log_probs, const void* targets,
   a.paths = paths; a.scores = scores;
   fa::ws_bind(a, workspace);
   hipStream_t s = (hipStream_t)stream;
-  int rc;
-  switch (dtype) {
-    case AAMD_SA_F32: rc = forward_launch<wa::kF32>(a, s); break;
-    case AAMD_SA_F64: rc = forward_launch<wa::kF64>(a, s); break;
-    case AAMD_SA_F16: rc = forward_launch<wa::kF16>(a, s); break;
-    default: rc = forward_launch<wa::kBF16>(a, s); break;
-  }
-  if (rc != AAMD_OK) return rc;
+  AAMD_TRY(for_dtype(dtype, [&](auto dt) { return forward_launch<dt.value>(a, s); }));
   return launch(fa::backtrack_kernel, batch, fa::kBtThreads, 0, s, a);
 }
 

@@ -1,11 +1,13 @@
 // Launcher internals shared by the api_*.hip sources of libaudio_amd.so (definitions: api_common.hip): the error string,
-// argument / HIP checks, the kernel-selection policy, the device scope and properties, and the one launch idiom.
+// argument / HIP checks, the element-type vocabulary (sizes and the one dispatch), the kernel-selection policy, the device
+// scope and properties, and the one launch idiom.
 // Everything here is hidden: the library exports the aamd_* functions of include/audio_amd.h and nothing of this.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
 #include <string>
+#include <type_traits>
 #include <utility>
 
 #include "../../include/audio_amd.h"
@@ -30,7 +32,37 @@ int fail(int code, const std::string& msg);
                                  " at " #expr);                                          \
   } while (0)
 
+// a launcher call that failed has set the error string already: pass its code on (variadic for the commas of f<A, B>(..))
+#define AAMD_TRY(...) \
+  do { const int rc_ = (__VA_ARGS__); if (rc_ != AAMD_OK) return rc_; } while (0)
+
 int launch_check();
+
+// The element types AAMD_SA_F32 / F64 / F16 / BF16 of the type-generic families.  Sizes: an unknown code counts as a
+// two-byte type, as every range check that follows one of them expects.
+inline int elem_size(int32_t dtype) { return dtype == AAMD_SA_F64 ? 8 : (dtype == AAMD_SA_F32 ? 4 : 2); }   // storage
+inline int comp_size(int32_t dtype) { return dtype == AAMD_SA_F64 ? 8 : 4; }          // compute type: float for the half types
+inline double comp_eps(int32_t dtype) { return dtype == AAMD_SA_F64 ? 2.220446049250313e-16 : 1.1920928955078125e-07; }
+
+// The one dispatch over them: f(std::integral_constant<int, AAMD_SA_*>) for the type `dtype` names, so that a call site is
+//   return for_dtype(dtype, [&](auto dt) { return run<dt.value>(a, s); });
+// with dt.value the kernels' wa::kF32 .. wa::kBF16 (api_post.hip asserts that the two enumerations agree).  kNoF64: the
+// families without a float64 kernel instantiate none.  A code that is not served is refused here; an entry point whose
+// refusal has a text of its own checks before it dispatches.  (The arms stand in the order of the codes: it is the order in
+// which a source instantiates its kernels, hence their order in its code object.)
+constexpr bool kNoF64 = false;
+template <bool WITH_F64 = true, class F>
+int for_dtype(int32_t dtype, F&& f) {
+  switch (dtype) {
+    case AAMD_SA_F32: return f(std::integral_constant<int, AAMD_SA_F32>{});
+    case AAMD_SA_F64:
+      if constexpr (WITH_F64) return f(std::integral_constant<int, AAMD_SA_F64>{});
+      break;
+    case AAMD_SA_F16: return f(std::integral_constant<int, AAMD_SA_F16>{});
+    case AAMD_SA_BF16: return f(std::integral_constant<int, AAMD_SA_BF16>{});
+  }
+  return fail(AAMD_EINVAL, "audio_amd: unknown element type");
+}
 
 // Kernel-selection switches (tests / A-B experiments): a process-wide bit mask, initialised ONCE from the environment
 // (AAMD_FORCE_GENERIC, AAMD_MEL400_WIDE, AAMD_ISTFT_ATOMIC) and changed afterwards only through

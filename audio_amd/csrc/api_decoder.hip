@@ -8,8 +8,7 @@ namespace {
 
 template <int DT>
 int search_launch(const cd::Args& a, hipStream_t s) {
-  const int rc = launch(cd::row_kernel<DT>, cd::row_blocks(a.B * a.T), cd::kRowThreads, 0, s, a);
-  if (rc != AAMD_OK) return rc;
+  AAMD_TRY(launch(cd::row_kernel<DT>, cd::row_blocks(a.B * a.T), cd::kRowThreads, 0, s, a));
   return launch(cd::beam_kernel<DT>, a.B, cd::kBeamThreads, 0, s, a);
 }
 
@@ -48,22 +47,15 @@ int aamd_ctc_beam_search(int32_t dtype, const void* log_probs, const void* lengt
   AAMD_CHECK_ARG(blank >= 0 && blank < vocab, "ctc_beam_search: blank must lie in [0, vocab)");
   if (batch == 0) return AAMD_OK;
   AAMD_CHECK_ARG(log_probs && lengths && workspace && tokens && token_lengths && scores, "null buffer");
-  const int es = dtype == AAMD_SA_F64 ? 8 : (dtype == AAMD_SA_F32 ? 4 : 2);
   AAMD_CHECK_ARG(((uintptr_t)workspace & 15) == 0, "ctc_beam_search: workspace must be 16-byte aligned");
-  AAMD_CHECK_ARG(((uintptr_t)log_probs & (uintptr_t)(es - 1)) == 0, "ctc_beam_search: log_probs is not aligned to its element");
+  AAMD_CHECK_ARG(((uintptr_t)log_probs & (uintptr_t)(elem_size(dtype) - 1)) == 0, "ctc_beam_search: log_probs is not aligned to its element");
   cd::Args a{};
   a.lp = log_probs; a.len = lengths;
   a.B = batch; a.T = max_t; a.V = vocab;
   a.blank = blank; a.len64 = lengths_int64 ? 1 : 0; a.K = beam; a.N = nbest; a.thr = threshold;
   a.tokens = tokens; a.out_len = token_lengths; a.scores = scores;
   cd::ws_bind(a, workspace);
-  hipStream_t s = (hipStream_t)stream;
-  switch (dtype) {
-    case AAMD_SA_F32: return search_launch<wa::kF32>(a, s);
-    case AAMD_SA_F64: return search_launch<wa::kF64>(a, s);
-    case AAMD_SA_F16: return search_launch<wa::kF16>(a, s);
-    default: return search_launch<wa::kBF16>(a, s);
-  }
+  return for_dtype(dtype, [&](auto dt) { return search_launch<dt.value>(a, (hipStream_t)stream); });
 }
 
 }  // extern "C"

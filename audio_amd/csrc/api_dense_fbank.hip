@@ -30,10 +30,10 @@ int aamd_dense_fbank(int32_t dtype, const void* x, const float* w, void* out, in
   const int64_t tiles = dfb::tiles_per_row(frames);
   AAMD_CHECK_ARG(rows < (1ll << 31) && frames < (1ll << 40) && rows * tiles < (1ll << 31), "dense_fbank: too many rows or frames");
   AAMD_CHECK_ARG(x && w && out, "null buffer");
-  const int es = dtype == AAMD_SA_F32 ? 4 : 2;
-  AAMD_CHECK_ARG(((uintptr_t)x & (uintptr_t)(es - 1)) == 0, "dense_fbank: the input is not aligned to its element");
+  AAMD_CHECK_ARG(((uintptr_t)x & (uintptr_t)(elem_size(dtype) - 1)) == 0, "dense_fbank: the input is not aligned to its element");
   // (a lane stores 4 consecutive outputs in one access where n_out % 4 == 0)
-  AAMD_CHECK_ARG(((uintptr_t)out & (uintptr_t)((n_out % 4 == 0 ? 4 : 1) * es - 1)) == 0, "dense_fbank: the output is not aligned");
+  AAMD_CHECK_ARG(((uintptr_t)out & (uintptr_t)((n_out % 4 == 0 ? 4 : 1) * elem_size(dtype) - 1)) == 0,
+                 "dense_fbank: the output is not aligned");
   AAMD_CHECK_ARG(((uintptr_t)w & 15) == 0, "dense_fbank: the filterbank's image must be 16-byte aligned");
   dfb::Args a{};
   a.x = x; a.W = w; a.out = out;
@@ -43,15 +43,10 @@ int aamd_dense_fbank(int32_t dtype, const void* x, const float* w, void* out, in
   const size_t lds = (size_t)dfb::lds_floats(n_out) * sizeof(float);     // 20 .. 48 KB
   hipStream_t s = (hipStream_t)stream;
   const bool small = dfb::n_tiles(n_out) <= dfb::kSmallNT;
-#define AAMD_DFB_LAUNCH(DT)                                                                                    \
-  return small ? launch(dfb::dense_fbank_kernel<DT, true>, rows * tiles, dfb::kThreads, lds, s, a, tiles)       \
-               : launch(dfb::dense_fbank_kernel<DT, false>, rows * tiles, dfb::kThreads, lds, s, a, tiles)
-  switch (dtype) {
-    case AAMD_SA_F32: AAMD_DFB_LAUNCH(wa::kF32);
-    case AAMD_SA_F16: AAMD_DFB_LAUNCH(wa::kF16);
-    default: AAMD_DFB_LAUNCH(wa::kBF16);
-  }
-#undef AAMD_DFB_LAUNCH
+  return for_dtype<kNoF64>(dtype, [&](auto dt) {
+    return small ? launch(dfb::dense_fbank_kernel<dt.value, true>, rows * tiles, dfb::kThreads, lds, s, a, tiles)
+                 : launch(dfb::dense_fbank_kernel<dt.value, false>, rows * tiles, dfb::kThreads, lds, s, a, tiles);
+  });
 }
 
 }  // extern "C"

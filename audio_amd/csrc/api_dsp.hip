@@ -7,46 +7,35 @@ using namespace aamd;
 
 namespace {
 
-bool aligned(const void* p, int32_t dtype) {
-  const uintptr_t el = dtype == AAMD_SA_F64 ? 7 : (dtype == AAMD_SA_F32 ? 3 : 1);
-  return ((uintptr_t)p & el) == 0;
-}
-
-#define AAMD_DSP_DISPATCH(dtype, KERNEL, ...)                                        \
-  switch (dtype) {                                                                   \
-    case AAMD_SA_F32: return launch(KERNEL<wa::kF32>, __VA_ARGS__);                  \
-    case AAMD_SA_F64: return launch(KERNEL<wa::kF64>, __VA_ARGS__);                  \
-    case AAMD_SA_F16: return launch(KERNEL<wa::kF16>, __VA_ARGS__);                  \
-    default: return launch(KERNEL<wa::kBF16>, __VA_ARGS__);                          \
-  }
+bool aligned(const void* p, int32_t dtype) { return ((uintptr_t)p & (uintptr_t)(elem_size(dtype) - 1)) == 0; }
 
 int osc_sums(int32_t dtype, const dsp::OscArgs& a, hipStream_t s) {
-  AAMD_DSP_DISPATCH(dtype, dsp::osc_sums_kernel, a.rows * (a.chunks - 1), dsp::kThreads, 0, s, a)
+  return for_dtype(dtype, [&](auto dt) { return launch(dsp::osc_sums_kernel<dt.value>, a.rows * (a.chunks - 1), dsp::kThreads, 0, s, a); });
 }
 int osc_apply(int32_t dtype, const dsp::OscArgs& a, hipStream_t s) {
-  AAMD_DSP_DISPATCH(dtype, dsp::osc_apply_kernel, a.rows * a.chunks, dsp::kThreads, 0, s, a)
+  return for_dtype(dtype, [&](auto dt) { return launch(dsp::osc_apply_kernel<dt.value>, a.rows * a.chunks, dsp::kThreads, 0, s, a); });
 }
 int fw(int32_t dtype, const dsp::FwArgs& a, size_t lds, hipStream_t s) {
-  AAMD_DSP_DISPATCH(dtype, dsp::fw_kernel, a.rows * a.tiles, dsp::kThreads, lds, s, a)
+  return for_dtype(dtype, [&](auto dt) { return launch(dsp::fw_kernel<dt.value>, a.rows * a.tiles, dsp::kThreads, lds, s, a); });
 }
 int pitch(int32_t dtype, const dsp::PitchArgs& a, int64_t blocks, hipStream_t s) {
-  AAMD_DSP_DISPATCH(dtype, dsp::pitch_kernel, blocks, dsp::kThreads, 0, s, a)
+  return for_dtype(dtype, [&](auto dt) { return launch(dsp::pitch_kernel<dt.value>, blocks, dsp::kThreads, 0, s, a); });
 }
 
 int fw_gx(int32_t dtype, const dsp::FwGradArgs& a, size_t lds, hipStream_t s) {
-  AAMD_DSP_DISPATCH(dtype, dsp::fw_gx_kernel, a.rows * a.tiles, dsp::kThreads, lds, s, a)
+  return for_dtype(dtype, [&](auto dt) { return launch(dsp::fw_gx_kernel<dt.value>, a.rows * a.tiles, dsp::kThreads, lds, s, a); });
 }
 int fw_gh(int32_t dtype, const dsp::FwGradArgs& a, hipStream_t s) {
-  AAMD_DSP_DISPATCH(dtype, dsp::fw_gh_kernel, a.rows * a.units * a.lag_tiles, dsp::kThreads, 0, s, a)
+  return for_dtype(dtype, [&](auto dt) { return launch(dsp::fw_gh_kernel<dt.value>, a.rows * a.units * a.lag_tiles, dsp::kThreads, 0, s, a); });
 }
 int fw_gh_fold(int32_t dtype, const dsp::FwGradArgs& a, int64_t blocks, hipStream_t s) {
-  AAMD_DSP_DISPATCH(dtype, dsp::fw_gh_fold_kernel, blocks, dsp::kThreads, 0, s, a)
+  return for_dtype(dtype, [&](auto dt) { return launch(dsp::fw_gh_fold_kernel<dt.value>, blocks, dsp::kThreads, 0, s, a); });
 }
 int osc_grad_totals(int32_t dtype, const dsp::OscGradArgs& a, hipStream_t s) {
-  AAMD_DSP_DISPATCH(dtype, dsp::osc_grad_totals_kernel, a.o.rows * (a.o.chunks - 1), dsp::kThreads, 0, s, a)
+  return for_dtype(dtype, [&](auto dt) { return launch(dsp::osc_grad_totals_kernel<dt.value>, a.o.rows * (a.o.chunks - 1), dsp::kThreads, 0, s, a); });
 }
 int osc_grad_apply(int32_t dtype, const dsp::OscGradArgs& a, hipStream_t s) {
-  AAMD_DSP_DISPATCH(dtype, dsp::osc_grad_apply_kernel, a.o.rows * a.o.chunks, dsp::kThreads, 0, s, a)
+  return for_dtype(dtype, [&](auto dt) { return launch(dsp::osc_grad_apply_kernel<dt.value>, a.o.rows * a.o.chunks, dsp::kThreads, 0, s, a); });
 }
 
 bool any_float(int32_t dtype) { return dtype == AAMD_SA_F32 || dtype == AAMD_SA_F64 || dtype == AAMD_SA_F16 || dtype == AAMD_SA_BF16; }
@@ -58,8 +47,6 @@ extern "C" {
 int32_t aamd_dsp_tiles(int32_t which) {
   static_assert(dsp::kMaxTaps == AAMD_DSP_MAX_TAPS && dsp::kMaxOsc == AAMD_DSP_MAX_OSCILLATORS &&
                 dsp::kMaxMags == AAMD_DSP_MAX_MAGNITUDES, "the header's limits are the kernels'");
-  static_assert(wa::kF32 == AAMD_SA_F32 && wa::kF64 == AAMD_SA_F64 && wa::kF16 == AAMD_SA_F16 && wa::kBF16 == AAMD_SA_BF16,
-                "the element codes are the header's");
   static_assert(dsp::kSum == AAMD_DSP_SUM && dsp::kMean == AAMD_DSP_MEAN && dsp::kNone == AAMD_DSP_NONE, "the reduction codes");
   switch (which) {
     case 0: return dsp::kOscChunk;
@@ -96,10 +83,7 @@ int aamd_oscillator_bank(int32_t dtype, const void* freq, const void* amp, void*
   a.rows = rows; a.T = time; a.sf = freq_row_stride; a.sa = amp_row_stride; a.chunks = chunks;
   a.sample_rate = sample_rate; a.N = (int32_t)n; a.reduction = reduction;
   hipStream_t s = (hipStream_t)stream;
-  if (chunks > 1) {
-    const int rc = osc_sums(dtype, a, s);
-    if (rc != AAMD_OK) return rc;
-  }
+  if (chunks > 1) AAMD_TRY(osc_sums(dtype, a, s));
   return osc_apply(dtype, a, s);
 }
 
@@ -119,7 +103,7 @@ int aamd_filter_waveform(int32_t dtype, const void* x, const void* kernels, void
   a.x = x; a.h = kernels; a.out = out;
   a.rows = rows; a.T = time; a.sx = row_stride; a.F = num_filters; a.C = time / num_filters; a.tiles = tiles;
   a.L = taps; a.batched = batched ? 1 : 0;
-  const size_t lds = dsp::fw_lds_values(taps) * (dtype == AAMD_SA_F64 ? 8 : 4);
+  const size_t lds = dsp::fw_lds_values(taps) * comp_size(dtype);
   return fw(dtype, a, lds, (hipStream_t)stream);
 }
 
@@ -161,9 +145,8 @@ int aamd_oscillator_bank_grad(int32_t dtype, const void* freq, const void* amp, 
   hipStream_t s = (hipStream_t)stream;
   if (chunks > 1) {
     dsp::OscArgs o = a.o;
-    int rc = osc_sums(dtype, o, s);
-    if (rc == AAMD_OK && grad_freq) rc = osc_grad_totals(dtype, a, s);
-    if (rc != AAMD_OK) return rc;
+    AAMD_TRY(osc_sums(dtype, o, s));
+    if (grad_freq) AAMD_TRY(osc_grad_totals(dtype, a, s));
   }
   return osc_grad_apply(dtype, a, s);
 }
@@ -200,10 +183,7 @@ int aamd_filter_waveform_grad(int32_t dtype, const void* x, const void* kernels,
                      aligned(grad_kernels, dtype) && ((uintptr_t)workspace & 7) == 0,
                  "filter_waveform_grad: a buffer is misaligned");
   hipStream_t s = (hipStream_t)stream;
-  if (grad_x) {
-    const int rc = fw_gx(dtype, a, dsp::fw_lds_values(taps) * (dtype == AAMD_SA_F64 ? 8 : 4), s);
-    if (rc != AAMD_OK) return rc;
-  }
+  if (grad_x) AAMD_TRY(fw_gx(dtype, a, dsp::fw_lds_values(taps) * comp_size(dtype), s));
   if (!grad_kernels) return AAMD_OK;
   const int rc = fw_gh(dtype, a, s);
   if (rc != AAMD_OK || a.direct) return rc;
@@ -240,7 +220,7 @@ int aamd_frequency_impulse_response(int32_t dtype, const void* magnitudes, const
   AAMD_CHECK_ARG(aligned(magnitudes, dtype) && aligned(table, dtype) && aligned(out, dtype), "frequency_impulse_response: a buffer is misaligned");
   dsp::FirArgs a{};
   a.mags = magnitudes; a.table = table; a.out = out; a.rows = rows; a.n = n;
-  const size_t lds = ((size_t)n + 2 * ((size_t)n - 1)) * (dtype == AAMD_SA_F64 ? 8 : 4);
+  const size_t lds = ((size_t)n + 2 * ((size_t)n - 1)) * comp_size(dtype);
   if (lds > 48 * 1024 && dev_props().ok && lds > dev_props().lds_per_block_optin)
     return fail(AAMD_EUNSUPPORTED, "audio_amd: frequency_impulse_response: the tables do not fit the device's LDS");
   hipStream_t s = (hipStream_t)stream;

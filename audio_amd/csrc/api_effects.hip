@@ -6,8 +6,6 @@ using namespace aamd;
 
 namespace {
 
-int elem_size(int32_t dtype) { return dtype == AAMD_SA_F64 ? 8 : (dtype == AAMD_SA_F32 ? 4 : 2); }
-int comp_size(int32_t dtype) { return dtype == AAMD_SA_F64 ? 8 : 4; }
 bool ring_fits(int32_t dtype, int64_t L) {
   return dtype == AAMD_SA_F64 ? fx::ring_in_lds<double>(L) : fx::ring_in_lds<float>(L);
 }
@@ -27,21 +25,13 @@ int delay_launch(const fx::DelayArgs& a, hipStream_t s) {
 
 template <bool FLANGER>
 int delay_dispatch(int32_t dtype, const fx::DelayArgs& a, hipStream_t s) {
-  switch (dtype) {
-    case AAMD_SA_F32: return delay_launch<wa::kF32, FLANGER>(a, s);
-    case AAMD_SA_F64: return delay_launch<wa::kF64, FLANGER>(a, s);
-    case AAMD_SA_F16: return delay_launch<wa::kF16, FLANGER>(a, s);
-    default: return delay_launch<wa::kBF16, FLANGER>(a, s);
-  }
+  return for_dtype(dtype, [&](auto dt) { return delay_launch<dt.value, FLANGER>(a, s); });
 }
 
 template <int DT>
 int overdrive_launch(const fx::OdArgs& a, hipStream_t s) {
   const int64_t blocks = a.rows * a.chunks;
-  if (a.chunks > 1) {
-    const int rc = launch(fx::overdrive_reduce_kernel<DT>, blocks, fx::kOdThreads, 0, s, a);
-    if (rc != AAMD_OK) return rc;
-  }
+  if (a.chunks > 1) AAMD_TRY(launch(fx::overdrive_reduce_kernel<DT>, blocks, fx::kOdThreads, 0, s, a));
   return launch(fx::overdrive_apply_kernel<DT>, blocks, fx::kOdThreads, 0, s, a);
 }
 
@@ -84,13 +74,7 @@ int aamd_overdrive(int32_t dtype, const void* x, void* out, void* workspace, int
   a.gain = gain; a.colour = colour;
   AAMD_CHECK_ARG(rows * a.chunks < (1ll << 31), "overdrive: too many workgroups");
   AAMD_CHECK_ARG(a.chunks == 1 || (workspace && ((uintptr_t)workspace & 7) == 0), "overdrive: workspace missing or misaligned");
-  hipStream_t s = (hipStream_t)stream;
-  switch (dtype) {
-    case AAMD_SA_F32: return overdrive_launch<wa::kF32>(a, s);
-    case AAMD_SA_F64: return overdrive_launch<wa::kF64>(a, s);
-    case AAMD_SA_F16: return overdrive_launch<wa::kF16>(a, s);
-    default: return overdrive_launch<wa::kBF16>(a, s);
-  }
+  return for_dtype(dtype, [&](auto dt) { return overdrive_launch<dt.value>(a, (hipStream_t)stream); });
 }
 
 int aamd_phaser(int32_t dtype, const void* x, void* out, void* workspace, int64_t rows, int64_t length, int64_t row_stride,
@@ -145,12 +129,9 @@ int aamd_flanger(int32_t dtype, const void* x, void* out, void* workspace, int64
   if (feedback_gain == 0.0 && !general) {
     const int64_t chunks = wa::n_chunks(length);
     AAMD_CHECK_ARG(rows * chunks < (1ll << 31), "flanger: too many workgroups");
-    switch (dtype) {
-      case AAMD_SA_F32: return launch(fx::stream_kernel<wa::kF32>, rows * chunks, wa::kThreads, 0, s, a, chunks);
-      case AAMD_SA_F64: return launch(fx::stream_kernel<wa::kF64>, rows * chunks, wa::kThreads, 0, s, a, chunks);
-      case AAMD_SA_F16: return launch(fx::stream_kernel<wa::kF16>, rows * chunks, wa::kThreads, 0, s, a, chunks);
-      default: return launch(fx::stream_kernel<wa::kBF16>, rows * chunks, wa::kThreads, 0, s, a, chunks);
-    }
+    return for_dtype(dtype, [&](auto dt) {
+      return launch(fx::stream_kernel<dt.value>, rows * chunks, wa::kThreads, 0, s, a, chunks);
+    });
   }
   AAMD_CHECK_ARG(ring_fits(dtype, ring) || (workspace && ((uintptr_t)workspace & 15) == 0),
                  "flanger: workspace missing or misaligned");

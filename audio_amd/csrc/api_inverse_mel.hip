@@ -27,8 +27,7 @@ int aamd_inverse_mel(int32_t dtype, const void* x, const float* pinv, void* out,
   const int64_t tiles = iml::tiles_per_row(frames);
   AAMD_CHECK_ARG(rows < (1ll << 31) && frames < (1ll << 40) && rows * tiles < (1ll << 31), "inverse_mel: too many rows or frames");
   AAMD_CHECK_ARG(x && pinv && out, "null buffer");
-  const int es = dtype == AAMD_SA_F32 ? 4 : 2;
-  AAMD_CHECK_ARG((((uintptr_t)x | (uintptr_t)out) & (uintptr_t)(es - 1)) == 0, "inverse_mel: a buffer is not aligned to its element");
+  AAMD_CHECK_ARG((((uintptr_t)x | (uintptr_t)out) & (uintptr_t)(elem_size(dtype) - 1)) == 0, "inverse_mel: a buffer is not aligned to its element");
   AAMD_CHECK_ARG(((uintptr_t)pinv & 15) == 0, "inverse_mel: the pseudo-inverse's tiles must be 16-byte aligned");
   iml::Args a{};
   a.x = x; a.P = pinv; a.out = out;
@@ -40,11 +39,9 @@ int aamd_inverse_mel(int32_t dtype, const void* x, const float* pinv, void* out,
   if (lds > 48 * 1024 && lds > dev_props().lds_per_block_optin)
     return fail(AAMD_EUNSUPPORTED, "audio_amd: inverse_mel: this device has less LDS than the tiles were planned for");
   hipStream_t s = (hipStream_t)stream;
-  switch (dtype) {
-    case AAMD_SA_F32: return launch(iml::inverse_mel_kernel<wa::kF32>, rows * tiles, iml::kThreads, lds, s, a, tiles);
-    case AAMD_SA_F16: return launch(iml::inverse_mel_kernel<wa::kF16>, rows * tiles, iml::kThreads, lds, s, a, tiles);
-    default: return launch(iml::inverse_mel_kernel<wa::kBF16>, rows * tiles, iml::kThreads, lds, s, a, tiles);
-  }
+  return for_dtype<kNoF64>(dtype, [&](auto dt) {
+    return launch(iml::inverse_mel_kernel<dt.value>, rows * tiles, iml::kThreads, lds, s, a, tiles);
+  });
 }
 
 }  // extern "C"

@@ -31,8 +31,6 @@ Layout layout_of(int64_t B, int64_t S, int64_t T) {
   return l;
 }
 
-size_t elem_size(int32_t dtype) { return dtype == AAMD_SA_F64 ? 8 : (dtype == AAMD_SA_F32 ? 4 : 2); }
-
 // the checks the waveform entry points share; fills what the kernels read of the inputs
 int common(const char* who, pit::Args& a, int32_t dtype, int32_t mode, const void* preds, const void* target, int64_t batch,
            int64_t sources, int64_t length, int64_t pb, int64_t ps, int64_t tb, int64_t ts, const void* lengths,
@@ -46,13 +44,13 @@ int common(const char* who, pit::Args& a, int32_t dtype, int32_t mode, const voi
     return fail(AAMD_EUNSUPPORTED, "audio_amd: " + w + ": more than " + std::to_string(pit::kMaxS) + " sources are not implemented");
   AAMD_CHECK_ARG(batch < (1ll << 31) && length < (1ll << 40), w + ": too many examples or samples");
   AAMD_CHECK_ARG((preds && target) || length == 0 || batch == 0, w + ": null buffer");
-  AAMD_CHECK_ARG((((uintptr_t)preds | (uintptr_t)target) & (elem_size(dtype) - 1)) == 0, w + ": a waveform is not aligned to its element");
+  AAMD_CHECK_ARG((((uintptr_t)preds | (uintptr_t)target) & (uintptr_t)(elem_size(dtype) - 1)) == 0, w + ": a waveform is not aligned to its element");
   AAMD_CHECK_ARG(((uintptr_t)lengths & (lengths_int64 ? 7 : 3)) == 0, w + ": lengths is misaligned");
   a.p = preds; a.t = target; a.lengths = lengths;
   a.B = batch; a.S = (int32_t)sources; a.T = length;
   a.pb = batch > 1 ? pb : 0; a.ps = sources > 1 ? ps : 0; a.tb = batch > 1 ? tb : 0; a.ts = sources > 1 ? ts : 0;
   a.len64 = lengths_int64 ? 1 : 0; a.zero_mean = zero_mean ? 1 : 0; a.mode = mode;
-  a.eps = dtype == AAMD_SA_F64 ? 2.220446049250313e-16 : 1.1920928955078125e-07;
+  a.eps = comp_eps(dtype);
   const Layout l = layout_of(batch, sources, length);
   a.gspans = l.gspans; a.rparts = l.rparts; a.chunks = l.chunks;
   a.gchunks = length > 0 ? sdr::ceil_div(length, sdr::kChunk) : 1;
@@ -63,17 +61,14 @@ int common(const char* who, pit::Args& a, int32_t dtype, int32_t mode, const voi
 template <int DT>
 int run_forward(const pit::Args& a, hipStream_t s) {
   using C = typename wa::Elem<DT>::C;
-  int rc = launch(pit::gram_kernel<DT>, a.B * a.gspans, pit::kThreads, 0, s, a);
-  if (rc != AAMD_OK) return rc;
-  rc = launch(pit::pair_stats_kernel<DT>, a.B, sdr::kSolveThreads, 0, s, a);
-  if (rc != AAMD_OK) return rc;
+  AAMD_TRY(launch(pit::gram_kernel<DT>, a.B * a.gspans, pit::kThreads, 0, s, a));
+  AAMD_TRY(launch(pit::pair_stats_kernel<DT>, a.B, sdr::kSolveThreads, 0, s, a));
   switch (pit::res_bucket(a.S)) {
-    case 1: rc = launch(pit::pair_residual_kernel<DT, 1>, a.B * a.chunks, pit::kThreads, 0, s, a); break;
-    case 2: rc = launch(pit::pair_residual_kernel<DT, 2>, a.B * a.chunks, pit::kThreads, 0, s, a); break;
-    case 4: rc = launch(pit::pair_residual_kernel<DT, 4>, a.B * a.chunks, pit::kThreads, 0, s, a); break;
-    default: rc = launch(pit::pair_residual_kernel<DT, 8>, a.B * a.chunks, pit::kThreads, 0, s, a); break;
+    case 1: AAMD_TRY(launch(pit::pair_residual_kernel<DT, 1>, a.B * a.chunks, pit::kThreads, 0, s, a)); break;
+    case 2: AAMD_TRY(launch(pit::pair_residual_kernel<DT, 2>, a.B * a.chunks, pit::kThreads, 0, s, a)); break;
+    case 4: AAMD_TRY(launch(pit::pair_residual_kernel<DT, 4>, a.B * a.chunks, pit::kThreads, 0, s, a)); break;
+    default: AAMD_TRY(launch(pit::pair_residual_kernel<DT, 8>, a.B * a.chunks, pit::kThreads, 0, s, a)); break;
   }
-  if (rc != AAMD_OK) return rc;
   return launch(pit::assign_kernel<C>, a.B, pit::kThreads, 0, s, a);
 }
 
@@ -81,14 +76,6 @@ template <int DT>
 int run_grad(const pit::Args& a, hipStream_t s) {
   return launch(pit::pit_grad_kernel<DT>, a.B * a.S * a.gchunks, pit::kThreads, 0, s, a);
 }
-
-#define AAMD_PIT_DISPATCH(fn, dtype, a, s)                      \
-  switch (dtype) {                                              \
-    case AAMD_SA_F32: return fn<wa::kF32>(a, s);                \
-    case AAMD_SA_F64: return fn<wa::kF64>(a, s);                \
-    case AAMD_SA_F16: return fn<wa::kF16>(a, s);                \
-    default: return fn<wa::kBF16>(a, s);                        \
-  }
 
 }  // namespace
 
@@ -116,12 +103,11 @@ int aamd_pit_forward(int32_t dtype, int32_t mode, const void* preds, const void*
                      void* stream) {
   DeviceScope dev_scope_(workspace);
   pit::Args a{};
-  int rc = common("pit_forward", a, dtype, mode, preds, target, batch, sources, length, preds_batch_stride, preds_source_stride,
-                  target_batch_stride, target_source_stride, lengths, lengths_int64, zero_mean);
-  if (rc != AAMD_OK) return rc;
+  AAMD_TRY(common("pit_forward", a, dtype, mode, preds, target, batch, sources, length, preds_batch_stride, preds_source_stride,
+                  target_batch_stride, target_source_stride, lengths, lengths_int64, zero_mean));
   if (batch == 0) return AAMD_OK;
   AAMD_CHECK_ARG(workspace, "pit_forward: null buffer");
-  const uintptr_t omask = dtype == AAMD_SA_F64 ? 7 : 3;
+  const uintptr_t omask = (uintptr_t)(comp_size(dtype) - 1);
   AAMD_CHECK_ARG((((uintptr_t)workspace | (uintptr_t)stat | (uintptr_t)best_perm) & 7) == 0 &&
                      (((uintptr_t)matrix | (uintptr_t)best_metric) & omask) == 0, "pit_forward: a buffer is misaligned");
   const Layout l = layout_of(batch, sources, length);
@@ -132,8 +118,7 @@ int aamd_pit_forward(int32_t dtype, int32_t mode, const void* preds, const void*
   a.res = reinterpret_cast<double*>(ws + l.res);
   a.minimize = minimize ? 1 : 0;
   a.mout = matrix; a.best = best_metric; a.perm = best_perm; a.stat = stat;
-  hipStream_t s = (hipStream_t)stream;
-  AAMD_PIT_DISPATCH(run_forward, dtype, a, s)
+  return for_dtype(dtype, [&](auto dt) { return run_forward<dt.value>(a, (hipStream_t)stream); });
 }
 
 int aamd_pit_assign(int32_t dtype, const void* matrix, int64_t batch, int64_t sources, int32_t minimize, void* best_metric,
@@ -146,7 +131,7 @@ int aamd_pit_assign(int32_t dtype, const void* matrix, int64_t batch, int64_t so
     return fail(AAMD_EUNSUPPORTED, "audio_amd: pit_assign: more than " + std::to_string(pit::kMaxS) + " sources are not implemented");
   if (batch == 0) return AAMD_OK;
   AAMD_CHECK_ARG(matrix && best_metric && best_perm, "pit_assign: null buffer");
-  const uintptr_t omask = dtype == AAMD_SA_F64 ? 7 : 3;
+  const uintptr_t omask = (uintptr_t)(comp_size(dtype) - 1);
   AAMD_CHECK_ARG((((uintptr_t)matrix | (uintptr_t)best_metric) & omask) == 0 && ((uintptr_t)best_perm & 7) == 0,
                  "pit_assign: a buffer is misaligned");
   pit::Args a{};
@@ -163,18 +148,16 @@ int aamd_pit_grad(int32_t dtype, int32_t mode, const void* preds, const void* ta
                   const int64_t* perm, const double* cotangent, void* grad_preds, void* grad_target, void* stream) {
   DeviceScope dev_scope_(stat);
   pit::Args a{};
-  int rc = common("pit_grad", a, dtype, mode, preds, target, batch, sources, length, preds_batch_stride, preds_source_stride,
-                  target_batch_stride, target_source_stride, lengths, lengths_int64, 0);
-  if (rc != AAMD_OK) return rc;
+  AAMD_TRY(common("pit_grad", a, dtype, mode, preds, target, batch, sources, length, preds_batch_stride, preds_source_stride,
+                  target_batch_stride, target_source_stride, lengths, lengths_int64, 0));
   if (batch == 0 || length == 0 || (!grad_preds && !grad_target)) return AAMD_OK;
   AAMD_CHECK_ARG(stat && perm && cotangent, "pit_grad: null buffer");
   AAMD_CHECK_ARG((((uintptr_t)stat | (uintptr_t)perm | (uintptr_t)cotangent) & 7) == 0 &&
-                     (((uintptr_t)grad_preds | (uintptr_t)grad_target) & (elem_size(dtype) - 1)) == 0, "pit_grad: a buffer is misaligned");
+                     (((uintptr_t)grad_preds | (uintptr_t)grad_target) & (uintptr_t)(elem_size(dtype) - 1)) == 0, "pit_grad: a buffer is misaligned");
   a.stat = const_cast<double*>(stat);
   a.perm_in = perm; a.cot = cotangent;
   a.gp = grad_preds; a.gt = grad_target;
-  hipStream_t s = (hipStream_t)stream;
-  AAMD_PIT_DISPATCH(run_grad, dtype, a, s)
+  return for_dtype(dtype, [&](auto dt) { return run_grad<dt.value>(a, (hipStream_t)stream); });
 }
 
 int aamd_pit_permutate(int32_t elem_bytes, const void* src, const int64_t* perm, int64_t batch, int64_t sources,

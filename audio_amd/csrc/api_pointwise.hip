@@ -6,12 +6,14 @@ using namespace aamd;
 
 namespace {
 
-int elem_size(int32_t dtype) {
+// elem_size with the integer codes of mu_decode
+int input_size(int32_t dtype) {
   switch (dtype) {
-    case AAMD_SA_F64: case AAMD_PW_I64: return 8;
-    case AAMD_SA_F32: case AAMD_PW_I32: return 4;
-    case AAMD_SA_F16: case AAMD_SA_BF16: case AAMD_PW_I16: return 2;
-    default: return 1;
+    case AAMD_PW_I64: return 8;
+    case AAMD_PW_I32: return 4;
+    case AAMD_PW_I16: return 2;
+    case AAMD_PW_I8: case AAMD_PW_U8: return 1;
+    default: return elem_size(dtype);
   }
 }
 
@@ -23,12 +25,7 @@ int run(const pw::Args& a, hipStream_t s) {
 // the four floating types, result in the input's type
 template <int OP>
 int run_float(int32_t dtype, const pw::Args& a, hipStream_t s) {
-  switch (dtype) {
-    case AAMD_SA_F32: return run<OP, wa::kF32, wa::kF32>(a, s);
-    case AAMD_SA_F64: return run<OP, wa::kF64, wa::kF64>(a, s);
-    case AAMD_SA_F16: return run<OP, wa::kF16, wa::kF16>(a, s);
-    default: return run<OP, wa::kBF16, wa::kBF16>(a, s);
-  }
+  return for_dtype(dtype, [&](auto dt) { return run<OP, dt.value, dt.value>(a, s); });
 }
 
 }  // namespace
@@ -57,7 +54,7 @@ int aamd_pointwise(int32_t op, int32_t dtype, const void* x, void* out, int64_t 
   if (rows == 0 || length == 0) return AAMD_OK;
   AAMD_CHECK_ARG(x && out, "null buffer");
   const int out_size = op == AAMD_PW_MU_ENCODE ? 8 : (dtype > AAMD_SA_BF16 ? 4 : elem_size(dtype));
-  AAMD_CHECK_ARG(((uintptr_t)x & (uintptr_t)(elem_size(dtype) - 1)) == 0 && ((uintptr_t)out & (uintptr_t)(out_size - 1)) == 0,
+  AAMD_CHECK_ARG(((uintptr_t)x & (uintptr_t)(input_size(dtype) - 1)) == 0 && ((uintptr_t)out & (uintptr_t)(out_size - 1)) == 0,
                  "pointwise: a buffer is not aligned to its element");
   pw::Args a{};
   a.x = x; a.out = out; a.rows = rows; a.L = length; a.sx = rows > 1 ? row_stride : 0; a.chunks = pw::n_chunks(length);

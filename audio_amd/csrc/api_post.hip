@@ -9,6 +9,10 @@
 
 using namespace aamd;
 
+// for_dtype (api_common.h) hands the launchers AAMD_SA_* codes; the kernels' templates take wa::k*
+static_assert(wa::kF32 == AAMD_SA_F32 && wa::kF64 == AAMD_SA_F64 && wa::kF16 == AAMD_SA_F16 && wa::kBF16 == AAMD_SA_BF16,
+              "the element codes are the header's");
+
 namespace {
 
 // ---- feature post-processing: deltas and sliding-window CMN (csrc/feat_post.h) -----------------------------------------
@@ -50,8 +54,7 @@ int sliding_window_cmn(const T* x, T* out, void* workspace, int64_t channels, in
   AAMD_CHECK_ARG(blocks < (1ll << 31), "too many chunks for one launch");
   hipStream_t s = (hipStream_t)stream;
   double* ws = static_cast<double*>(workspace);
-  int rc = launch(fp::cmn_chunk_kernel<T>, blocks, g.threads, 0, s, x, ws, g);
-  if (rc != AAMD_OK) return rc;
+  AAMD_TRY(launch(fp::cmn_chunk_kernel<T>, blocks, g.threads, 0, s, x, ws, g));
   return launch(fp::cmn_walk_kernel<T>, blocks, g.threads, 0, s, x, ws, out, g);
 }
 
@@ -128,8 +131,7 @@ int spec_augment(const void* x, void* out, int64_t examples, int64_t n_outer, in
 // ---- waveform augmentation: add_noise and preemphasis (csrc/wave_augment.h) ----------------------------------------------
 template <int DT>
 int add_noise_launch(const wa::NoiseArgs& a, int64_t blocks, hipStream_t s) {
-  int rc = launch(wa::add_noise_reduce_kernel<DT>, blocks, wa::kThreads, 0, s, a);
-  if (rc != AAMD_OK) return rc;
+  AAMD_TRY(launch(wa::add_noise_reduce_kernel<DT>, blocks, wa::kThreads, 0, s, a));
   return launch(wa::add_noise_apply_kernel<DT>, blocks, wa::kThreads, 0, s, a);
 }
 
@@ -153,14 +155,8 @@ int add_noise(int32_t dtype, const void* w, const void* n, const void* g, void* 
   a.grad = mode == AAMD_ADD_NOISE_GRADIENT;
   const int64_t blocks = rows * a.chunks;
   AAMD_CHECK_ARG(blocks < (1ll << 31), "too many chunks for one launch");
-  hipStream_t s = (hipStream_t)stream;
-  switch (dtype) {
-    case AAMD_SA_F32: return add_noise_launch<wa::kF32>(a, blocks, s);
-    case AAMD_SA_F64: return add_noise_launch<wa::kF64>(a, blocks, s);
-    case AAMD_SA_F16: return add_noise_launch<wa::kF16>(a, blocks, s);
-    case AAMD_SA_BF16: return add_noise_launch<wa::kBF16>(a, blocks, s);
-    default: return fail(AAMD_EINVAL, "audio_amd: add_noise: unknown element type");
-  }
+  AAMD_CHECK_ARG(dtype >= AAMD_SA_F32 && dtype <= AAMD_SA_BF16, "add_noise: unknown element type");
+  return for_dtype(dtype, [&](auto dt) { return add_noise_launch<dt.value>(a, blocks, (hipStream_t)stream); });
 }
 
 int preemphasis(int32_t dtype, const void* x, void* out, int64_t rows, int64_t length, int64_t stride_row, double coeff,
@@ -174,14 +170,10 @@ int preemphasis(int32_t dtype, const void* x, void* out, int64_t rows, int64_t l
   a.coeff = coeff; a.transposed = transposed ? 1 : 0;
   const int64_t blocks = rows * a.chunks;
   AAMD_CHECK_ARG(blocks < (1ll << 31), "too many chunks for one launch");
-  hipStream_t s = (hipStream_t)stream;
-  switch (dtype) {
-    case AAMD_SA_F32: return launch(wa::preemphasis_kernel<wa::kF32>, blocks, wa::kThreads, 0, s, a);
-    case AAMD_SA_F64: return launch(wa::preemphasis_kernel<wa::kF64>, blocks, wa::kThreads, 0, s, a);
-    case AAMD_SA_F16: return launch(wa::preemphasis_kernel<wa::kF16>, blocks, wa::kThreads, 0, s, a);
-    case AAMD_SA_BF16: return launch(wa::preemphasis_kernel<wa::kBF16>, blocks, wa::kThreads, 0, s, a);
-    default: return fail(AAMD_EINVAL, "audio_amd: preemphasis: unknown element type");
-  }
+  AAMD_CHECK_ARG(dtype >= AAMD_SA_F32 && dtype <= AAMD_SA_BF16, "preemphasis: unknown element type");
+  return for_dtype(dtype, [&](auto dt) {
+    return launch(wa::preemphasis_kernel<dt.value>, blocks, wa::kThreads, 0, (hipStream_t)stream, a);
+  });
 }
 
 // ---- MVDR beamforming: psd, the per-bin solve, apply (csrc/beamform.h) ---------------------------------------------------
@@ -335,8 +327,7 @@ int aamd_beamform_psd(int32_t dtype, const void* x, int64_t batch, int64_t chann
   DeviceScope dev_scope_(x);
   AAMD_CHECK_ARG(dtype == AAMD_BF_C64 || dtype == AAMD_BF_C128, "beamform: unknown element type");
   bf::PsdArgs a{};
-  int rc = bf_view(a.x, x, batch, channels, freq, time, stride_b, stride_c, stride_f, stride_t, a.fmajor);
-  if (rc != AAMD_OK) return rc;
+  AAMD_TRY(bf_view(a.x, x, batch, channels, freq, time, stride_b, stride_c, stride_f, stride_t, a.fmajor));
   AAMD_CHECK_ARG(mask1 || !mask2, "psd: a second mask needs a first one");
   AAMD_CHECK_ARG((!mask1 || mask1_strides) && (!mask2 || mask2_strides), "psd: a mask needs its strides");
   if (batch * freq == 0) return AAMD_OK;
@@ -391,8 +382,7 @@ int aamd_beamform_apply(int32_t dtype, const void* w, const void* x, int64_t bat
   DeviceScope dev_scope_(x);
   AAMD_CHECK_ARG(dtype == AAMD_BF_C64 || dtype == AAMD_BF_C128, "beamform: unknown element type");
   bf::ApplyArgs a{};
-  int rc = bf_view(a.x, x, batch, channels, freq, time, stride_b, stride_c, stride_f, stride_t, a.fmajor);
-  if (rc != AAMD_OK) return rc;
+  AAMD_TRY(bf_view(a.x, x, batch, channels, freq, time, stride_b, stride_c, stride_f, stride_t, a.fmajor));
   if (batch * freq * time == 0) return AAMD_OK;
   AAMD_CHECK_ARG(w && x && out && out_strides, "null buffer");
   AAMD_CHECK_ARG(out_strides[0] >= 0 && out_strides[1] >= 1 && out_strides[2] >= 1, "apply_beamforming: bad output strides");

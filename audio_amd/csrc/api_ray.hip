@@ -18,8 +18,7 @@ int launch_trace(const ray::Args& a, int64_t blocks, hipStream_t s) {
 template <int DT>
 int launch_both(ray::Args a, hipStream_t s) {
   a.blocks_per_room = (a.N + ray::kThreads - 1) / ray::kThreads;
-  const int rc = a.D == 2 ? launch_trace<DT, 2>(a, a.B * a.blocks_per_room, s) : launch_trace<DT, 3>(a, a.B * a.blocks_per_room, s);
-  if (rc != AAMD_OK) return rc;
+  AAMD_TRY(a.D == 2 ? launch_trace<DT, 2>(a, a.B * a.blocks_per_room, s) : launch_trace<DT, 3>(a, a.B * a.blocks_per_room, s));
   a.blocks_per_room = ((int64_t)a.M * a.NB * a.bins + ray::kThreads - 1) / ray::kThreads;
   return launch(ray::convert_kernel<DT>, a.B * a.blocks_per_room, ray::kThreads, 0, s, a);
 }
@@ -66,7 +65,7 @@ int aamd_ray_trace(int32_t dtype, const void* room, const void* source, const vo
   AAMD_CHECK_ARG(batch < (1ll << 31) / ((num_rays + ray::kThreads - 1) / ray::kThreads) &&
                      batch < (1ll << 31) / ((per_room + ray::kThreads - 1) / ray::kThreads), "ray_trace: too many workgroups");
   AAMD_CHECK_ARG(room && source && mic && absorption && scattering && acc && out, "null buffer");
-  const uintptr_t el = dtype == AAMD_SA_F64 ? 7 : 3;
+  const uintptr_t el = (uintptr_t)(elem_size(dtype) - 1);
   AAMD_CHECK_ARG((((uintptr_t)room | (uintptr_t)source | (uintptr_t)mic | (uintptr_t)absorption | (uintptr_t)scattering |
                    (uintptr_t)out) & el) == 0 && ((uintptr_t)acc & 7) == 0, "ray_trace: a buffer is misaligned");
   ray::Args a{};

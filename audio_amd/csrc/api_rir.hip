@@ -32,7 +32,7 @@ int aamd_simulate_rir(int32_t dtype, const void* room, const void* source, const
   AAMD_CHECK_ARG(batch < (1ll << 31) && mics < (1ll << 31) && batch * mics < (1ll << 31) && batch * mics * tiles < (1ll << 31),
                  "simulate_rir: too many workgroups");
   AAMD_CHECK_ARG(room && source && mic && absorption && lattice && out, "null buffer");
-  const uintptr_t el = dtype == AAMD_SA_F64 ? 7 : 3;
+  const uintptr_t el = (uintptr_t)(elem_size(dtype) - 1);
   AAMD_CHECK_ARG((((uintptr_t)room | (uintptr_t)source | (uintptr_t)mic | (uintptr_t)absorption | (uintptr_t)out) & el) == 0 &&
                      ((uintptr_t)lattice & 1) == 0, "simulate_rir: a buffer is misaligned");
   rir::Args a{};

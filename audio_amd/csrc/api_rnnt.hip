@@ -6,8 +6,6 @@ using namespace aamd;
 
 namespace {
 
-int elem_bytes(int32_t dtype) { return dtype == AAMD_SA_F64 ? 8 : (dtype == AAMD_SA_F32 ? 4 : 2); }
-
 int rnnt_args(rnnt::Args& a, int32_t dtype, const void* logits, const int32_t* targets, const int32_t* logit_lengths,
               const int32_t* target_lengths, int64_t batch, int64_t max_t, int64_t max_u1, int64_t vocab, int32_t blank,
               int32_t fused, const void* workspace) {
@@ -20,7 +18,7 @@ int rnnt_args(rnnt::Args& a, int32_t dtype, const void* logits, const int32_t* t
   if (batch == 0) return AAMD_OK;
   AAMD_CHECK_ARG(logits && logit_lengths && target_lengths && workspace && (targets || max_u1 == 1), "null buffer");
   AAMD_CHECK_ARG(((uintptr_t)workspace & 7) == 0, "rnnt_loss: workspace must be 8-byte aligned");
-  AAMD_CHECK_ARG(((uintptr_t)logits & (uintptr_t)(elem_bytes(dtype) - 1)) == 0, "rnnt_loss: logits is not aligned to its element");
+  AAMD_CHECK_ARG(((uintptr_t)logits & (uintptr_t)(elem_size(dtype) - 1)) == 0, "rnnt_loss: logits is not aligned to its element");
   a.logits = logits; a.targets = targets; a.logit_lengths = logit_lengths; a.target_lengths = target_lengths;
   a.B = batch; a.T = max_t; a.U1 = max_u1; a.V = vocab; a.blank = blank; a.fused = fused ? 1 : 0;
   rnnt::ws_bind(a, const_cast<void*>(workspace));
@@ -45,12 +43,7 @@ int team_launch_w(const rnnt::Args& a, hipStream_t s) {
 }
 template <int KIND>
 int team_launch_dt(int32_t dtype, const rnnt::Args& a, hipStream_t s) {
-  switch (dtype) {
-    case AAMD_SA_F32: return team_launch_w<KIND, wa::kF32>(a, s);
-    case AAMD_SA_F64: return team_launch_w<KIND, wa::kF64>(a, s);
-    case AAMD_SA_F16: return team_launch_w<KIND, wa::kF16>(a, s);
-    default: return team_launch_w<KIND, wa::kBF16>(a, s);
-  }
+  return for_dtype(dtype, [&](auto dt) { return team_launch_w<KIND, dt.value>(a, s); });
 }
 
 // KIND 0: gather_kernel (forward, not fused), 1: grad_sparse_kernel (backward, not fused): one thread per cell
@@ -59,23 +52,17 @@ int cell_launch(int32_t dtype, const rnnt::Args& a, hipStream_t s) {
   const int64_t n = rnnt::cells(a.B, a.T, a.U1);
   int64_t blocks = (n + rnnt::kThreads - 1) / rnnt::kThreads;
   if (blocks > (1 << 22)) blocks = 1 << 22;
-#define AAMD_RNNT_CELL(DT) \
-  return KIND == 0 ? launch(rnnt::gather_kernel<DT>, blocks, rnnt::kThreads, 0, s, a) \
-                   : launch(rnnt::grad_sparse_kernel<DT>, blocks, rnnt::kThreads, 0, s, a)
-  switch (dtype) {
-    case AAMD_SA_F32: AAMD_RNNT_CELL(wa::kF32);
-    case AAMD_SA_F64: AAMD_RNNT_CELL(wa::kF64);
-    case AAMD_SA_F16: AAMD_RNNT_CELL(wa::kF16);
-    default: AAMD_RNNT_CELL(wa::kBF16);
-  }
-#undef AAMD_RNNT_CELL
+  return for_dtype(dtype, [&](auto dt) {
+    return KIND == 0 ? launch(rnnt::gather_kernel<dt.value>, blocks, rnnt::kThreads, 0, s, a)
+                     : launch(rnnt::grad_sparse_kernel<dt.value>, blocks, rnnt::kThreads, 0, s, a);
+  });
 }
 
 }  // namespace
 
 extern "C" {
 
-int32_t aamd_rnnt_team_width(int32_t dtype, int64_t vocab) { return rnnt::team_width(elem_bytes(dtype), vocab); }
+int32_t aamd_rnnt_team_width(int32_t dtype, int64_t vocab) { return rnnt::team_width(elem_size(dtype), vocab); }
 int32_t aamd_rnnt_lattice_threads(void) { return rnnt::kLatThreads; }
 
 int64_t aamd_rnnt_loss_workspace(int64_t batch, int64_t max_t, int64_t max_u1) {
@@ -96,8 +83,7 @@ int aamd_rnnt_loss_forward(int32_t dtype, const void* logits, const int32_t* tar
   AAMD_CHECK_ARG(2 * batch < (1ll << 31), "rnnt_loss: too many examples for one launch");
   a.costs = costs;
   hipStream_t s = (hipStream_t)stream;
-  rc = a.fused ? team_launch_dt<0>(dtype, a, s) : cell_launch<0>(dtype, a, s);
-  if (rc != AAMD_OK) return rc;
+  AAMD_TRY(a.fused ? team_launch_dt<0>(dtype, a, s) : cell_launch<0>(dtype, a, s));
   switch (rnnt::lat_ku(max_u1)) {
     case 1: return launch(rnnt::lattice_kernel<1>, 2 * batch, rnnt::kLatThreads, 0, s, a);
     case 2: return launch(rnnt::lattice_kernel<2>, 2 * batch, rnnt::kLatThreads, 0, s, a);
@@ -115,7 +101,7 @@ int aamd_rnnt_loss_backward(int32_t dtype, const void* logits, const int32_t* ta
                      fused_log_softmax, workspace);
   if (rc != AAMD_OK || batch == 0) return rc;
   AAMD_CHECK_ARG(grad_costs && grad, "null buffer");
-  AAMD_CHECK_ARG(((uintptr_t)grad & (uintptr_t)(elem_bytes(dtype) - 1)) == 0, "rnnt_loss: grad is not aligned to its element");
+  AAMD_CHECK_ARG(((uintptr_t)grad & (uintptr_t)(elem_size(dtype) - 1)) == 0, "rnnt_loss: grad is not aligned to its element");
   a.grad_costs = grad_costs; a.grad = grad; a.clamp = clamp;
   hipStream_t s = (hipStream_t)stream;
   rc = team_launch_dt<1>(dtype, a, s);

@@ -41,13 +41,13 @@ int common(const char* who, sdr::Args& a, int32_t dtype, int32_t mode, const voi
   AAMD_CHECK_ARG(rows < (1ll << 31) && length < (1ll << 40), w + ": too many rows or samples");
   AAMD_CHECK_ARG(rows <= 1 || (preds_stride >= length && target_stride >= length), w + ": rows overlap");
   AAMD_CHECK_ARG((preds && target) || length == 0 || rows == 0, w + ": null buffer");
-  const uintptr_t emask = (uintptr_t)((dtype == AAMD_SA_F64 ? 8 : (dtype == AAMD_SA_F32 ? 4 : 2)) - 1);
-  AAMD_CHECK_ARG((((uintptr_t)preds | (uintptr_t)target) & emask) == 0, w + ": a waveform is not aligned to its element");
+  AAMD_CHECK_ARG((((uintptr_t)preds | (uintptr_t)target) & (uintptr_t)(elem_size(dtype) - 1)) == 0,
+                 w + ": a waveform is not aligned to its element");
   AAMD_CHECK_ARG(((uintptr_t)lengths & (lengths_int64 ? 7 : 3)) == 0, w + ": lengths is misaligned");
   a.p = preds; a.t = target; a.lengths = lengths;
   a.rows = rows; a.T = length; a.sp = rows > 1 ? preds_stride : 0; a.st = rows > 1 ? target_stride : 0;
   a.len64 = lengths_int64 ? 1 : 0; a.zero_mean = zero_mean ? 1 : 0; a.mode = mode;
-  a.eps = dtype == AAMD_SA_F64 ? 2.220446049250313e-16 : 1.1920928955078125e-07;
+  a.eps = comp_eps(dtype);
   a.chunks = length > 0 ? sdr::ceil_div(length, sdr::kChunk) : 1;
   a.spans = length > 0 ? sdr::ceil_div(length, sdr::kSpan) : 1;
   AAMD_CHECK_ARG(rows * a.chunks < (1ll << 31), w + ": too many workgroups");
@@ -56,24 +56,19 @@ int common(const char* who, sdr::Args& a, int32_t dtype, int32_t mode, const voi
 
 template <int DT>
 int run_sdr(const sdr::Args& a, hipStream_t s) {
-  int rc = launch(sdr::moments_kernel<DT>, a.rows * a.chunks, sdr::kThreads, 0, s, a);
-  if (rc != AAMD_OK) return rc;
+  AAMD_TRY(launch(sdr::moments_kernel<DT>, a.rows * a.chunks, sdr::kThreads, 0, s, a));
   if (a.flen <= sdr::kLagsSmall) {
-    rc = launch(sdr::corr_kernel<DT, sdr::kTilesSmall>, a.rows * a.spans, sdr::kThreads, 0, s, a);
-    if (rc != AAMD_OK) return rc;
+    AAMD_TRY(launch(sdr::corr_kernel<DT, sdr::kTilesSmall>, a.rows * a.spans, sdr::kThreads, 0, s, a));
     return launch(sdr::solve_kernel<DT, 1>, a.rows, sdr::kSolveThreads, 0, s, a);
   }
-  rc = launch(sdr::corr_kernel<DT, sdr::kTilesMax>, a.rows * a.spans, sdr::kThreads, 0, s, a);
-  if (rc != AAMD_OK) return rc;
+  AAMD_TRY(launch(sdr::corr_kernel<DT, sdr::kTilesMax>, a.rows * a.spans, sdr::kThreads, 0, s, a));
   return launch(sdr::solve_kernel<DT, sdr::kLagsMax / 64>, a.rows, sdr::kSolveThreads, 0, s, a);
 }
 
 template <int DT>
 int run_si(const sdr::Args& a, hipStream_t s) {
-  int rc = launch(sdr::moments_kernel<DT>, a.rows * a.chunks, sdr::kThreads, 0, s, a);
-  if (rc != AAMD_OK) return rc;
-  rc = launch(sdr::residual_kernel<DT>, a.rows * a.chunks, sdr::kThreads, 0, s, a);
-  if (rc != AAMD_OK) return rc;
+  AAMD_TRY(launch(sdr::moments_kernel<DT>, a.rows * a.chunks, sdr::kThreads, 0, s, a));
+  AAMD_TRY(launch(sdr::residual_kernel<DT>, a.rows * a.chunks, sdr::kThreads, 0, s, a));
   return launch(sdr::finish_kernel<DT>, a.rows, sdr::kSolveThreads, 0, s, a);
 }
 
@@ -81,14 +76,6 @@ template <int DT>
 int run_grad(const sdr::Args& a, hipStream_t s) {
   return launch(sdr::grad_kernel<DT>, a.rows * a.chunks, sdr::kThreads, 0, s, a);
 }
-
-#define AAMD_SDR_DISPATCH(fn, dtype, a, s)                      \
-  switch (dtype) {                                              \
-    case AAMD_SA_F32: return fn<wa::kF32>(a, s);                \
-    case AAMD_SA_F64: return fn<wa::kF64>(a, s);                \
-    case AAMD_SA_F16: return fn<wa::kF16>(a, s);                \
-    default: return fn<wa::kBF16>(a, s);                        \
-  }
 
 }  // namespace
 
@@ -116,15 +103,14 @@ int aamd_sdr(int32_t dtype, const void* preds, const void* target, int64_t rows,
              int32_t has_load_diag, double load_diag, void* workspace, void* out, void* stream) {
   DeviceScope dev_scope_(out);
   sdr::Args a{};
-  int rc = common("sdr", a, dtype, sdr::kModeSdr, preds, target, rows, length, preds_stride, target_stride, lengths,
-                  lengths_int64, zero_mean);
-  if (rc != AAMD_OK) return rc;
+  AAMD_TRY(common("sdr", a, dtype, sdr::kModeSdr, preds, target, rows, length, preds_stride, target_stride, lengths,
+                  lengths_int64, zero_mean));
   AAMD_CHECK_ARG(filter_length >= 1, "sdr: filter_length must be at least 1");
   if (filter_length > sdr::kLagsMax)
     return fail(AAMD_EUNSUPPORTED, "audio_amd: sdr: filter_length above " + std::to_string(sdr::kLagsMax) + " is not implemented");
   if (rows == 0) return AAMD_OK;
   AAMD_CHECK_ARG(workspace && out, "sdr: null buffer");
-  AAMD_CHECK_ARG(((uintptr_t)workspace & 7) == 0 && ((uintptr_t)out & (dtype == AAMD_SA_F64 ? 7 : 3)) == 0, "sdr: a buffer is misaligned");
+  AAMD_CHECK_ARG(((uintptr_t)workspace & 7) == 0 && ((uintptr_t)out & (uintptr_t)(comp_size(dtype) - 1)) == 0, "sdr: a buffer is misaligned");
   const Layout l = layout_of(sdr::kModeSdr, rows, length, filter_length);
   AAMD_CHECK_ARG(rows * l.spans < (1ll << 31), "sdr: too many workgroups");
   char* ws = static_cast<char*>(workspace);
@@ -133,8 +119,7 @@ int aamd_sdr(int32_t dtype, const void* preds, const void* target, int64_t rows,
   a.mom = reinterpret_cast<double*>(ws + l.mom);
   a.corr = reinterpret_cast<double*>(ws + l.tail);
   a.out = out;
-  hipStream_t s = (hipStream_t)stream;
-  AAMD_SDR_DISPATCH(run_sdr, dtype, a, s)
+  return for_dtype(dtype, [&](auto dt) { return run_sdr<dt.value>(a, (hipStream_t)stream); });
 }
 
 int aamd_si_sdr(int32_t dtype, int32_t mode, const void* preds, const void* target, int64_t rows, int64_t length,
@@ -142,13 +127,12 @@ int aamd_si_sdr(int32_t dtype, int32_t mode, const void* preds, const void* targ
                 void* workspace, double* stat, void* out, void* stream) {
   DeviceScope dev_scope_(out);
   sdr::Args a{};
-  int rc = common("si_sdr", a, dtype, mode, preds, target, rows, length, preds_stride, target_stride, lengths, lengths_int64,
-                  zero_mean);
-  if (rc != AAMD_OK) return rc;
+  AAMD_TRY(common("si_sdr", a, dtype, mode, preds, target, rows, length, preds_stride, target_stride, lengths, lengths_int64,
+                  zero_mean));
   AAMD_CHECK_ARG(mode != sdr::kModeSdr, "si_sdr: mode must be 1 (SI-SDR) or 2 (SNR)");
   if (rows == 0) return AAMD_OK;
   AAMD_CHECK_ARG(workspace && out && stat, "si_sdr: null buffer");
-  AAMD_CHECK_ARG((((uintptr_t)workspace | (uintptr_t)stat) & 7) == 0 && ((uintptr_t)out & (dtype == AAMD_SA_F64 ? 7 : 3)) == 0,
+  AAMD_CHECK_ARG((((uintptr_t)workspace | (uintptr_t)stat) & 7) == 0 && ((uintptr_t)out & (uintptr_t)(comp_size(dtype) - 1)) == 0,
                  "si_sdr: a buffer is misaligned");
   const Layout l = layout_of(mode, rows, length, 1);
   char* ws = static_cast<char*>(workspace);
@@ -156,8 +140,7 @@ int aamd_si_sdr(int32_t dtype, int32_t mode, const void* preds, const void* targ
   a.res = reinterpret_cast<double*>(ws + l.tail);
   a.stat = stat;
   a.out = out;
-  hipStream_t s = (hipStream_t)stream;
-  AAMD_SDR_DISPATCH(run_si, dtype, a, s)
+  return for_dtype(dtype, [&](auto dt) { return run_si<dt.value>(a, (hipStream_t)stream); });
 }
 
 int aamd_si_sdr_grad(int32_t dtype, int32_t mode, const void* preds, const void* target, int64_t rows, int64_t length,
@@ -165,21 +148,19 @@ int aamd_si_sdr_grad(int32_t dtype, int32_t mode, const void* preds, const void*
                      const double* stat, const double* cotangent, void* grad_preds, void* grad_target, void* stream) {
   DeviceScope dev_scope_(stat);
   sdr::Args a{};
-  int rc = common("si_sdr_grad", a, dtype, mode, preds, target, rows, length, preds_stride, target_stride, lengths,
-                  lengths_int64, 0);
-  if (rc != AAMD_OK) return rc;
+  AAMD_TRY(common("si_sdr_grad", a, dtype, mode, preds, target, rows, length, preds_stride, target_stride, lengths,
+                  lengths_int64, 0));
   AAMD_CHECK_ARG(mode != sdr::kModeSdr, "si_sdr_grad: mode must be 1 (SI-SDR) or 2 (SNR)");
   if (rows == 0 || length == 0 || (!grad_preds && !grad_target)) return AAMD_OK;
   AAMD_CHECK_ARG(stat && cotangent, "si_sdr_grad: null buffer");
-  const uintptr_t emask = (uintptr_t)((dtype == AAMD_SA_F64 ? 8 : (dtype == AAMD_SA_F32 ? 4 : 2)) - 1);
-  AAMD_CHECK_ARG((((uintptr_t)stat | (uintptr_t)cotangent) & 7) == 0 && (((uintptr_t)grad_preds | (uintptr_t)grad_target) & emask) == 0,
+  AAMD_CHECK_ARG((((uintptr_t)stat | (uintptr_t)cotangent) & 7) == 0 &&
+                     (((uintptr_t)grad_preds | (uintptr_t)grad_target) & (uintptr_t)(elem_size(dtype) - 1)) == 0,
                  "si_sdr_grad: a buffer is misaligned");
   a.stat = const_cast<double*>(stat);
   a.cot = cotangent;
   a.gp = grad_preds; a.gt = grad_target;
   a.want_p = grad_preds ? 1 : 0; a.want_t = grad_target ? 1 : 0;
-  hipStream_t s = (hipStream_t)stream;
-  AAMD_SDR_DISPATCH(run_grad, dtype, a, s)
+  return for_dtype(dtype, [&](auto dt) { return run_grad<dt.value>(a, (hipStream_t)stream); });
 }
 
 }  // extern "C"

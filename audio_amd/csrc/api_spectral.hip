@@ -37,19 +37,14 @@ int aamd_spectral_centroid(int32_t out_dtype, const float* mag, const float* fre
   if (rows == 0 || frames == 0) return AAMD_OK;
   AAMD_CHECK_ARG(mag && freqs && out, "null buffer");
   AAMD_CHECK_ARG(((uintptr_t)mag & 3) == 0 && ((uintptr_t)freqs & 15) == 0, "spectral_centroid: a float buffer is misaligned");
-  AAMD_CHECK_ARG(((uintptr_t)out & (uintptr_t)(out_dtype == AAMD_SA_F32 ? 3 : 1)) == 0, "spectral_centroid: the result is misaligned");
+  AAMD_CHECK_ARG(((uintptr_t)out & (uintptr_t)(elem_size(out_dtype) - 1)) == 0, "spectral_centroid: the result is misaligned");
   sf::CentArgs a{};
   a.m = mag; a.freqs = freqs; a.out = out; a.rows = rows; a.frames = frames; a.n_freq = n_freq;
   a.sr = stride_row; a.st = stride_frame; a.sk = stride_freq;
   const bool lines = stride_freq == 1 || n_freq == 1;
   a.lanes = lines ? sf::lanes_for(n_freq) : 1;
   AAMD_CHECK_ARG(rows * frames / (sf::kThreads / a.lanes) < (1ll << 31) - 1, "spectral_centroid: too many workgroups");
-  hipStream_t s = (hipStream_t)stream;
-  switch (out_dtype) {
-    case AAMD_SA_F32: return centroid_launch<wa::kF32>(a, lines, s);
-    case AAMD_SA_F16: return centroid_launch<wa::kF16>(a, lines, s);
-    default: return centroid_launch<wa::kBF16>(a, lines, s);
-  }
+  return for_dtype<kNoF64>(out_dtype, [&](auto dt) { return centroid_launch<dt.value>(a, lines, (hipStream_t)stream); });
 }
 
 }  // extern "C"

@@ -19,11 +19,10 @@ Layout layout_of(int32_t dtype, int64_t rows, int64_t T) {
   l.M_max = l.K_max > 0 ? l.K_max - 1 : 0;
   l.nb_e = l.K_max > 0 ? stoi::ceil_div(l.K_max, stoi::kEnergyFrames) : 1;
   l.nt_seg = l.M_max >= stoi::kSeg ? stoi::ceil_div(l.M_max - stoi::kSeg + 1, stoi::kSegTile) : 0;
-  const int64_t csize = dtype == AAMD_SA_F64 ? 8 : 4;
   l.e = 0;
   l.part = l.e + rows * l.K_max * 8;
   l.tob = l.part + rows * l.nt_seg * 8;
-  l.kept = l.tob + up8(rows * 2 * l.M_max * stoi::kBands * csize);
+  l.kept = l.tob + up8(rows * 2 * l.M_max * stoi::kBands * comp_size(dtype));
   l.bad = l.kept + up8(rows * l.K_max * 4);
   l.n_kept = l.bad + up8(rows * l.nb_e * 4);
   l.total = l.n_kept + up8(rows * 4);
@@ -33,15 +32,11 @@ Layout layout_of(int32_t dtype, int64_t rows, int64_t T) {
 template <int DT>
 int run(const stoi::Args& a, hipStream_t s) {
   using C = typename stoi::Elem<DT>::C;
-  int rc = launch(stoi::energy_kernel<DT>, a.rows * a.nb_e, stoi::kThreads, 0, s, a);
-  if (rc != AAMD_OK) return rc;
-  rc = launch(stoi::select_kernel, a.rows, stoi::kThreads, 0, s, a);
-  if (rc != AAMD_OK) return rc;
+  AAMD_TRY(launch(stoi::energy_kernel<DT>, a.rows * a.nb_e, stoi::kThreads, 0, s, a));
+  AAMD_TRY(launch(stoi::select_kernel, a.rows, stoi::kThreads, 0, s, a));
   if (a.nt_seg > 0) {
-    rc = launch(stoi::tob_kernel<DT>, a.rows * stoi::ceil_div(a.M_max, stoi::kTobFrames), stoi::kThreads, stoi::tob_lds_bytes<C>(), s, a);
-    if (rc != AAMD_OK) return rc;
-    rc = launch(stoi::segment_kernel<C>, a.rows * a.nt_seg, stoi::kThreads, 0, s, a);
-    if (rc != AAMD_OK) return rc;
+    AAMD_TRY(launch(stoi::tob_kernel<DT>, a.rows * stoi::ceil_div(a.M_max, stoi::kTobFrames), stoi::kThreads, stoi::tob_lds_bytes<C>(), s, a));
+    AAMD_TRY(launch(stoi::segment_kernel<C>, a.rows * a.nt_seg, stoi::kThreads, 0, s, a));
   }
   return launch(stoi::finish_kernel<C>, a.rows, stoi::kFinishThreads, 0, s, a);
 }
@@ -79,9 +74,9 @@ int aamd_stoi(int32_t dtype, const void* preds, const void* target, int64_t rows
   AAMD_CHECK_ARG(rows * l.nb_e < (1ll << 31) && rows * stoi::ceil_div(l.M_max, stoi::kTobFrames) < (1ll << 31),
                  "stoi: too many workgroups");
   AAMD_CHECK_ARG(workspace && out && ((preds && target) || length == 0), "null buffer");
-  const uintptr_t emask = (uintptr_t)((dtype == AAMD_SA_F64 ? 8 : (dtype == AAMD_SA_F32 ? 4 : 2)) - 1);
-  AAMD_CHECK_ARG((((uintptr_t)preds | (uintptr_t)target) & emask) == 0, "stoi: a waveform is not aligned to its element");
-  AAMD_CHECK_ARG(((uintptr_t)workspace & 7) == 0 && ((uintptr_t)out & (dtype == AAMD_SA_F64 ? 7 : 3)) == 0 &&
+  AAMD_CHECK_ARG((((uintptr_t)preds | (uintptr_t)target) & (uintptr_t)(elem_size(dtype) - 1)) == 0,
+                 "stoi: a waveform is not aligned to its element");
+  AAMD_CHECK_ARG(((uintptr_t)workspace & 7) == 0 && ((uintptr_t)out & (uintptr_t)(comp_size(dtype) - 1)) == 0 &&
                      ((uintptr_t)lengths & (lengths_int64 ? 7 : 3)) == 0,
                  "stoi: a buffer is misaligned");
   char* ws = static_cast<char*>(workspace);
@@ -97,13 +92,7 @@ int aamd_stoi(int32_t dtype, const void* preds, const void* target, int64_t rows
   a.bad = reinterpret_cast<int32_t*>(ws + l.bad);
   a.n_kept = reinterpret_cast<int32_t*>(ws + l.n_kept);
   a.out = out;
-  hipStream_t s = (hipStream_t)stream;
-  switch (dtype) {
-    case AAMD_SA_F32: return run<wa::kF32>(a, s);
-    case AAMD_SA_F64: return run<wa::kF64>(a, s);
-    case AAMD_SA_F16: return run<wa::kF16>(a, s);
-    default: return run<wa::kBF16>(a, s);
-  }
+  return for_dtype(dtype, [&](auto dt) { return run<dt.value>(a, (hipStream_t)stream); });
 }
 
 }  // extern "C"

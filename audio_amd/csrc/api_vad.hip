@@ -7,16 +7,12 @@ using namespace aamd;
 
 namespace {
 
-int elem_size(int32_t dtype) { return dtype == AAMD_SA_F64 ? 8 : (dtype == AAMD_SA_F32 ? 4 : 2); }
-
 template <int DT>
 int measure_launch(const vad::MeasArgs& a, hipStream_t s) {
   const int64_t items = a.rows * a.frames;
-  int rc = launch(vad::spec_kernel<DT>, items, vad::kThreads, vad::lds_bytes(a.N), s, a);
-  if (rc != AAMD_OK) return rc;
+  AAMD_TRY(launch(vad::spec_kernel<DT>, items, vad::kThreads, vad::lds_bytes(a.N), s, a));
   const int64_t lanes = a.rows * (a.s1 - a.s0);
-  rc = launch(vad::smooth_kernel, (lanes + vad::kThreads - 1) / vad::kThreads, vad::kThreads, 0, s, a);
-  if (rc != AAMD_OK) return rc;
+  AAMD_TRY(launch(vad::smooth_kernel, (lanes + vad::kThreads - 1) / vad::kThreads, vad::kThreads, 0, s, a));
   return launch(vad::ceps_kernel, items, vad::kThreads, vad::lds_bytes(a.N >> 1), s, a);
 }
 
@@ -64,13 +60,7 @@ int aamd_vad_measure(int32_t dtype, const void* x, int64_t rows, int64_t length,
   a.P = period; a.s0 = s0; a.s1 = s1; a.c0 = c0; a.c1 = c1; a.boot_max = boot_max;
   if (vad::lds_bytes(n_fft) > 48 * 1024 && vad::lds_bytes(n_fft) > dev_props().lds_per_block_optin)
     return fail(AAMD_EUNSUPPORTED, "audio_amd: vad: this device has less LDS than the transform was planned for");
-  hipStream_t s = (hipStream_t)stream;
-  switch (dtype) {
-    case AAMD_SA_F32: return measure_launch<wa::kF32>(a, s);
-    case AAMD_SA_F64: return measure_launch<wa::kF64>(a, s);
-    case AAMD_SA_F16: return measure_launch<wa::kF16>(a, s);
-    default: return measure_launch<wa::kBF16>(a, s);
-  }
+  return for_dtype(dtype, [&](auto dt) { return measure_launch<dt.value>(a, (hipStream_t)stream); });
 }
 
 int aamd_vad_trigger(const float* meas, int64_t rows, int64_t frames, int64_t ring, int64_t gap, int64_t period, int64_t fixed,
@@ -87,10 +77,7 @@ int aamd_vad_trigger(const float* meas, int64_t rows, int64_t frames, int64_t ri
   a.meas = meas; a.rows = rows; a.frames = frames; a.M = ring; a.gap = gap; a.P = period; a.fixed = fixed;
   a.level = trigger_level; a.trig = trigger_mult; a.first = first; a.start = start; a.joint = joint;
   hipStream_t s = (hipStream_t)stream;
-  if (rows > 0) {
-    const int rc = launch(vad::trigger_kernel, (rows + vad::kTrigThreads - 1) / vad::kTrigThreads, vad::kTrigThreads, 0, s, a);
-    if (rc != AAMD_OK) return rc;
-  }
+  if (rows > 0) AAMD_TRY(launch(vad::trigger_kernel, (rows + vad::kTrigThreads - 1) / vad::kTrigThreads, vad::kTrigThreads, 0, s, a));
   return joint ? launch(vad::joint_kernel, 1, vad::kThreads, 0, s, a) : AAMD_OK;
 }
 

@@ -163,6 +163,29 @@ def test_gradient_against_float64_autograd(S, dtype):
         g.sum().backward()
 
 
+@pytest.mark.parametrize("half", [torch.float16, torch.bfloat16], ids=["f16", "bf16"])
+def test_gradient_of_the_half_types(half):
+    """float16 / bfloat16 gradients come back in the input's type, rounded once.  The reference is float64 autograd on the
+    widened inputs (float32's eps: the half types compute as float32 does); the bar is 4 x the distance of that reference from
+    its own rounding to the type -- the margin float32 gets over float32 autograd."""
+    S, T = 2, F.pit_tiles()[1] + 1
+    p, t, planted = batch(S, T)
+    ph, th, idx = dev(p).to(half), dev(t).to(half), torch.arange(3, device=DEV)[:, None]
+    w, inv = -torch.ones(3, S, device=DEV, dtype=torch.float64) / S, dev(np.argsort(planted, axis=1), torch.int64)
+    for name, (fn, kw) in FUSED.items():
+        gp64, gl64 = autograd(name, ph.double(), th[idx, dev(planted, torch.int64)].double(), w, float(np.finfo(np.float32).eps))
+        refs = (gp64, gl64[idx, inv])                                       # back to the references' own order
+        own = max(rel(r.to(half), r) for r in refs)
+        pg, tg = ph.clone().requires_grad_(), th.clone().requires_grad_()
+        best, perm = F.permutation_invariant_training(pg, tg, fn, **kw)
+        assert perm.cpu().numpy().tolist() == planted.tolist(), name
+        (-best.sum()).backward()
+        assert pg.grad.dtype == half and tg.grad.dtype == half
+        worst = max(rel(pg.grad, refs[0]), rel(tg.grad, refs[1]))
+        print(f"{name} {half} gradients: worst {worst:.3e}, the reference's own rounding {own:.3e}, bar {4 * own:.3e}")
+        assert 0 < own and worst <= 4 * own
+
+
 @pytest.mark.parametrize("name", ["si_sdr", "si_snr", "snr_zm"])
 def test_bit_for_bit(name):
     (fn, kw), S, span = FUSED[name], 3, F.pit_tiles()[1]

@@ -82,6 +82,17 @@ def test_sdr_against_the_longdouble_oracle(case):
     assert worst <= bar
 
 
+@pytest.mark.parametrize("half", [torch.float16, torch.bfloat16], ids=["f16", "bf16"])
+def test_sdr_half_types_equal_the_call_on_the_widened_tensor(half):
+    """float16 / bfloat16 are widened on load and every sum is float64: the bits of the float32 call on the widened tensor, one
+    sample past a span, at a filter length of either class of the correlation kernel."""
+    p, t = signals(F.sdr_tiles()[3] + 1)
+    ph, th = dev(p).to(half), dev(t).to(half)
+    for fl in (17, 65):
+        got = F.signal_distortion_ratio(ph, th, filter_length=fl)
+        assert got.isfinite().all() and same_bits(got, F.signal_distortion_ratio(ph.float(), th.float(), filter_length=fl))
+
+
 def si_times():
     chunk = F.sdr_tiles()[1]
     return [1, 3, chunk - 1, chunk + 1, 3 * chunk + 5]
@@ -120,18 +131,17 @@ def test_si_family_against_the_definition(name, dtype):
     assert worst <= bar
 
 
-def torch_expr(name, p, t):
+def torch_expr(name, p, t, eps=torch.finfo(torch.float32).eps):
     if name.endswith("_zm") or name == "si_snr":
         p, t = p - p.mean(-1, keepdim=True), t - t.mean(-1, keepdim=True)
-    eps = torch.finfo(torch.float32).eps
     if name.startswith("si"):
         t = ((p * t).sum(-1, keepdim=True) + eps) / ((t * t).sum(-1, keepdim=True) + eps) * t
     return 10 * torch.log10(((t * t).sum(-1) + eps) / (((t - p) ** 2).sum(-1) + eps))
 
 
-def autograd(name, p, t, w):
+def autograd(name, p, t, w, eps=torch.finfo(torch.float32).eps):
     p, t = p.clone().requires_grad_(), t.clone().requires_grad_()
-    (torch_expr(name, p, t) * w.to(p.dtype)).sum().backward()
+    (torch_expr(name, p, t, eps) * w.to(p.dtype)).sum().backward()
     return p.grad, t.grad
 
 
@@ -176,6 +186,34 @@ def test_gradients_against_float64_autograd(name):
         pp = p.detach().clone().requires_grad_()
         g, = torch.autograd.grad(SI_FNS[name][0](pp, t.detach()).sum(), pp, create_graph=True)
         g.sum().backward()
+
+
+@pytest.mark.parametrize("name", list(SI_FNS))
+def test_gradients_of_float64_and_half_inputs(name):
+    """One sample past a chunk.  float64 input: against float64 autograd with float64's eps, under float32's bar (the sums are
+    float64 for every dtype).  float16 / bfloat16: the gradients come back in the input's type, rounded once; the reference is
+    float64 autograd on the widened inputs, and the bar 4 x the distance of that reference from its own rounding to the type --
+    the margin float32 gets over float32 autograd."""
+    fn, w, T = SI_FNS[name][0], dev([1.0, -0.5, 2.0]), si_times()[3]
+
+    def device_grads(p, t):
+        p, t = p.clone().requires_grad_(), t.clone().requires_grad_()
+        (fn(p, t) * w).sum().backward()
+        assert p.grad.dtype == p.dtype and t.grad.dtype == t.dtype
+        return p.grad, t.grad
+
+    p, t = (dev(x).double() for x in signals(T))
+    refs = autograd(name, p, t, w, eps=torch.finfo(torch.float64).eps)
+    worst, bar = max(rel(g, g64) for g, g64 in zip(device_grads(p, t), refs)), grad_refs()[1][False]
+    print(f"{name} float64 gradients (of the row's largest element): worst {worst:.3e}, bar {bar:.3e}")
+    assert worst <= bar
+    for half in (torch.float16, torch.bfloat16):
+        ph, th = p.to(half), t.to(half)
+        refs = autograd(name, ph.double(), th.double(), w)
+        own = max(rel(g64.to(half), g64) for g64 in refs)
+        worst = max(rel(g, g64) for g, g64 in zip(device_grads(ph, th), refs))
+        print(f"{name} {half} gradients: worst {worst:.3e}, the reference's own rounding {own:.3e}, bar {4 * own:.3e}")
+        assert 0 < own and worst <= 4 * own
 
 
 BIT_FNS = {"sdr": lambda p, t, **k: F.signal_distortion_ratio(p, t, filter_length=65, zero_mean=True, **k),
