@@ -260,6 +260,13 @@ _SIGS = {
     "aamd_pit_assign": (C.c_int, [C.c_int32, _P, C.c_int64, C.c_int64, C.c_int32, _P, _P, _P]),
     "aamd_pit_grad": (C.c_int, [C.c_int32, C.c_int32, _P, _P] + [C.c_int64] * 7 + [_P, C.c_int32] + [_P] * 6),
     "aamd_pit_permutate": (C.c_int, [C.c_int32, _P, _P] + [C.c_int64] * 5 + [C.c_uint64, _P, _P]),
+    # CTC loss (additions to ABI 7)
+    "aamd_ctc_loss_config": (C.c_int32, [C.c_int32, C.c_int64]),
+    "aamd_ctc_loss_workspace": (C.c_int64, [C.c_int64] * 3),
+    "aamd_ctc_loss_forward": (C.c_int, [C.c_int32, _P, C.c_int64, C.c_int64, _P, C.c_int32, C.c_int64, C.c_int64, _P, _P, C.c_int32]
+                              + [C.c_int64] * 4 + [C.c_int32] * 4 + [_P, _P, _P]),
+    "aamd_ctc_loss_backward": (C.c_int, [C.c_int32, _P, C.c_int64, C.c_int64, _P, C.c_int32, C.c_int64, C.c_int64, _P, _P, C.c_int32]
+                               + [C.c_int64] * 4 + [C.c_int32] * 4 + [_P, _P, C.c_int64, _P, C.c_int64, C.c_int64, _P]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS)

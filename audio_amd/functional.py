@@ -52,6 +52,7 @@ __all__ = [
     "signal_distortion_ratio", "scale_invariant_signal_distortion_ratio", "scale_invariant_signal_noise_ratio",
     "signal_noise_ratio", "sdr_tiles",
     "permutation_invariant_training", "pit_metric_matrix", "pit_assignment", "pit_permutate", "pit_tiles",
+    "ctc_loss", "ctc_loss_tiles", "CTC_MAX_TARGET",
 ]
 
 # --------------------------------------------------------------------------- #
@@ -5163,6 +5164,166 @@ def merge_tokens(tokens: Tensor, scores: Tensor, blank: int = 0) -> List[TokenSp
     edges = [0] + (np.flatnonzero(tok[1:] != tok[:-1]) + 1).tolist() + [n]
     return [TokenSpan(token=int(tok[s]), start=s, end=e, score=float(sc[s:e].mean()))
             for s, e in zip(edges[:-1], edges[1:]) if tok[s] != blank]
+
+
+# --------------------------------------------------------------------------- #
+# CTC loss (csrc/ctc_loss.h)                                                  #
+# --------------------------------------------------------------------------- #
+CTC_MAX_TARGET = 2047                # AAMD_CTC_MAX_TARGET: the longest target the lattice kernel serves
+_CTC_REDUCTIONS = {"none": 0, "mean": 1, "sum": 2}
+
+
+def ctc_loss_tiles() -> Tuple[Tuple[Tuple[int, int, int], ...], int, Tuple[int, ...], int]:
+    """(((largest S, states per lane, lanes per workgroup) of every lattice configuration, by S), steps the lattice's gathers
+    run ahead, team widths of the row and gradient passes, largest S = CTC_MAX_TARGET) of csrc/ctc_loss.h."""
+    lib = _lib.lib()
+    configs, prev = [], None
+    for S in range(CTC_MAX_TARGET + 1):
+        cur = (int(lib.aamd_ctc_loss_config(0, S)), int(lib.aamd_ctc_loss_config(1, S)))
+        if cur != prev and prev is not None:
+            configs.append((S - 1,) + prev)
+        prev = cur
+    configs.append((CTC_MAX_TARGET,) + prev)
+    widths = tuple(sorted({int(lib.aamd_rnnt_team_width(0, 1 << k)) for k in range(12)}))
+    return tuple(configs), int(lib.aamd_ctc_loss_config(2, 0)), widths, int(lib.aamd_ctc_loss_config(3, 0))
+
+
+def _ctc_prepare(logits: Tensor, targets: Tensor, input_lengths, target_lengths, blank: int, reduction: str,
+                 zero_infinity: bool, fused: bool):
+    """The host-side checks of F.ctc_loss and the batched form of its arguments: (logits (T, N, V), targets, input_lengths,
+    target_lengths, launch parameters, unbatched).  Nothing is read from the device."""
+    if reduction not in _CTC_REDUCTIONS:
+        raise ValueError("reduction should be one of 'none', 'mean', or 'sum'")
+    if logits.dim() not in (2, 3):
+        raise ValueError(f"logits must be 3-D (time, batch, class) or 2-D (time, class), got {tuple(logits.shape)}")
+    unbatched = logits.dim() == 2
+    if targets.dim() not in ((1,) if unbatched else (1, 2)):
+        raise ValueError(f"targets must be {'1-D (label,)' if unbatched else '2-D (batch, label) or 1-D concatenated'}, got "
+                         f"{tuple(targets.shape)}")
+    if logits.dtype not in _RNNT_DTYPES:
+        raise TypeError(f"logits must be float32, float64, float16 or bfloat16 (got {logits.dtype})")
+    if targets.dtype not in _ALIGN_INTS:
+        raise TypeError(f"targets must be int32 or int64 (got {targets.dtype})")
+    listed = []
+    for t, what in ((input_lengths, "input_lengths"), (target_lengths, "target_lengths")):
+        if isinstance(t, Tensor):
+            if t.dtype not in _ALIGN_INTS:
+                raise TypeError(f"{what} must be int32 or int64 (got {t.dtype})")
+            listed.append(None)
+        else:
+            listed.append([int(v) for v in (t if isinstance(t, (tuple, list)) else [t])])
+    if unbatched:
+        logits, targets = logits.unsqueeze(1), targets.unsqueeze(0)
+    T_, N, V = logits.shape
+    if T_ < 1 or V < 1:
+        raise ValueError(f"logits needs at least one frame and one class, got {tuple(logits.shape)}")
+    lens = []
+    for t, vals, what in ((input_lengths, listed[0], "input_lengths"), (target_lengths, listed[1], "target_lengths")):
+        n = len(vals) if vals is not None else (t.numel() if t.dim() <= 1 else -1)
+        if n != N:
+            raise ValueError(f"{what} must hold one length per example ({N}), got "
+                             f"{len(vals) if vals is not None else tuple(t.shape)}")
+        lens.append(t.reshape(N) if vals is None else torch.tensor(vals, dtype=torch.int64, device=logits.device))
+    if targets.dim() == 2 and targets.shape[0] != N:
+        raise ValueError(f"batch sizes differ: logits {N}, targets {targets.shape[0]}")
+    if not 0 <= blank < V:
+        raise ValueError(f"blank must lie in [0, {V}) for {V} classes (got {blank})")
+    total = targets.numel()
+    if targets.dim() == 2:
+        pitch = max_s = targets.shape[1]
+    else:                                                     # concatenated: a bound that needs no read-back
+        pitch = -1
+        max_s = min(total, max(listed[1]) if listed[1] else 0) if listed[1] is not None else min(total, T_)
+    if max_s > CTC_MAX_TARGET:
+        raise NotImplementedError(f"audio_amd: ctc_loss serves targets up to CTC_MAX_TARGET = {CTC_MAX_TARGET} labels (got "
+                                  f"{max_s}): the lattice of one example belongs to one workgroup")
+    for t, what in ((logits, "logits"), (targets, "targets"), (lens[0], "input_lengths"), (lens[1], "target_lengths")):
+        if not t.is_cuda:
+            raise RuntimeError(f"audio_amd: {what} must be on an MI355X (ROCm) device, got {t.device}. "
+                               "The HIP kernels have no CPU fallback.")
+        if t.device != logits.device:
+            raise RuntimeError(f"audio_amd: {what} must be on the logits' device")
+    if lens[0].dtype != lens[1].dtype:
+        lens = [t.to(torch.int64) for t in lens]
+    if V > 1 and logits.stride(2) != 1:                       # any time / batch strides are read in place; classes are gathered once
+        logits = logits.contiguous()
+    cfg = (int(blank), _CTC_REDUCTIONS[reduction], int(bool(zero_infinity)), int(bool(fused)), int(pitch), int(total), int(max_s))
+    return logits, targets.contiguous(), lens[0].contiguous(), lens[1].contiguous(), cfg, unbatched
+
+
+def _ctc_call(fn, logits: Tensor, targets: Tensor, in_len: Tensor, tg_len: Tensor, cfg, ws: Tensor, *tail) -> None:
+    """aamd_ctc_loss_forward / _backward: the arguments the two share, then `tail` and the stream."""
+    blank, reduction, zero_inf, fused, pitch, total, max_s = cfg
+    T_, N, V = logits.shape
+    with torch.cuda.device(logits.device):
+        _lib.check(fn(_RNNT_DTYPES[logits.dtype], _lib.ptr(logits) or None, logits.stride(0), logits.stride(1),
+                      _lib.ptr(targets) or None, int(targets.dtype == torch.int64), pitch, total, _lib.ptr(in_len) or None,
+                      _lib.ptr(tg_len) or None, int(in_len.dtype == torch.int64), N, T_, V, max_s, blank, fused, reduction,
+                      zero_inf, ws.data_ptr(), *tail, _lib.current_stream(logits.device)))
+
+
+def _ctc_forward_launch(logits: Tensor, targets: Tensor, in_len: Tensor, tg_len: Tensor, cfg,
+                        ws: Optional[Tensor] = None) -> Tuple[Tensor, Tensor]:
+    """(the reduced loss in the dtype of logits, workspace): row pass, alpha lattice, reduction.  Nothing is read back."""
+    T_, N, _ = logits.shape
+    lib = _lib.lib()
+    if ws is None:
+        ws = torch.empty((max(int(lib.aamd_ctc_loss_workspace(N, T_, cfg[5])) // 8, 1),), dtype=torch.float64, device=logits.device)
+    out = torch.empty((N,) if cfg[1] == 0 else (), dtype=logits.dtype, device=logits.device)
+    if out.numel():
+        _ctc_call(lib.aamd_ctc_loss_forward, logits, targets, in_len, tg_len, cfg, ws, out.data_ptr())
+    return out, ws
+
+
+class _CTCLossFunction(torch.autograd.Function):
+    """What is kept for backward is logits itself and the float64 workspace (denominators and alpha); the gradient is formed in
+    backward, once: a second derivative raises.  Backward turns alpha into the occupancy in place, so a second backward over
+    a retained graph runs the forward launches again first."""
+
+    @staticmethod
+    def forward(ctx, logits, targets, in_len, tg_len, cfg):
+        out, ws = _ctc_forward_launch(logits, targets, in_len, tg_len, cfg)
+        ctx.save_for_backward(logits, targets, in_len, tg_len, ws)
+        ctx.ctc, ctx.spent = cfg, False
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        logits, targets, in_len, tg_len, ws = ctx.saved_tensors
+        if ctx.spent:
+            _ctc_forward_launch(logits, targets, in_len, tg_len, ctx.ctc, ws)
+        ctx.spent = True
+        grad = torch.empty(tuple(logits.shape), dtype=logits.dtype, device=logits.device)
+        if grad.numel():
+            go = grad_out.to(torch.float64).reshape(-1).contiguous()
+            _ctc_call(_lib.lib().aamd_ctc_loss_backward, logits, targets, in_len, tg_len, ctx.ctc, ws, go.data_ptr(),
+                      int(ctx.ctc[1] == 0), grad.data_ptr(), grad.stride(0), grad.stride(1))
+        return grad, None, None, None, None
+
+
+def ctc_loss(logits: Tensor, targets: Tensor, input_lengths, target_lengths, blank: int = 0, reduction: str = "mean",
+             zero_infinity: bool = False, fused_log_softmax: bool = True) -> Tensor:
+    r"""Connectionist temporal classification loss with the log-softmax fused in (reference: ``torch.nn.functional.ctc_loss``
+    of ``torch.log_softmax(logits, -1)``; shapes, argument order and reductions are its own).  ``logits`` ``(T, N, V)`` or
+    ``(T, V)``: raw logits, or log-probabilities with ``fused_log_softmax=False``; float32 / float64 / float16 / bfloat16, read
+    in place through any time and batch strides (``(N, T, V).transpose(0, 1)`` is not copied).  ``targets`` ``(N, S)`` padded or
+    1-D concatenated, ``input_lengths`` / ``target_lengths`` ``(N,)`` tensors (int32 / int64) or tuples.  Forward is one
+    streaming read of ``logits`` (online log-sum-exp per row, padding frames not read), a float64 alpha lattice per example
+    and the reduction, all on the device in a fixed order -- two calls give the same bits; backward is the beta lattice and one
+    read of ``logits`` with one write of the gradient ``softmax - occupancy`` (the reference's own form, ``exp(input) -
+    occupancy``, when not fused).  No log-probability tensor and no intermediate gradient exist.  Lengths and labels are
+    read on the device -- no synchronisation, so the call can be captured in a graph -- and an example with an impossible
+    length or label gets a NaN loss and a NaN gradient block instead of the reference's host-side error; an example with
+    fewer frames than labels plus adjacent repeats costs ``inf`` (0 and a zero gradient with ``zero_infinity``).  A plain
+    Python entry point through the C ABI: not registered as a dispatcher op."""
+    logits, targets, in_len, tg_len, cfg, unbatched = _ctc_prepare(logits, targets, input_lengths, target_lengths, blank,
+                                                                   reduction, zero_infinity, fused_log_softmax)
+    if torch.is_grad_enabled() and logits.requires_grad:
+        out = _CTCLossFunction.apply(logits, targets, in_len, tg_len, cfg)
+    else:
+        out = _ctc_forward_launch(logits.detach(), targets, in_len, tg_len, cfg)[0]
+    return out.reshape(()) if unbatched else out
 
 
 # --------------------------------------------------------------------------- #

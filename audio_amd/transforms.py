@@ -37,7 +37,8 @@ __all__ = ["Spectrogram", "InverseSpectrogram", "GriffinLim", "TimeStretch", "Pi
            "MelScale", "InverseMelScale", "MelSpectrogram", "AmplitudeToDB", "MFCC", "Resample", "FFTConvolve", "ComputeDeltas",
            "SlidingWindowCmn", "FrequencyMasking", "TimeMasking", "SpecAugment", "AddNoise", "Preemphasis", "Deemphasis",
            "Convolve", "PSD", "MVDR", "SoudenMVDR", "RTFMVDR", "RNNTLoss", "Vad", "LFCC", "SpectralCentroid", "MuLawEncoding",
-           "MuLawDecoding", "Fade", "Vol", "BarkScale", "InverseBarkScale", "BarkSpectrogram", "ChromaScale", "ChromaSpectrogram"]
+           "MuLawDecoding", "Fade", "Vol", "BarkScale", "InverseBarkScale", "BarkSpectrogram", "ChromaScale", "ChromaSpectrogram",
+           "CTCLoss"]
 
 
 class Spectrogram(torch.nn.Module):
@@ -1256,3 +1257,21 @@ class RNNTLoss(torch.nn.Module):
     def forward(self, logits: Tensor, targets: Tensor, logit_lengths: Tensor, target_lengths: Tensor) -> Tensor:
         return F.rnnt_loss(logits, targets, logit_lengths, target_lengths, self.blank, self.clamp, self.reduction,
                            self.fused_log_softmax)
+
+
+class CTCLoss(torch.nn.Module):
+    r"""CTC loss of ``(time, batch, class)`` logits (reference: ``torch.nn.CTCLoss`` on ``log_softmax``): ``F.ctc_loss`` with the
+    module's ``blank``, ``reduction``, ``zero_infinity`` and ``fused_log_softmax``; no buffers."""
+    __constants__ = ["blank", "reduction", "zero_infinity", "fused_log_softmax"]
+
+    def __init__(self, blank: int = 0, reduction: str = "mean", zero_infinity: bool = False,
+                 fused_log_softmax: bool = True) -> None:
+        super().__init__()
+        self.blank = blank
+        self.reduction = reduction
+        self.zero_infinity = zero_infinity
+        self.fused_log_softmax = fused_log_softmax
+
+    def forward(self, logits: Tensor, targets: Tensor, input_lengths, target_lengths) -> Tensor:
+        return F.ctc_loss(logits, targets, input_lengths, target_lengths, self.blank, self.reduction, self.zero_infinity,
+                          self.fused_log_softmax)

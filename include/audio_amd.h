@@ -86,6 +86,10 @@
  *   aamd_pit_permutate        F.permutation_invariant_training, F.pit_assignment, F.pit_permutate (torchmetrics' metric call on
  *                             S^2 expanded pairs and scipy's linear_sum_assignment on the host); four launches forward, one
  *                             backward, no read-back -- additions to ABI 7
+ *   aamd_ctc_loss_forward,
+ *   aamd_ctc_loss_backward    F.ctc_loss / T.CTCLoss (log_softmax followed by ctc_loss and both backwards in the reference: a
+ *                             (T, N, V) log-probability tensor and a gradient of that size in between); three launches
+ *                             forward, two backward, no read-back -- additions to ABI 7
  *   aamd_detect_pitch_f32     F.detect_pitch_frequency (_compute_nccf + _find_max_per_frame + _median_smoothing in the
  *                             reference; an addition to ABI 7 as well)
  *
@@ -1217,6 +1221,47 @@ int aamd_pit_grad(int32_t dtype, int32_t mode, const void* preds, const void* ta
 int aamd_pit_permutate(int32_t elem_bytes, const void* src, const int64_t* perm, int64_t batch, int64_t sources,
                        int64_t row_elems, int64_t src_batch_stride, int64_t src_source_stride, uint64_t fill, void* out,
                        void* stream);
+
+/* ---- CTC loss (additions to ABI 7; csrc/ctc_loss.h) --------------------------------------------------------------------- */
+
+#define AAMD_CTC_MAX_TARGET 2047     /* the longest target the lattice kernel serves */
+
+/* which 0: states per lane, 1: lanes per workgroup of the lattice kernel for targets of up to max_s labels; 2: steps its
+ * gathers run ahead; 3: AAMD_CTC_MAX_TARGET.  (The row and gradient passes take aamd_rnnt_team_width lanes per row.) */
+int32_t aamd_ctc_loss_config(int32_t which, int64_t max_s);
+
+/* Bytes of workspace: float64 denominators (max_t, batch), the alpha / occupancy blocks (max_t, 2 S_b + 1) of the examples,
+ * which take max_t * (2 * target_entries + batch) values, and per-example scalars.  Written forward, read and rewritten
+ * backward; 8-byte aligned. */
+int64_t aamd_ctc_loss_workspace(int64_t batch, int64_t max_t, int64_t target_entries);
+
+/* F.ctc_loss forward.  logits (max_t, batch, vocab) of `dtype` (AAMD_SA_*), unit class stride, stride_t / stride_n in
+ * elements: raw logits (fused_log_softmax) or log-probabilities.  targets: int32 / int64 (targets_int64), padded (batch,
+ * target_pitch) or, with target_pitch < 0, the examples' labels one after another; target_entries is their count either
+ * way.  input_lengths / target_lengths: (batch,) int32 / int64 (lengths_int64).  Everything is read on the device.  max_s:
+ * a bound on the target lengths (>= target_pitch; it picks the lattice's configuration); above AAMD_CTC_MAX_TARGET:
+ * AAMD_EUNSUPPORTED.  reduction 0: out (batch,), 1: the mean of cost / max(target_length, 1), 2: the sum, one element; out
+ * has `dtype`; zero_infinity turns an infinite cost into 0.  An example with input_length outside [0, max_t], target_length
+ * outside its row, or a live label outside [0, vocab) or equal to blank costs NaN and nothing is indexed with those values;
+ * input_length < target_length + adjacent equal labels costs inf.  Three launches (two when not fused), no atomics on
+ * floating-point values: two calls give the same bits. */
+int aamd_ctc_loss_forward(int32_t dtype, const void* logits, int64_t stride_t, int64_t stride_n, const void* targets,
+                          int32_t targets_int64, int64_t target_pitch, int64_t target_entries, const void* input_lengths,
+                          const void* target_lengths, int32_t lengths_int64, int64_t batch, int64_t max_t, int64_t vocab,
+                          int64_t max_s, int32_t blank, int32_t fused_log_softmax, int32_t reduction, int32_t zero_infinity,
+                          void* workspace, void* out, void* stream);
+
+/* The gradient of out with respect to logits, after aamd_ctc_loss_forward with the same arguments and workspace:
+ * (exp(logit - denominator) - occupancy) * grad_out[b * grad_out_stride] * (the reduction's factor), the denominator 0 when
+ * not fused, as the reference forms it.  grad_out: float64, one element (stride 0) or one per example (stride 1).  grad:
+ * (max_t, batch, vocab) of `dtype`, unit class stride.  Rows from input_length on are zeros, an example that costs NaN is
+ * NaN, one that costs inf is NaN, or zeros with zero_infinity.  Two launches; the workspace's alpha becomes the occupancy. */
+int aamd_ctc_loss_backward(int32_t dtype, const void* logits, int64_t stride_t, int64_t stride_n, const void* targets,
+                           int32_t targets_int64, int64_t target_pitch, int64_t target_entries, const void* input_lengths,
+                           const void* target_lengths, int32_t lengths_int64, int64_t batch, int64_t max_t, int64_t vocab,
+                           int64_t max_s, int32_t blank, int32_t fused_log_softmax, int32_t reduction, int32_t zero_infinity,
+                           void* workspace, const double* grad_out, int64_t grad_out_stride, void* grad, int64_t grad_stride_t,
+                           int64_t grad_stride_n, void* stream);
 
 #ifdef __cplusplus
 }

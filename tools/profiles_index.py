@@ -5,6 +5,7 @@ import re
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DESC = [
+    (r'r\d\d_.*bench_ctc_loss\..*', "tools/bench_ctc_loss.py: F.ctc_loss with reduction mean, forward and forward + backward, on (1500, 32, 32) with 200 labels, (1500, 32, 1024) with 300 and (1500, 8, 5000) with 300, float32, ragged lengths, inputs rotating over more than twice the Infinity Cache, beside torch.nn.functional.ctc_loss(torch.log_softmax(x, -1), ...) on the same device with the same autograd, both by one protocol in alternating rounds, with the allocator's peaks and the bytes of logits and gradient at 8 TB/s", 'DESIGN 4.30, README kernel table'),
     (r'r\d\d_.*bench_pit\..*', "tools/bench_pit.py: F.permutation_invariant_training with SI-SNR, forward and forward + backward, on (256, 2, 64000), (64, 4, 160000) and (16, 8, 160000) float32, inputs rotating over more than twice the Infinity Cache, beside the composition available before (S^2 expanded rows through F.scale_invariant_signal_noise_ratio, a torch maximum over the stacked permutations, the host's itertools search at S = 8) with the same autograd, both by one protocol in alternating rounds, with the allocator's peaks and the forward's fraction of two reads at 8 TB/s", 'DESIGN 4.29, README kernel table'),
     (r'r0\d_.*bench_sdr.*', "tools/bench_sdr.py: F.signal_distortion_ratio at filter_length 512 and F.scale_invariant_signal_distortion_ratio forward and forward + backward on (256, 160000), (32, 40000) and (8, 441000) float32, beside the definition restated in torch on the same device (float64 torch.fft correlations and torch.linalg.solve; the torch expression and its autograd), both by one protocol in alternating rounds over rotating input sets, with the allocator's peaks", "DESIGN 4.28, README kernel table"),
     (r'r0\d_.*stoi_kernel_stats.*', "rocprofv3 --kernel-trace --stats of 10 STOI and 10 ESTOI calls of F.stoi on (256, 100000) float32 white noise at 10 kHz (every frame kept, the most work a row can have): calls, total and mean time of the five kernels of csrc/stoi.h; the segment kernel's mean is over both modes, its minimum is STOI and its maximum ESTOI", "DESIGN 4.27"),
